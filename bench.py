@@ -66,7 +66,13 @@ def parse():
                     "change from step to step under --compact-rows exact then fall into few block classes)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the LAST timed step handed back "
+                    "(losses, gradient norm, fixed seeded samples of the returned hidden states, of the gradients and of the updated "
+                    "parameters and fp32 master weights) as DIR/<name>.npy, float32 / float64, at most 64 MB in all; rank 0 only")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1: ms_per_step is the time of one timed step")
+    return args
 
 
 def make_batch(B, L, T, device, seed, frames=1, all_generation=False, ragged=0.0):
@@ -507,6 +513,61 @@ def self_launch(n):
         raise SystemExit(rc)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SEED = 20240611
+DUMP_FLAT_SAMPLE = 1 << 20           # elements drawn from the hidden states and from the flat fp32 master weights
+DUMP_PER_TENSOR = 2048               # elements drawn from every trainable parameter and its gradient (all of them when it is smaller)
+
+
+def _sample_index(n, k, gen):
+    """Fixed positions in a flat tensor of n elements: all of them when n <= k, else k drawn with replacement from `gen`."""
+    return torch.arange(n) if n <= k else torch.randint(n, (k,), generator=gen)
+
+
+def dump_outputs(path, out, model, opt):
+    """--dump-outputs: what the last timed step handed back to its caller -- the model output (loss, the loss terms, the final hidden
+    states) and the training step's result (gradients, updated parameters, fp32 master weights) -- as float32 / float64 .npy files.
+    Large tensors are represented by samples at positions drawn from a generator under a fixed seed, in a fixed order, so two builds
+    run with the same arguments write the same positions.  Returns {name: shape}."""
+    import numpy as np
+    if hasattr(opt, "synchronize"):                              # (the host copies below wait for the current stream)
+        opt.synchronize()
+    gen = torch.Generator().manual_seed(DUMP_SEED)
+
+    def take(t, idx):
+        flat = t.detach().reshape(-1)
+        return flat[idx.to(flat.device)].float().cpu()
+
+    def scalar(x):
+        return torch.tensor([float(x)], dtype=torch.float64)
+
+    arrays = {"loss": scalar(out.loss.detach()), "loss_language": scalar(model.loss_language), "loss_image_ar": scalar(model.loss_image_ar)}
+    if hasattr(opt, "grad_norm_value"):
+        arrays["grad_norm"] = scalar(opt.grad_norm_value())
+    hs = out.hidden_states
+    arrays["hidden_states"] = take(hs, _sample_index(hs.numel(), DUMP_FLAT_SAMPLE, gen))
+    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    grads = [getattr(p, "_mm_grad_buf", None) if p.grad is None else p.grad for _, p in named]
+    pv, gv = [], []
+    for (_, p), g in zip(named, grads):
+        idx = _sample_index(p.numel(), DUMP_PER_TENSOR, gen)
+        pv.append(take(p, idx))
+        if g is not None and g.numel() == p.numel():
+            gv.append(take(g, idx))
+    arrays["params"] = torch.cat(pv)
+    if len(gv) == len(named):
+        arrays["grads"] = torch.cat(gv)
+    if isinstance(getattr(opt, "master", None), torch.Tensor):
+        arrays["master_weights"] = take(opt.master, _sample_index(opt.master.numel(), DUMP_FLAT_SAMPLE, gen))
+    total = sum(a.numel() * a.element_size() for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.numpy())
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def newest_profiles(stem):
     """profiles/r<N>_<stem>*.json, newest round first (the counter evidence the bench line cites: taken on the shipped kernels of that round)."""
     import glob
@@ -633,9 +694,10 @@ def main():
         timer.install()
         hbm_timer.install()
     step_no = [0]
+    last_out = [None]                                            # --dump-outputs: the model output of the last timed step
     from metamorph_amd import hostmirror
 
-    def step():
+    def step(keep=False):
         ids, labels, mask, images = pool[step_no[0] % n_pool]
         valid_timed[0] += pool_valid[step_no[0] % n_pool]
         step_no[0] += 1
@@ -648,6 +710,8 @@ def main():
             opt.arm_overlap()                                    # no accumulation: these gradients are final
         out.loss.backward()
         opt.step()
+        if keep:
+            last_out[0] = out
         return out.loss
 
     loss_first = None                                            # loss of the very first step: the model as built, before any update
@@ -664,8 +728,8 @@ def main():
     if dist_run and hasattr(opt, "comm_timing"):
         opt.comm_timing = True                                   # HIP events around the parts of step() that wait for RCCL
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        loss = step(keep=args.dump_outputs is not None and i == args.steps - 1)
         loss_first = loss.detach() if loss_first is None else loss_first
     torch.cuda.synchronize()
     if world > 1:
@@ -678,6 +742,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
     loss_val = float(loss.detach())
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:              # before anything below runs another step
+        dumped = dump_outputs(args.dump_outputs, last_out[0], model, opt)
+        last_out[0] = None
     comm = opt.comm_summary(args.steps) if (dist_run and hasattr(opt, "comm_summary")) else None
     if comm is not None:
         opt.comm_timing = False
@@ -808,6 +876,8 @@ def main():
         }
         if roofline:
             rec["roofline"] = roofline
+        if dumped:
+            rec["dumped_outputs"] = dumped
         # the pre-registered multi-GPU expectation: at one rank for 2 / 4 / 8 ranks from THIS run's step time, at N > 1
         # for this N from the committed one-rank reference -- beside the measured `ms_per_step`
         seg_b, tail_b = 218_112_000 * 2.0, (n_params - 32 * 218_112_000) * 2.0 if args.layers == 32 else 0.0

@@ -1100,6 +1100,60 @@ def test_pre_registered_multi_gpu_prediction_model():
     assert 7.0 <= last["ring"]["scaling_vs_one_rank"] <= 7.7 and 7.8 <= last["direct"]["scaling_vs_one_rank"] <= 8.2, last
 
 
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(REPO, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    return b
+
+
+def test_bench_refuses_zero_timed_steps(monkeypatch):
+    b = _bench_module()
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "3", "--warmup", "0", "--dump-outputs", "d"])
+    a = b.parse()
+    assert a.steps == 3 and a.warmup == 0 and a.dump_outputs == "d"
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        b.parse()
+
+
+def test_bench_dump_outputs_is_a_fixed_sample_within_the_size_limit(tmp_path):
+    """bench.dump_outputs on stand-in objects: float32 / float64 .npy files, the same positions on every call, parameters and gradients
+    sampled at the same positions, small tensors whole, at most 64 MB in all."""
+    b = _bench_module()
+    g = torch.Generator().manual_seed(5)
+    big = torch.nn.Parameter(torch.randn(3000, 7, generator=g).to(torch.bfloat16))
+    small = torch.nn.Parameter(torch.randn(10, generator=g).to(torch.bfloat16))
+    frozen = torch.nn.Parameter(torch.randn(50, generator=g), requires_grad=False)
+    big._mm_grad_buf = big.detach().float() * 2           # a gradient kept outside .grad, as Zero2AdamW keeps it
+    small.grad = small.detach() * 4
+    model = SimpleNamespace(named_parameters=lambda: [("big", big), ("frozen", frozen), ("small", small)], loss_language=1.5,
+                            loss_image_ar=float("nan"))
+    opt = SimpleNamespace(master=torch.randn(3 << 20, generator=g), grad_norm_value=lambda: 0.25)
+    out = SimpleNamespace(loss=torch.tensor(2.0), hidden_states=torch.randn(2, 600, 1000, generator=g).to(torch.bfloat16))
+    shapes = b.dump_outputs(str(tmp_path / "a"), out, model, opt)
+    b.dump_outputs(str(tmp_path / "b"), out, model, opt)
+    names = {"loss", "loss_language", "loss_image_ar", "grad_norm", "hidden_states", "params", "grads", "master_weights"}
+    assert set(shapes) == names and sorted(os.listdir(tmp_path / "a")) == sorted(n + ".npy" for n in names)
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert x.dtype in (np.float32, np.float64) and list(x.shape) == shapes[n], n
+        assert np.array_equal(x, y, equal_nan=True), n
+        total += x.nbytes
+    assert total <= 64 << 20
+    d = tmp_path / "a"
+    assert np.load(d / "loss.npy").tolist() == [2.0] and np.load(d / "grad_norm.npy").tolist() == [0.25]
+    assert np.load(d / "loss_language.npy").tolist() == [1.5] and np.isnan(np.load(d / "loss_image_ar.npy")).all()
+    assert shapes["hidden_states"] == [b.DUMP_FLAT_SAMPLE] and shapes["master_weights"] == [b.DUMP_FLAT_SAMPLE]
+    params, grads = np.load(d / "params.npy"), np.load(d / "grads.npy")
+    assert params.shape == (b.DUMP_PER_TENSOR + 10,)                  # the frozen parameter is not part of the training step's result
+    np.testing.assert_array_equal(params[-10:], small.detach().float().numpy())      # small tensors whole, in order
+    np.testing.assert_array_equal(grads, np.concatenate([params[:-10] * 2, params[-10:] * 4]).astype(np.float32))
+    assert set(params[:-10].tolist()) <= set(big.detach().float().reshape(-1).tolist())
+
+
 def test_decode_attention_bound_follows_the_host_known_lengths():
     """mm355_attn_decode sizes its launch by an upper bound on the cached lengths: 1024 (one key group, one workgroup per query head) while
     every sequence INCLUDING the row about to be appended fits, the cache's capacity afterwards; a cache smaller than 1024 rows is its own

@@ -1000,6 +1000,31 @@ def test_bench_emits_the_driver_contract_on_device():
     assert r["batch_pool"] >= 8 and math.isfinite(r["loss"])
 
 
+def test_bench_dumps_what_its_last_timed_step_computed(tmp_path):
+    """`bench.py ... --steps 3 --dump-outputs DIR` times exactly 3 steps and writes the last one's results: the loss of the JSON line, the
+    loss terms, finite hidden-state / parameter / master-weight samples and non-zero gradients, float32 / float64, at most 64 MB."""
+    import json
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--layers", "2", "--vit-layers", "2", "--steps", "3", "--warmup", "1", "--batch", "2",
+                        "--no-cpu-baseline", "--no-kernel-timing", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900, cwd=repo)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    r = json.loads(lines[0])
+    assert r["steps"] == 3 and r["ms_per_step"] > 0
+    names = {"loss", "loss_language", "loss_image_ar", "grad_norm", "hidden_states", "params", "grads", "master_weights"}
+    assert set(r["dumped_outputs"]) == names and sorted(os.listdir(d)) == sorted(n + ".npy" for n in names)
+    a = {n: np.load(d / f"{n}.npy") for n in names}
+    assert all(x.dtype in (np.float32, np.float64) and list(x.shape) == r["dumped_outputs"][n] for n, x in a.items())
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert abs(float(a["loss"][0]) - r["loss"]) <= 1e-4 * max(1.0, abs(r["loss"]))
+    assert all(np.isfinite(a[n]).all() for n in names - {"loss_image_ar"})
+    assert np.abs(a["grads"]).max() > 0 and a["grad_norm"][0] > 0 and a["params"].shape == a["grads"].shape
+
+
 # ------------------------------------------------------------------ BASELINE configs[0] geometry class (TinyLlama: d = 64, GQA 8:1)
 D64_HIDDEN_TOL, D64_GRAD_TOL = 9.5e-3, 2.2e-2          # 1.5 x measured (6.3e-3, 1.44e-2)
 
