@@ -50,9 +50,10 @@ const char* mm355_strerror(int code);
  *             if ACCUMULATE v += C_old[m][n];  store as bf16 (or f32 with OUT_F32).
  * Requirements: K % 8 == 0, lda/ldb % 8 == 0 (ldc/ldr % 8 == 0 for bf16 vector stores, else scalar tail).
  * variant: 0 = auto (ping-pong 256x256 kernel, variant 11, once >= 200 tiles and K % 64 == 0; 128x128 LDS-DMA otherwise);
- *          1..mm355_gemm_num_variants() select a specific tile configuration / schedule (bench / tests); 13 = the one-wave-per-SIMD
- *          kernel (csrc/gemm_st.hip: persistent 4-wave workgroups, 128 x 128 wave tiles, hand-placed stream; K % 128 == 0, K >= 256,
- *          MM355_EUNSUPPORTED otherwise), 14 = the same stream serialised -- both bit-identical to 11.
+ *          for bench / tests: 1 = 128x128 register-staged (any K % 8 == 0), 2 = 128x128 LDS-DMA, 7 = 256x256 LDS-DMA software-pipelined,
+ *          9 = 64x128 LDS-DMA, 11 = the 256x256 ping-pong kernel (falls back to 7 when K % 128 != 0 or an offset passes 2 GiB); 2, 7, 9 and 11
+ *          need K % 64 == 0.  Any other number returns MM355_EUNSUPPORTED (mm355_gemm_num_variants() keeps the numbering of the
+ *          retired ones).
  * ------------------------------------------------------------------------------------------------ */
 #define MM355_GEMM_BIAS        1u
 #define MM355_GEMM_GELU_ERF    2u    /* nn.GELU() default (projector, vision_head)         */
@@ -243,10 +244,10 @@ int mm355_attn_fwd(const mm355_bf16* q, const mm355_bf16* k, const mm355_bf16* v
                    int64_t B, int64_t L, int64_t Hq, int64_t Hkv, int64_t d, float scale, int causal, void* stream);
 
 /* mm355_attn_fwd with the kernel generation chosen by the caller -- for tests and tools/ (A/B timing, the serialised debugging stream);
- * the product calls mm355_attn_fwd.  variant: 0 = as mm355_attn_fwd; 2 = the generic-d kernels; 3 = the round-2 two-waves-per-SIMD d == 128 kernels
- * (-DMM355_LEGACY_VARIANTS builds only); 4 = the one-wave-per-SIMD
+ * the product calls mm355_attn_fwd.  variant: 0 = as mm355_attn_fwd; 2 = the generic-d kernels; 4 = the one-wave-per-SIMD
  * hand-placed stream (d == 128); 41 = the same stream serialised (every LDS read waited for at once, 32 wait states behind every MFMA:
- * bit-identical to 4 by construction).  MM355_EUNSUPPORTED when the variant does not cover the geometry.  Same reference call site as
+ * bit-identical to 4 by construction).  MM355_EUNSUPPORTED when the variant does not cover the geometry, and for variant 3 (a retired
+ * kernel generation); MM355_EINVAL for any other number.  Same reference call site as
  * mm355_attn_fwd (torch SDPA reached at metamorph_llama.py:349-359). */
 int mm355_attn_fwd_variant(const mm355_bf16* q, const mm355_bf16* k, const mm355_bf16* v, int64_t ld_q, int64_t ld_k,
                            mm355_bf16* o, int64_t ld_o, float* lse, const int32_t* seqlens,
@@ -291,9 +292,8 @@ int mm355_attn_bwd_rope(const mm355_bf16* q, const mm355_bf16* k, const mm355_bf
 
 /* The general form: mm355_attn_bwd (cos_t = sin_t = NULL) or mm355_attn_bwd_rope (tables given) with the kernel generation chosen by the
  * caller: variant 0 = the product's choice; for tests / tools 2 = the generic-d kernels (under GQA their 2*B*L*Hq*d workspace is the
- * caller's to provide), 3 = the round-2 two-waves-per-SIMD d == 128 kernels (only in -DMM355_LEGACY_VARIANTS builds, MM355_EUNSUPPORTED
- * otherwise), 4 = the one-wave-per-SIMD hand-placed streams (d == 128, workspace required), 41 = the same streams serialised
- * (bit-identical to 4 by construction).
+ * caller's to provide), 4 = the one-wave-per-SIMD hand-placed streams (d == 128, workspace required), 41 = the same streams serialised
+ * (bit-identical to 4 by construction).  Variant 3 (a retired kernel generation) returns MM355_EUNSUPPORTED, any other number MM355_EINVAL.
  * Same reference call site as mm355_attn_bwd (backward of torch SDPA reached at metamorph_llama.py:349-359). */
 int mm355_attn_bwd_variant(const mm355_bf16* q, const mm355_bf16* k, const mm355_bf16* v, int64_t ld_q, int64_t ld_k,
                            const mm355_bf16* d_o, int64_t ld_o, const float* lse, const float* delta, const int32_t* seqlens,

@@ -1,4 +1,4 @@
-// Shared argument block of the second-generation attention kernels (attn2.hip), launched from attn.hip.
+// Shared argument block and device helpers of the attention kernels (attn2.hip, attn4.hip, attn4_bwd.hip), launched from attn.hip.
 #pragma once
 #include "mm355_common.h"
 
@@ -104,16 +104,35 @@ MM_DEV float quad_sum(float x) {
     swap32(a, b);
     return a + b;
 }
+
+// LDS pointer operand of the LDS-DMA builtins (attn4*.hip)
+typedef __attribute__((address_space(3))) void* lptr_t;
+
+// 1-D grid -> (x, head, sample) with all blocks that share K / V (fwd, dQ: the query blocks of a GQA group) or Q / dO (dK/dV:
+// the key blocks of a query head) on ONE XCD, so the shared tiles stay in that XCD's 4-MiB L2: hardware deals consecutive
+// block ids round-robin over the 8 XCDs, so XCD x is given the x-th contiguous eighth of the logical order.
+// Logical order: `inner` heads fastest, then x, then the remaining heads, then the sample; `reverse` walks x downwards.  Causal
+// work grows with the query block index (fwd, dQ) and shrinks with the key block index (dK/dV): with x SLOWER than a few heads, the
+// heavy blocks of several heads start together and the light ones fill the tail.  (x fastest -- 15, 14, ..., 0 per head -- leaves
+// the last head's heaviest block to start late: 7 % / 13 % longer kernels in a dispatch simulation with measured block times.)
+MM_DEV void block_coords(int nx, int H, int inner, bool reverse, int& x, int& h, int& b) {
+    const int total = gridDim.x, bid = blockIdx.x;
+    const int q8 = total >> 3, r8 = total & 7, xcd = bid & 7, idx = bid >> 3;
+    const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
+    const int span = nx * inner, within = logical % span, rest = logical / span, outer = H / inner;
+    const int xx = within / inner;
+    x = reverse ? nx - 1 - xx : xx;
+    h = (rest % outer) * inner + within % inner;
+    b = rest / outer;
+}
+// heads walked fastest: the GQA group (its blocks share K / V), else four heads when they divide evenly
+MM_DEV int inner_heads(int H, int group) { return group > 1 ? group : ((H & 3) == 0 ? 4 : ((H & 1) == 0 ? 2 : 1)); }
 #endif
 }  // namespace attn2
 
 int mm355_attn2_fwd_launch(const attn2::Args& a, int dp, hipStream_t s);
 int mm355_attn2_dq_launch(const attn2::Args& a, int dp, hipStream_t s);
 int mm355_attn2_dkdv_launch(const attn2::Args& a, int dp, hipStream_t s);
-// d == 128 fast paths (attn3.hip): LDS-DMA staged, double-buffered
-int mm355_attn3_fwd_launch(const attn2::Args& a, hipStream_t s);
-int mm355_attn3_dq_launch(const attn2::Args& a, hipStream_t s);
-int mm355_attn3_dkdv_launch(const attn2::Args& a, hipStream_t s);
 // d == 128 forward, one wave per SIMD, hand-placed stream (attn4.hip); variant 1 = the serialised debugging stream
 int mm355_attn4_fwd_launch(const attn2::Args& a, int variant, hipStream_t s);
 // d == 128 backward (dK / dV then dQ), same construction (attn4_bwd.hip); workspace: 2 * B * Hq * L floats

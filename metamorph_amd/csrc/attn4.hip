@@ -18,7 +18,7 @@
 //   * software pipeline per wave: step t = { QK(t + 1) || exponentials + packing of tile t || V reads }  { PV(t) || row sums of tile t ||
 //     row maxima of tile t + 1 || K reads || DMA of tiles t + 3 / t + 2 }; a wave's last tile (the only masked one) drains unpipelined
 // Replaces torch SDPA as driven by HF LlamaModel (reference call site metamorph_llama.py:349-359).
-#include "attn3_kernels.h"
+#include "attn2.h"
 
 // the generated streams; timing-only ablation builds (tools/gen_attn4.py --abl ...) compile with -DATTN4_GEN_DIR=attn4_gen_<name>
 #ifndef ATTN4_GEN_DIR
@@ -30,9 +30,6 @@
 
 namespace attn4 {
 using namespace attn2;
-using attn3::block_coords;
-using attn3::inner_heads;
-using attn3::lptr_t;
 
 constexpr int TILE = 16384;                                  // [64 rows][128] bf16
 constexpr int VRING = 2 * TILE;                              // K slots 0, 1 | V slots 0, 1

@@ -14,7 +14,7 @@
 //     software pipeline (the group sum happens in the accumulators: no partials, no atomics); dQ: workgroup = 128 query rows (4 x 32)
 //   * scale is applied once to the finished accumulators; the inverse RoPE rotation of dq / dk (mm355_attn_bwd_rope) in the epilogues
 // Replaces the backward of torch SDPA as driven by HF LlamaModel (reference call site metamorph_llama.py:349-359).
-#include "attn3_kernels.h"
+#include "attn2.h"
 
 #ifndef ATTN4B_GEN_DIR
 #define ATTN4B_GEN_DIR attn4_bwd_gen
@@ -25,9 +25,6 @@
 
 namespace attn4b {
 using namespace attn2;
-using attn3::block_coords;
-using attn3::inner_heads;
-using attn3::lptr_t;
 
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr int SLOT = 32768;                                  // kv: Q tile | dO tile;  q: K tile | V tile

@@ -547,150 +547,6 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_nt_kernel(GemmArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Ring-pipelined 256x256 kernel: the K dimension is consumed in HALF tiles (BK = 32) from a ring of four 32-KiB LDS
-// slots.  Measurements (timing-only ablation builds, since removed) suggested that the cost of the staging is the BURST: when all eight waves
-// issue their LDS-DMAs right after a barrier they queue in the texture path and no wave issues MFMAs meanwhile.  Here
-//   * each wave issues its 4 DMA pieces of half-tile s+3 two at a time IN BETWEEN its 16-MFMA units,
-//   * waits are counted (s_waitcnt vmcnt(8): the two most recent half-tiles may still be in flight), never a drain,
-//   * a raw s_barrier per half-tile (32 MFMAs per wave) publishes half-tile s+1 and frees slot s for the DMA of s+4.
-// LDS half-tile layout: [512 rows (A then B)][32 bf16] (64-B rows); physical 16-B chunk = logical ^ 3*((row>>3)&1), which
-// makes every ds_read_b128 fragment read conflict free; the DMA applies the same XOR on its per-lane source address.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(512) void gemm_nt_ring_kernel(GemmArgs a) {
-    constexpr int BM = 256, BN = 256, WM = 2, WN = 4, NW = 8;
-    constexpr int TM = BM / WM, TN = BN / WN, FM = TM / 16, FN = TN / 16, HM = FM / 2;
-    constexpr int SLOT = (BM + BN) * 64;                    // 32 KiB
-    constexpr int A_BYTES = BM * 64;
-    constexpr int GM = 8;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-
-    const int total = a.ntm * a.ntn;
-    const int bid = blockIdx.x;
-    const int q8 = total >> 3, r8 = total & 7;
-    const int xcd = bid & 7, idx = bid >> 3;
-    const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-    const int gsize = GM * a.ntn;
-    const int grp = logical / gsize;
-    const int first_m = grp * GM;
-    const int gm = min(a.ntm - first_m, GM);
-    const int in_g = logical - grp * gsize;
-    const int tm = first_m + in_g % gm;
-    const int tn = in_g / gm;
-    const int m0 = tm * BM, n0 = tn * BN;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-    const int wm = wave_s / WN, wn = wave_s % WN;
-    const int fr = lane & 15, fq = lane >> 4;
-    const int M = a.M, N = a.N;
-    const int nh = a.K >> 5;                                 // half tiles (K % 64 == 0 => nh even, >= 2)
-
-    f32x4 acc[FM][FN];
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // DMA sources: half tile = 512 rows x 64 B = 32 pieces of 1 KiB (16 rows each); wave w owns pieces w, w+8, w+16, w+24
-    // (pieces 0..15 = A rows, 16..31 = B rows)
-    const uint16_t* src[4];
-    {
-        const int rin = lane >> 2;                           // row inside the 16-row piece
-        const int c = (lane & 3) ^ (3 * ((rin >> 3) & 1));   // logical chunk that belongs in physical slot (lane & 3)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int piece = i * NW + wave_s;
-            const int row = (piece & 15) * 16 + rin;
-            src[i] = (piece < 16) ? a.A + (int64_t)min(m0 + row, M - 1) * a.lda + c * 8
-                                  : a.B + (int64_t)min(n0 + row, N - 1) * a.ldb + c * 8;
-        }
-    }
-    auto dma = [&](int s, int i) {                           // piece i of half tile s
-        unsigned char* slot = smem + (s & 3) * SLOT + (i * NW + wave_s) * 1024;
-        __builtin_amdgcn_global_load_lds((gptr_t)(src[i] + (s << 5)), (lptr_t)slot, 16, 0, 0);
-    };
-    const int sw = (fq ^ (3 * ((fr >> 3) & 1))) << 4;
-    const int a_off = (wm * TM + fr) * 64 + sw;
-    const int b_off = A_BYTES + (wn * TN + fr) * 64 + sw;
-    bf16x8 X[HM], Y[HM], P[FN];
-    auto rdA = [&](bf16x8 (&af)[HM], int s, int half) {
-        const unsigned char* sb = smem + (s & 3) * SLOT + a_off + half * HM * 1024;
-#pragma unroll
-        for (int i = 0; i < HM; ++i) af[i] = *(const bf16x8*)(sb + i * 1024);
-    };
-    auto rdB = [&](bf16x8 (&bf)[FN], int s) {
-        const unsigned char* sb = smem + (s & 3) * SLOT + b_off;
-#pragma unroll
-        for (int j = 0; j < FN; ++j) bf[j] = *(const bf16x8*)(sb + j * 1024);
-    };
-    auto mm = [&](const bf16x8 (&af)[HM], const bf16x8 (&bf)[FN], int half) {
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = 0; i < HM; ++i)
-#pragma unroll
-            for (int j = 0; j < FN; ++j)
-                acc[half * HM + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bf[j], acc[half * HM + i][j], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
-    };
-
-    // one half tile: MODE 0 = steady state (issue s+3, keep 8 in flight), 1 = two tiles still in flight after this one,
-    // 2 = last staged tile is the next one (drain), 3 = final half tile (nothing to fetch or publish)
-    auto step = [&](auto mode_c, int s, bf16x8 (&Pc)[FN], bf16x8 (&Pn)[FN]) {
-        constexpr int MODE = decltype(mode_c)::value;
-        rdA(Y, s, 1);
-        if constexpr (MODE == 0) { dma(s + 3, 0); dma(s + 3, 1); }
-        __builtin_amdgcn_sched_barrier(0);
-        mm(X, Pc, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (MODE == 0) {
-            dma(s + 3, 2); dma(s + 3, 3);
-            asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-        } else if constexpr (MODE == 1) {
-            asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-        } else if constexpr (MODE == 2) {
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        }
-        if constexpr (MODE != 3) {
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            rdA(X, s + 1, 0);
-            rdB(Pn, s + 1);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        mm(Y, Pc, 1);
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    using M0 = std::integral_constant<int, 0>;
-    using M1 = std::integral_constant<int, 1>;
-    using M2 = std::integral_constant<int, 2>;
-    using M3 = std::integral_constant<int, 3>;
-    bf16x8 Q[FN];
-
-    // prologue: half tiles 0, 1, 2 in flight; wait for 0   (host guarantees nh >= 4)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) dma(0, i);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) dma(1, i);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) dma(2, i);
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    rdA(X, 0, 0);
-    rdB(P, 0);
-    int s = 0;
-    for (; s < nh - 4; s += 2) {
-        step(M0{}, s, P, Q);
-        step(M0{}, s + 1, Q, P);
-    }
-    step(M0{}, s, P, Q);
-    step(M1{}, s + 1, Q, P);
-    step(M2{}, s + 2, P, Q);
-    step(M3{}, s + 3, Q, P);
-    __syncthreads();
-    gemm_epilogue<TM, TN, FM, FN>(acc, a, smem, m0, n0, wm, wn, wave, lane);
-}
-
-// ------------------------------------------------------------------------------------------------
 // Ping-pong 256x256x64 kernel.  The eight waves form two groups (wave w and w + 4 share a SIMD; group = M half of the tile)
 // that run ONE BARRIER APART: while one group issues its 16-MFMA cluster (one 64x32 quadrant of its 128x64 output x K = 64),
 // the other does everything else (fragment ds_reads for its next cluster, two LDS-DMA pieces, counted waits), then they swap.
@@ -1039,179 +895,6 @@ __global__ __launch_bounds__(512) void gemm_pp_swiglu_bwd_kernel(GemmArgs a) {
     gemm_pp_tile<false, false, 0, false, true>(a, blockIdx.x, smem);
 }
 
-// ------------------------------------------------------------------------------------------------
-// Two-phase form of the ping-pong tile (row-major operands): the same two wave groups one barrier apart, but a K tile is TWO phases of
-// 32 MFMAs instead of four of 16, i.e. half as many hand-overs between the groups per unit of matrix work:
-//        phase   quadrants                 fragments read in the load section          LDS-DMA issued in the load section
-//        X(t)    (a0,b0) (a0,b1)           B cols blocks 0, 1 of tile t (8 reads)      A rows block 0 of t+2, A rows block 1 of t+1
-//        Y(t)    (a1,b1) (a1,b0)           A rows block 1 of t, block 0 of t+1 (16)    B cols blocks 0, 1 of t+2
-// Ring = two K tiles as in gemm_pp_tile; a quarter is re-issued in the first load section after its last reader (of either group)
-// has passed, is waited for (counted vmcnt(8): the two quarters of this phase and of the one before stay in flight) at the end of
-// the load section that precedes its first read, and is published by the barrier that follows.  Same accumulation order per output
-// element as gemm_pp_tile: bit-identical results.
-// ------------------------------------------------------------------------------------------------
-MM_DEV void gemm_pp2_tile(const GemmArgs& a, const int bid, unsigned char* smem) {
-    constexpr int BM = 256, BN = 256, TM = 128, TN = 64, FM = 8, FN = 4;
-    constexpr int BUF = (BM + BN) * 128;
-    constexpr int A_BYTES = BM * 128;
-
-    const int total = a.ntm * a.ntn;
-    const int q8 = total >> 3, r8 = total & 7;
-    const int xcd = bid & 7, idx = bid >> 3;
-    const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-    const int GM = a.gm;
-    const int gsize = GM * a.ntn;
-    const int grp = logical / gsize;
-    const int first_m = grp * GM;
-    const int gm = min(a.ntm - first_m, GM);
-    const int in_g = logical - grp * gsize;
-    const int tm = first_m + in_g % gm;
-    const int tn = in_g / gm;
-    const int m0 = tm * BM, n0 = tn * BN;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-    const int wm = wave_s >> 2, wn = wave_s & 3;
-    const int fr = lane & 15, fq = lane >> 4;
-    const int M = a.M, N = a.N;
-    const int nk = a.K >> 6;                                 // host guarantees K % 128 == 0, K >= 128
-
-    f32x4 acc[FM][FN];
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // quarter kinds as in gemm_pp_tile: 0 = A rows block 0, 1 = B cols block 0, 2 = B cols block 1, 3 = A rows block 1
-    uint32_t src[4][2];
-    int dst[4][2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int q = wave_s + 8 * h;
-#pragma unroll
-        for (int kd = 0; kd < 4; ++kd) {
-            const bool isA = kd == 0 || kd == 3;
-            const int blk = isA ? (kd == 3) : (kd - 1);
-            const int rin = lane >> 3, c = (lane & 7) ^ rin;
-            if (isA) {
-                const int row = h * 128 + blk * 64 + wave_s * 8;
-                src[kd][h] = (uint32_t)((int64_t)(min(m0 + row + rin, M - 1) - m0) * a.lda * 2 + c * 16);
-                dst[kd][h] = row * 128;
-            } else {
-                const int row = (q >> 2) * 64 + blk * 32 + (q & 3) * 8;
-                src[kd][h] = (uint32_t)((int64_t)(min(n0 + row + rin, N - 1) - n0) * a.ldb * 2 + c * 16);
-                dst[kd][h] = A_BYTES + row * 128;
-            }
-        }
-    }
-    const uint16_t* baseA = a.A + (int64_t)m0 * a.lda;
-    const uint16_t* baseB = a.B + (int64_t)n0 * a.ldb;
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)baseA, 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)baseB, 0, 0x7fffffff, 0x00020000);
-    auto issue = [&](int kd, int tile) {
-        unsigned char* sb = smem + (tile & 1) * BUF;
-        const bool isA = kd == 0 || kd == 3;
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(isA ? rsA : rsB, (lptr_t)(sb + dst[kd][h]), 16, src[kd][h], tile * 128, 0, 0);
-    };
-
-    const int sw0 = ((fq) ^ (fr & 7)) << 4;
-    const int sw1 = ((4 + fq) ^ (fr & 7)) << 4;
-    const int a_off = (wm * TM + fr) * 128;
-    const int b_off = A_BYTES + (wn * TN + fr) * 128;
-    bf16x8 A[2][4][2], B[2][2][2];
-    auto rdA = [&](int ah, int tile) {
-        const unsigned char* sb = smem + (tile & 1) * BUF + a_off + ah * 8192;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            A[ah][i][0] = *(const bf16x8*)(sb + i * 2048 + sw0);
-            A[ah][i][1] = *(const bf16x8*)(sb + i * 2048 + sw1);
-        }
-    };
-    auto rdB = [&](int bh, int tile) {
-        const unsigned char* sb = smem + (tile & 1) * BUF + b_off + bh * 4096;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            B[bh][j][0] = *(const bf16x8*)(sb + j * 2048 + sw0);
-            B[bh][j][1] = *(const bf16x8*)(sb + j * 2048 + sw1);
-        }
-    };
-    // one phase.  YP: false = X, true = Y;  VM = vmcnt kept in flight;  I0 / I1: issue the phase's first / second quarter
-    // (X: A0 of t+2 / A1 of t+1;  Y: B0 / B1 of t+2);  NEXTA: tile t+1 exists (Y reads its A rows block 0)
-    auto phase = [&](auto y_c, auto vm_c, auto i0_c, auto i1_c, auto nexta_c, int t) {
-        constexpr bool YP = decltype(y_c)::value, I0 = decltype(i0_c)::value, I1 = decltype(i1_c)::value, NEXTA = decltype(nexta_c)::value;
-        constexpr int VM = decltype(vm_c)::value;
-        constexpr int ah = YP ? 1 : 0;
-        if constexpr (!YP) {
-            rdB(0, t);
-            rdB(1, t);
-            if constexpr (I0) issue(0, t + 2);
-            if constexpr (I1) issue(3, t + 1);
-        } else {
-            rdA(1, t);
-            if constexpr (NEXTA) rdA(0, t + 1);
-            if constexpr (I0) issue(1, t + 2);
-            if constexpr (I1) issue(2, t + 2);
-        }
-        wait_vmcnt<VM>();
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int hb = 0; hb < 2; ++hb) {
-            const int bh = YP ? 1 - hb : hb;                 // X: (a0,b0) (a0,b1);  Y: (a1,b1) (a1,b0)
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[ah * 4 + i][bh * 2 + j] =
-                            __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[ah][i][kk], B[bh][j][kk], acc[ah * 4 + i][bh * 2 + j], 0, 0, 0);
-        }
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-    };
-    using I0_ = std::integral_constant<int, 0>; using I2_ = std::integral_constant<int, 2>;
-    using I6_ = std::integral_constant<int, 6>; using I8_ = std::integral_constant<int, 8>;
-    using T = std::true_type; using F = std::false_type;
-
-    // prologue: tiles 0 and 1 in flight except A rows block 1 of tile 1 (issued by X(0)); first needed: A0, B0, B1 of tile 0
-    issue(0, 0); issue(1, 0); issue(2, 0);
-    issue(3, 0); issue(0, 1);
-    issue(1, 1); issue(2, 1);
-    wait_vmcnt<8>();
-    __builtin_amdgcn_s_barrier();
-    rdA(0, 0);
-    // X(0) re-issues the A rows block 0 slot of buffer 0 (for tile 2) right away: every wave's read of it must have completed
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (wm == 1) __builtin_amdgcn_s_barrier();               // the second group runs one barrier behind the first
-
-    int t = 0;
-    for (; t + 2 < nk; ++t) {                                // steady state
-        phase(F{}, I8_{}, T{}, T{}, T{}, t);
-        phase(T{}, I8_{}, T{}, T{}, T{}, t);
-    }
-    // t = nk - 2: only A rows block 1 of the last tile is still to be issued; then the ring drains
-    phase(F{}, I6_{}, F{}, T{}, T{}, t);
-    phase(T{}, I2_{}, F{}, F{}, T{}, t);
-    phase(F{}, I0_{}, F{}, F{}, F{}, t + 1);
-    phase(T{}, I0_{}, F{}, F{}, F{}, t + 1);
-    if (wm == 0) __builtin_amdgcn_s_barrier();               // the first group catches the barrier count up
-    __syncthreads();
-    gemm_epilogue<TM, TN, FM, FN>(acc, a, smem, m0, n0, wm, wn, wave, lane);
-}
-
-__global__ __launch_bounds__(512) void gemm_pp2_kernel(GemmArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    gemm_pp2_tile(a, blockIdx.x, smem);
-}
-
 template <bool TA, bool TB, int ABL = 0>
 __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1285,39 +968,10 @@ bool pp_eligible(const GemmArgs& a, bool ta, bool tb) {
     return ea < 0x7fffffffLL && eb < 0x7fffffffLL;
 }
 
-#ifdef MM355_LEGACY_VARIANTS
-int launch_gemm_pp2(GemmArgs a, hipStream_t s) {
-    if (!pp_eligible(a, false, false)) return launch_gemm<256, 256, 2, 4, true, 1, false>(a, s);
-    static std::atomic<uint64_t> lds_ok{0};
-    if (mm_ensure_dynamic_lds((const void*)gemm_pp2_kernel, PP_LDS, lds_ok) != MM355_OK) return MM355_ELAUNCH;
-    const int64_t total = pp_prepare(a);
-    if (total <= 0 || total > 0x7fffffff) return MM355_EINVAL;
-    hipLaunchKernelGGL(gemm_pp2_kernel, dim3((unsigned)total), dim3(512), PP_LDS, s, a);
-    return mm_launch_status();
-}
-
-#endif
-
 int launch_gemm_pp(GemmArgs a, hipStream_t s) {
     if (!pp_eligible(a, false, false)) return launch_gemm<256, 256, 2, 4, true, 1, false>(a, s);
     return launch_gemm_pp_t<false, false>(a, s);
 }
-
-#ifdef MM355_LEGACY_VARIANTS
-int launch_gemm_ring(GemmArgs a, hipStream_t s) {
-    if (a.K < 128) return launch_gemm<256, 256, 2, 4, true, 0, false>(a, s);
-    constexpr int LDS = 4 * (256 + 256) * 64;               // 128 KiB
-    static std::atomic<uint64_t> lds_ok{0};              // per-device opt-in to > 64 KiB of dynamic LDS
-    if (mm_ensure_dynamic_lds((const void*)gemm_nt_ring_kernel, LDS, lds_ok) != MM355_OK) return MM355_ELAUNCH;
-    a.ntm = (a.M + 255) / 256;
-    a.ntn = (a.N + 255) / 256;
-    const int64_t total = (int64_t)a.ntm * a.ntn;
-    if (total <= 0 || total > 0x7fffffff) return MM355_EINVAL;
-    hipLaunchKernelGGL(gemm_nt_ring_kernel, dim3((unsigned)total), dim3(512), LDS, s, a);
-    return mm_launch_status();
-}
-
-#endif
 
 template <int BM, int BN, int WM, int WN, bool GLDS, int PIPE = 0, bool TNL = false>
 int launch_gemm(GemmArgs a, hipStream_t s) {
@@ -1727,15 +1381,6 @@ extern "C" int mm355_gemm_splitk_rope_append_bf16(const mm355_bf16* X, int64_t l
 
 extern "C" int mm355_gemm_num_variants(void) { return 14; }
 
-int mm355_gemm_st_launch(const void* args, int serialised, void* stream);   // gemm_st.hip: one wave per SIMD, hand-placed stream
-
-#ifdef MM355_LEGACY_VARIANTS
-namespace {
-// the stream kernel moves whole pairs of K stages and fetches two stages ahead: K % 128 == 0, K >= 256, 31-bit tile-relative offsets
-bool st_eligible(const GemmArgs& a) { return a.K >= 256 && pp_eligible(a, false, false); }
-}  // namespace
-#endif
-
 extern "C" int mm355_gemm_bf16(const mm355_bf16* A, int64_t lda, const mm355_bf16* B, int64_t ldb, void* C, int64_t ldc,
                                int64_t M, int64_t N, int64_t K, const mm355_bf16* bias, const mm355_bf16* residual,
                                int64_t ldr, int64_t res_row_mod, uint32_t flags, int variant, void* stream) {
@@ -1764,29 +1409,19 @@ extern "C" int mm355_gemm_bf16(const mm355_bf16* A, int64_t lda, const mm355_bf1
             if (variant == 2 && t128 < 224 && M > 64 && t128 * 2 >= 64) variant = 9;
         } else variant = 1;
     }
-    if (!dma_ok && (variant == 2 || variant == 4 || variant >= 6)) return MM355_EUNSUPPORTED;
+    if (!dma_ok && variant != 1) return MM355_EUNSUPPORTED;        // only the register-staged kernel takes K % 64 != 0
     switch (variant) {
         case 1: return launch_gemm<128, 128, 2, 2, false>(a, s);
         case 2: return launch_gemm<128, 128, 2, 2, true>(a, s);
         case 7: return launch_gemm<256, 256, 2, 4, true, 1>(a, s);
         case 9: return launch_gemm<64, 128, 1, 4, true>(a, s);    // 64 x 128 tiles, four waves side by side (small-M / prompt-pass shapes)
         case 11: return launch_gemm_pp(a, s);
-#ifdef MM355_LEGACY_VARIANTS                                 // tools build: kernels no product path selects, kept for A/B timing
-        case 3: return launch_gemm<256, 128, 4, 2, false>(a, s);
-        case 4: return launch_gemm<256, 128, 4, 2, true>(a, s);
-        case 5: return launch_gemm<256, 256, 2, 4, false>(a, s);
-        case 6: return launch_gemm<256, 256, 2, 4, true>(a, s);
-        case 8: return launch_gemm<128, 128, 2, 2, true, 1>(a, s);
-        case 10: return launch_gemm_ring(a, s);
-        case 12: return launch_gemm_pp2(a, s);
-        case 13: case 14: return st_eligible(a) ? mm355_gemm_st_launch(&a, variant == 14, s) : MM355_EUNSUPPORTED;
-#endif
 #ifdef MM355_ABLATIONS                                       // TIMING-ONLY builds (tools/build_ablation.sh ... -DMM355_ABLATIONS): wrong results on purpose
         case 91: return launch_gemm_pp_t<false, false, 1>(a, s);     // no DMA
         case 92: return launch_gemm_pp_t<false, false, 2>(a, s);     // no fragment reads
         case 93: return launch_gemm_pp_t<false, false, 3>(a, s);     // every DMA issued, but always K tiles 0 / 1 (L2-resident sources)
 #endif
-        default: return MM355_EUNSUPPORTED;
+        default: return MM355_EUNSUPPORTED;                // retired (3-6, 8, 10, 12-14) or unknown
     }
 }
 

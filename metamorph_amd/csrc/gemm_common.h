@@ -1,5 +1,5 @@
-// Shared between the GEMM translation units (gemm_bf16.hip, gemm_st.hip): the argument block and the fused store of eight adjacent
-// output columns (bias / GELU / residual / accumulate / fp32 or bf16 output), so that every kernel rounds exactly the same way.
+// The GEMM argument block and the fused store of eight adjacent output columns (bias / GELU / residual / accumulate / fp32 or bf16
+// output), shared by every kernel of gemm_bf16.hip so that all of them round exactly the same way.
 #pragma once
 #include "mm355_common.h"
 

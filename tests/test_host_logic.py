@@ -844,7 +844,7 @@ def test_bench_rccl_log_summary_and_bus_bandwidth(tmp_path):
     assert bench.rccl_summary(str(tmp_path / "missing.log"), Opt(), 1, 8) == {"log": str(tmp_path / "missing.log")}
 
 
-@pytest.mark.parametrize("gen,sub", [("gen_attn4", "attn4_gen"), ("gen_attn4_bwd", "attn4_bwd_gen"), ("gen_gemm_st", "gemm_st_gen")])
+@pytest.mark.parametrize("gen,sub", [("gen_attn4", "attn4_gen"), ("gen_attn4_bwd", "attn4_bwd_gen")])
 def test_committed_instruction_streams_are_what_the_generators_emit(tmp_path, monkeypatch, gen, sub):
     """The hand-placed streams (csrc/*_gen/*.inc: one asm statement per instruction) are build inputs generated by tools/gen_*.py; the
     committed files must be exactly what the committed generators emit -- no hand edits, no stale files."""
@@ -855,11 +855,8 @@ def test_committed_instruction_streams_are_what_the_generators_emit(tmp_path, mo
     spec.loader.exec_module(mod)
     out = str(tmp_path / sub)
     monkeypatch.setattr(sys, "argv", [gen + ".py"])
-    if gen == "gen_gemm_st":
-        mod.emit(out, rd1=8, b1=32, b2=40, dma_every=5, stagger=False)
-    else:
-        monkeypatch.setattr(mod, "OUT", out)
-        mod.main()
+    monkeypatch.setattr(mod, "OUT", out)
+    mod.main()
     committed = os.path.join(REPO, "metamorph_amd", "csrc", sub)
     new, old = sorted(os.listdir(out)), sorted(f for f in os.listdir(committed) if f.endswith(".inc"))
     assert new == old, (set(new) ^ set(old))
@@ -867,15 +864,15 @@ def test_committed_instruction_streams_are_what_the_generators_emit(tmp_path, mo
         assert open(os.path.join(out, f)).read() == open(os.path.join(committed, f)).read(), f
 
 
-def test_compiler_stays_out_of_the_streams_registers():
-    """tools/audit_attn4.py on the code objects of csrc/attn4.hip, attn4_bwd.hip and gemm_st.hip (compiled here with the build's flags):
+def test_compiler_stays_out_of_the_attention_streams_registers():
+    """tools/audit_attn4.py on the code objects of csrc/attn4.hip and attn4_bwd.hip (compiled here with the build's flags):
     outside the asm statements no instruction may name a VGPR at or above the kernel's amdgpu_num_vgpr limit or any AGPR, and there is no
     scratch traffic and no VGPR spill -- a compiler copy into a register the hand-placed stream owns would be silent corruption."""
     import importlib.util
     spec = importlib.util.spec_from_file_location("audit_attn4", os.path.join(REPO, "tools", "audit_attn4.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    for name in ("attn4", "attn4_bwd", "gemm_st"):
+    for name in ("attn4", "attn4_bwd"):
         bad, stats = mod.audit(mod.compile_s(name))
         assert stats and all(v["mfma"] >= 64 and v["asm_lines"] > v["mfma"] for v in stats.values()), (name, stats)
         assert not bad, (name, bad[:5])
@@ -995,43 +992,6 @@ def test_fused_decode_gemv_row_ownership_is_a_partition():
         assert rows == list(range((Hq + 2 * Hkv) * d)), (Hq, Hkv, d)
         for u in us[:(Hq + Hkv) * d // 4]:                    # partners stay inside one head, d/2 apart
             assert u[0] // d == u[3] // d and u[2] - u[0] == d // 2 and u[0] % d < d // 2
-
-
-def test_gemm_st_lds_address_algebra():
-    """csrc/gemm_st.hip's address formulas, restated: (1) a fragment ds_read_b128 is bank-conflict free -- in each of the four 16-lane
-    groups the hardware services together (MI355X_MICROARCH.md, LDS table) the 16 addresses fall into 16 different 16-B slots of the
-    256-B bank row; (2) the LDS-DMA source swizzle is the inverse of the read swizzle (lane i of a piece writes LDS chunk i & 7 of row
-    i >> 3 and must therefore FETCH logical chunk (i & 7) ^ (i >> 3)); (3) the epilogue's staging write address (SW[b] + 128 j for block
-    jn = 2 j + b) is chunk (4 jn + lane >> 4) ^ (m & 7) of row m = lane & 15, which is where the read-back looks for columns 8 g .. 8 g + 7."""
-    groups = [list(range(0, 4)) + list(range(12, 16)) + list(range(20, 28)), list(range(4, 12)) + list(range(16, 20)) + list(range(28, 32)),
-              list(range(32, 36)) + list(range(44, 48)) + list(range(52, 60)), list(range(36, 44)) + list(range(48, 52)) + list(range(60, 64))]
-    assert sorted(l for g in groups for l in g) == list(range(64))
-    for u in range(2):
-        for base_row in (0, 16, 112, 128 + 48):
-            addr = {}
-            for lane in range(64):
-                fr, fq = lane & 15, lane >> 4
-                addr[lane] = (base_row + fr) * 128 + (((4 * u + fq) ^ (fr & 7)) << 4)
-            for g in groups:
-                assert len({(addr[l] >> 4) & 15 for l in g}) == 16, (u, base_row)
-    # (2) DMA piece: LDS row r = i >> 3 (row & 7 == r: pieces start at multiples of 8 rows), LDS chunk i & 7, source chunk (i & 7) ^ r
-    for i in range(64):
-        r, lds_chunk, src_chunk = i >> 3, i & 7, (i & 7) ^ (i >> 3)
-        for q in range(8):                                    # a reader of logical chunk q of row r looks at LDS chunk q ^ (r & 7)
-            if (q ^ (r & 7)) == lds_chunk:
-                assert src_chunk == q
-    # (3) staging slab [16 m][128 n] fp32, 512-B rows, 32 chunks of 16 B
-    for lane in range(64):
-        fr, fq = lane & 15, lane >> 4
-        for jn in range(8):
-            j, b = jn >> 1, jn & 1
-            sw = fr * 512 + ((((b ^ ((fr >> 2) & 1)) << 2) + (fq ^ (fr & 3))) << 4) + 128 * j
-            assert sw == fr * 512 + (((4 * jn + fq) ^ (fr & 7)) << 4)
-    for row in range(16):
-        for g in range(16):                                   # read-back lane: columns 8 g .. 8 g + 7 = logical chunks 2 g, 2 g + 1
-            want = {row * 512 + (((2 * g + e) ^ (row & 7)) << 4) for e in range(2)}
-            have = {row * 512 + (((c) ^ (row & 7)) << 4) for c in range(32) if c // 2 == g}
-            assert want == have
 
 
 def test_host_mirrors_serve_the_splice_plan_without_a_device_copy():

@@ -17,9 +17,6 @@ pytestmark = pytest.mark.gpu
 from oracle import ref_ops as R  # noqa: E402  (the checker)
 
 DEV = "cuda"
-# kernel generations no product path selects (GEMM variants 3-6, 8, 10, 12-14, attention variant 3) exist only in a library built with
-# MM355_LEGACY_VARIANTS=1; their cases are generated only when MM355_TEST_LEGACY=1 asks for them (the default -m gpu run tests what ships)
-LEGACY = os.environ.get("MM355_TEST_LEGACY") == "1"
 
 
 @pytest.fixture(scope="module")
@@ -59,11 +56,11 @@ GEMM_SHAPES = [(128, 128, 64), (256, 256, 128), (300, 200, 192), (512, 384, 1152
                (200, 1152, 592), (1024, 1024, 4096)]
 
 
-@pytest.mark.parametrize("variant", [0, 1, 2, 7, 9, 11] + ([3, 4, 5, 6, 8, 10] if LEGACY else []))
+@pytest.mark.parametrize("variant", [0, 1, 2, 7, 9, 11])
 @pytest.mark.parametrize("shape", GEMM_SHAPES)
 def test_gemm_plain(ops, variant, shape):
     M, N, K = shape
-    if K % 64 and variant in (2, 4, 6, 7, 8, 9, 10, 11):
+    if K % 64 and variant in (2, 7, 9, 11):
         pytest.skip("LDS-DMA variants need K % 64 == 0")
     a, b = rnd(M, K, seed=1), rnd(N, K, seed=2)
     ref = a.float() @ b.float().t()
@@ -105,40 +102,6 @@ def test_gemm_pingpong_race_screen(ops, shape):
         assert torch.equal(out, ref), f"variant 11 differs from variant 1 at {shape} round {rep}: max |d| = {float((out.float() - ref.float()).abs().max())}"
     a, b = rnd(M, K, seed=1), rnd(N, K, seed=2)
     close(ops.gemm(a.to(DEV), b.to(DEV), variant=11), a.float() @ b.float().t(), 1e-2, 0.02 * math.sqrt(K), f"gemm v11 {shape}")
-
-
-if LEGACY:
-    @pytest.mark.parametrize("shape", [(256, 256, 256), (300, 520, 384), (2048, 2304, 256), (8192, 4096, 512), (8448, 2560, 384), (1024, 1028, 1152)])
-    def test_gemm_one_wave_per_simd_stream_is_bit_identical(ops, shape):
-        """Variant 13 (csrc/gemm_st.hip: persistent workgroups of four waves, 128 x 128 wave tiles with all 256 accumulators in AGPRs, a
-        hand-placed instruction stream) and variant 14 (the same stream serialised: every LDS read / LDS-DMA piece waited for on the spot)
-        against the eight-wave ping-pong kernel: the same 16x16x32 MFMA per 32 k in ascending order and the same fused store, so every
-        output -- ragged edges, the N % 8 scalar tail, several tiles per workgroup (the persistent hand-over with the next tile's first two
-        K stages in flight during the epilogue), uneven per-XCD tile ranges, each epilogue flag -- is BIT-identical; two data sets (race screen)."""
-        M, N, K = shape
-        for rep in range(2):
-            a, b = rnd(M, K, seed=30 + rep).to(DEV), rnd(N, K, seed=40 + rep).to(DEV)
-            ref = ops.gemm(a, b, variant=11)
-            for v in (13, 14):
-                out = ops.gemm(a, b, variant=v)
-                assert torch.equal(out, ref), f"variant {v} differs from variant 11 at {shape} round {rep}: max |d| = {float((out.float() - ref.float()).abs().max())}"
-        a, b = rnd(M, K, seed=1, scale=0.3).to(DEV), rnd(N, K, seed=2, scale=0.3).to(DEV)
-        bias, res, c0 = rnd(N, seed=5).to(DEV), rnd(64, N, seed=6).to(DEV), rnd(M, N, seed=8).to(DEV)
-        for kw in (dict(bias=bias, gelu="erf"), dict(bias=bias, gelu="tanh"), dict(bias=bias, residual=res, res_row_mod=64), dict(accumulate=True),
-                   dict(accumulate=True, out_f32=True)):
-            outs = []
-            for v in (11, 13, 14):
-                c = (c0.float() if kw.get("out_f32") else c0).clone()
-                ops.gemm(a, b, out=c, variant=v, **kw)
-                outs.append(c)
-            assert torch.equal(outs[1], outs[0]) and torch.equal(outs[2], outs[0]), f"epilogue {sorted(kw)} at {shape}"
-
-
-    def test_gemm_stream_variant_rejects_short_k(ops):
-        from metamorph_amd.lib import Mm355Error
-        a, b = rnd(256, 128, seed=1).to(DEV), rnd(256, 128, seed=2).to(DEV)
-        with pytest.raises(Mm355Error):
-            ops.gemm(a, b, variant=13)                              # two K stages: the stream fetches two stages ahead (K >= 256, K % 128 == 0)
 
 
 @pytest.mark.parametrize("shapes", [((512, 768, 256), (300, 520, 384)), ((256, 256, 128), (256, 256, 128)),
@@ -197,7 +160,7 @@ def test_gemm_pair_rejects_ineligible(ops):
         ops.gemm_pair(a, b, o, False, a1, b1, o1, False)
 
 
-@pytest.mark.parametrize("variant", [1, 2, 7, 11] + ([6, 10] if LEGACY else []))
+@pytest.mark.parametrize("variant", [1, 2, 7, 11])
 def test_gemm_epilogues(ops, variant):
     M, N, K = 320, 256, 128
     a, b = rnd(M, K, seed=3, scale=0.3), rnd(N, K, seed=4, scale=0.3)
@@ -287,6 +250,26 @@ def test_gemm_tn_rejects_ragged_k(ops):
     at, bt = rnd(100, 64, seed=1).to(DEV), rnd(100, 64, seed=2).to(DEV)
     with pytest.raises(Mm355Error):
         ops.gemm_tn(at, bt, torch.empty(64, 64, device=DEV, dtype=torch.bfloat16))
+
+
+def test_retired_variant_numbers_are_unsupported(ops):
+    """The numbers of the retired kernel generations (GEMM 3-6, 8, 10, 12-14; attention 3) stay reserved: each is
+    refused with MM355_EUNSUPPORTED (-2), not MM355_EINVAL, on a request the live variants accept."""
+    from metamorph_amd.lib import Mm355Error
+    a, b = rnd(256, 256, seed=1).to(DEV), rnd(256, 256, seed=2).to(DEV)
+    for v in (3, 4, 5, 6, 8, 10, 12, 13, 14):
+        with pytest.raises(Mm355Error, match=r"\(-2\)$"):
+            ops.gemm(a, b, variant=v)
+    B, L, Hq, Hkv, d = 1, 128, 4, 2, 128
+    qkv = rnd(B * L, (Hq + 2 * Hkv) * d, seed=3, scale=0.5).to(DEV)
+    q, k, v = qkv[:, :Hq * d], qkv[:, Hq * d:(Hq + Hkv) * d], qkv[:, (Hq + Hkv) * d:]
+    with pytest.raises(Mm355Error, match=r"\(-2\)$"):
+        ops.attn_fwd(q, k, v, B, L, Hq, Hkv, d, d ** -0.5, True, variant=3)
+    o, lse = ops.attn_fwd(q, k, v, B, L, Hq, Hkv, d, d ** -0.5, True)
+    dqkv = torch.empty_like(qkv)
+    with pytest.raises(Mm355Error, match=r"\(-2\)$"):
+        ops.attn_bwd(q, k, v, o, rnd(B * L, Hq * d, seed=4).to(DEV), lse, B, L, Hq, Hkv, d, d ** -0.5, True, None,
+                     dqkv[:, :Hq * d], dqkv[:, Hq * d:(Hq + Hkv) * d], dqkv[:, (Hq + Hkv) * d:], variant=3)
 
 
 @pytest.mark.parametrize("M,h,Rp", [(300, 512, 304), (1024, 4096, 1024), (777, 1152, 896)])
@@ -547,7 +530,7 @@ def test_attn_bwd(ops, case):
 
 
 @pytest.mark.parametrize("L,Hq", [(2048, 32), (4096, 32), (4096, 64)])
-def test_attn3_full_length_against_oracle_slice(ops, L, Hq):
+def test_attn_d128_full_length_against_oracle_slice(ops, L, Hq):
     """The d = 128 LDS-DMA kernels at BASELINE sequence lengths (configs[1] L = 2048, configs[2] L = 4096), LLaMA-3-8B head
     geometry (32 query / 8 KV heads) and configs[4]'s LLaMA-3-70B geometry (64 query / 8 KV heads: eight query heads per KV group,
     L = 4096), per-sample lengths: forward output, lse and all three gradients of ONE (sample, KV group) slice against the fp32
@@ -578,18 +561,18 @@ def test_attn3_full_length_against_oracle_slice(ops, L, Hq):
         dos = do[rows].view(L, Hq, d)[:, g * rep:(g + 1) * rep].permute(1, 0, 2)[None].float()
         (ref * dos).sum().backward()
         got_o = o[rows].view(L, Hq, d)[:, g * rep:(g + 1) * rep].permute(1, 0, 2)
-        close(got_o[:, :n], ref[0, :, :n], 1e-2, 4e-3, f"attn3 fwd L={L} sample {b} group {g}")
+        close(got_o[:, :n], ref[0, :, :n], 1e-2, 4e-3, f"d128 fwd L={L} sample {b} group {g}")
         assert float(got_o[:, n:].float().abs().max()) == 0 if n < L else True
         s = torch.matmul(q[0].detach(), k[0].detach().transpose(-1, -2)) * d ** -0.5
         s = s.masked_fill(~torch.ones(L, L, dtype=torch.bool).tril(), float("-inf")).masked_fill(~valid[b][None, None, :], float("-inf"))
-        close(lse[b, g * rep:(g + 1) * rep, :n], torch.logsumexp(s, -1)[:, :n], 1e-3, 5e-3, f"attn3 lse L={L}")
+        close(lse[b, g * rep:(g + 1) * rep, :n], torch.logsumexp(s, -1)[:, :n], 1e-3, 5e-3, f"d128 lse L={L}")
         tol = dict(rtol=2e-2, atol=1e-2)
         gq = dqkv[rows, :Hq * d].view(L, Hq, d)[:, g * rep:(g + 1) * rep].permute(1, 0, 2)
         gk = dqkv[rows, Hq * d:(Hq + Hkv) * d].view(L, Hkv, d)[:, g]
         gv = dqkv[rows, (Hq + Hkv) * d:].view(L, Hkv, d)[:, g]
-        close(gq, q.grad[0], what=f"attn3 dq L={L} sample {b} group {g}", **tol)
-        close(gk, k.grad[0, 0], what=f"attn3 dk L={L} sample {b} group {g}", **tol)
-        close(gv, v.grad[0, 0], what=f"attn3 dv L={L} sample {b} group {g}", **tol)
+        close(gq, q.grad[0], what=f"d128 dq L={L} sample {b} group {g}", **tol)
+        close(gk, k.grad[0, 0], what=f"d128 dk L={L} sample {b} group {g}", **tol)
+        close(gv, v.grad[0, 0], what=f"d128 dv L={L} sample {b} group {g}", **tol)
 
 
 def test_gemm_swiglu_fused_equals_two_launches(ops):

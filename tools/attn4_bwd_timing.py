@@ -10,7 +10,7 @@ CAUSAL = os.environ.get("CAUSAL", "1") == "1"
 nq, nk = Hq * d, Hkv * d
 qkv = (torch.randn(B * L, (Hq + 2 * Hkv) * d, device="cuda") * 0.5).bfloat16()
 q2, k2, v2 = qkv[:, :nq], qkv[:, nq:nq + nk], qkv[:, nq + nk:]
-o, lse = ops.attn_fwd(q2, k2, v2, B, L, Hq, Hkv, d, d ** -0.5, CAUSAL, None, variant=3)
+o, lse = ops.attn_fwd(q2, k2, v2, B, L, Hq, Hkv, d, d ** -0.5, CAUSAL, None, variant=4)
 do = torch.randn_like(o)
 dqkv = torch.zeros_like(qkv)
 for _ in range(3):

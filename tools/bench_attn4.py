@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""attn4 (one wave per SIMD, hand-placed stream) against attn3 (shipped two-waves-per-SIMD kernels) and an fp32 reference:
+"""attn4 (one wave per SIMD, hand-placed stream) against attn2 (the generic-d kernels, variant 2) and an fp32 reference:
 correctness on the d == 128 cases of tests/test_kernels_gpu.py + full-size shapes, the serialised stream (variant 41) bit for bit
 against the placed one (variant 4), then timings.   python tools/bench_attn4.py [--quick]"""
 import os
@@ -11,20 +11,7 @@ import torch
 from metamorph_amd import ops
 
 DEV = "cuda"
-
-
-def _base_variant():
-    """the comparison kernels: attn3 (round 2's d == 128 kernels) when the library was built with MM355_LEGACY_VARIANTS=1, else the generic attn2"""
-    from metamorph_amd.lib import Mm355Error
-    x = torch.zeros(64, 3 * 128, device=DEV, dtype=torch.bfloat16)
-    try:
-        ops.attn_fwd(x[:, :128], x[:, 128:256], x[:, 256:], 1, 64, 1, 1, 128, 128 ** -0.5, True, None, variant=3)
-        return 3
-    except Mm355Error:
-        return 2
-
-
-BASE = None
+BASE = 2                                                     # the comparison kernels: the generic attn2
 
 
 def ref_attention(q, k, v, seqlens, causal):
@@ -56,7 +43,7 @@ def run_case(B, L, Hq, Hkv, causal, seqlens, seed=0, full_ref=True):
     qkv = (torch.randn(B * L, (Hq + 2 * Hkv) * d, generator=g) * 0.7).bfloat16().to(DEV)
     q2, k2, v2 = qkv[:, :Hq * d], qkv[:, Hq * d:(Hq + Hkv) * d], qkv[:, (Hq + Hkv) * d:]
     sl = torch.tensor(seqlens, dtype=torch.int32, device=DEV) if seqlens else None
-    o3, l3 = ops.attn_fwd(q2, k2, v2, B, L, Hq, Hkv, d, d ** -0.5, causal, sl, variant=BASE)
+    o2, l2 = ops.attn_fwd(q2, k2, v2, B, L, Hq, Hkv, d, d ** -0.5, causal, sl, variant=BASE)
     res = {}
     for var in (41, 4):
         o = torch.full((B * L, Hq * d), float("nan"), device=DEV, dtype=torch.bfloat16)
@@ -70,22 +57,22 @@ def run_case(B, L, Hq, Hkv, causal, seqlens, seed=0, full_ref=True):
         ro = ro.reshape(B * L, Hq * d)
     for var, (o4, l4) in res.items():
         fin = bool(torch.isfinite(o4.float()).all()) and bool(torch.isfinite(l4).all())
-        e3 = float((o4.float() - o3.float()).abs().max())
-        el3 = float((l4 - l3).abs().max())
-        msg = f"[{tag}] variant {var}: finite={fin} |o - o_attn3|max={e3:.3e} |lse - lse_attn3|max={el3:.3e}"
+        e2 = float((o4.float() - o2.float()).abs().max())
+        el2 = float((l4 - l2).abs().max())
+        msg = f"[{tag}] variant {var}: finite={fin} |o - o_attn2|max={e2:.3e} |lse - lse_attn2|max={el2:.3e}"
         if full_ref:
             er = float((o4.float() - ro).abs().max())
-            e3r = float((o3.float() - ro).abs().max())
+            e2r = float((o2.float() - ro).abs().max())
             elr = float((l4 - rl).abs().max())
-            msg += f"  vs fp32: attn4 {er:.3e} (attn3 {e3r:.3e}) lse {elr:.3e}"
-            good = fin and er <= max(2.0 * e3r, 1.5e-2) and elr <= 1e-2
+            msg += f"  vs fp32: attn4 {er:.3e} (attn2 {e2r:.3e}) lse {elr:.3e}"
+            good = fin and er <= max(2.0 * e2r, 1.5e-2) and elr <= 1e-2
         else:
-            good = fin and e3 <= 3e-2 and el3 <= 1e-2
+            good = fin and e2 <= 3e-2 and el2 <= 1e-2
         print(msg + ("  OK" if good else "  **MISMATCH**"), flush=True)
         if not good:
             ok = False
             # localise: worst 64-row wave segment / head / column block
-            diff = (o4.float() - (ro if full_ref else o3.float())).abs().view(B, L, Hq, d)
+            diff = (o4.float() - (ro if full_ref else o2.float())).abs().view(B, L, Hq, d)
             diff = torch.nan_to_num(diff, nan=1e9)
             per_row = diff.amax(dim=(2, 3))                  # [B, L]
             seg = per_row.view(B, -1, min(64, L)) if L % 64 == 0 else None
@@ -96,7 +83,7 @@ def run_case(B, L, Hq, Hkv, causal, seqlens, seed=0, full_ref=True):
             per_head = diff.amax(dim=(0, 1, 3))
             print("   per-head max error:", [f"{x:.1e}" for x in per_head.tolist()])
             rr = int(per_row[0].argmax())
-            print(f"   worst row of sample 0: {rr}; row values attn4 {o4.view(B, L, Hq, d)[0, rr, 0, :8].tolist()} ref {(ro if full_ref else o3.float()).view(B, L, Hq, d)[0, rr, 0, :8].tolist()}")
+            print(f"   worst row of sample 0: {rr}; row values attn4 {o4.view(B, L, Hq, d)[0, rr, 0, :8].tolist()} ref {(ro if full_ref else o2.float()).view(B, L, Hq, d)[0, rr, 0, :8].tolist()}")
     same = torch.equal(res[4][0], res[41][0]) and torch.equal(res[4][1], res[41][1])
     print(f"[{tag}] placed stream == serialised stream bit for bit: {same}", flush=True)
     return ok and same
@@ -127,8 +114,6 @@ def bench(B, L, Hq, Hkv, causal=True, variants=(0, 4, 41)):
 
 
 if __name__ == "__main__":
-    BASE = _base_variant()
-    print(f"comparison kernels: variant {BASE}", flush=True)
     quick = "--quick" in sys.argv
     cases = [  # B, L, Hq, Hkv, causal, seqlens
         (1, 64, 2, 1, True, None),

@@ -4,7 +4,7 @@ import os, sys, statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from metamorph_amd import ops
-variants = [int(x) for x in os.environ.get("VARIANTS", "6,7").split(",")]
+variants = [int(x) for x in os.environ.get("VARIANTS", "7,11").split(",")]
 shapes = [("qkv", 16384, 6144, 4096), ("gate_up", 16384, 28672, 4096), ("down", 16384, 4096, 14336), ("dW_gate_up", 28672, 4096, 16384), ("o", 16384, 4096, 4096)]
 for name, m, n, k in shapes:
     a = torch.randn(m, k, device="cuda").bfloat16(); b = torch.randn(n, k, device="cuda").bfloat16()
