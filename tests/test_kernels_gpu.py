@@ -60,9 +60,13 @@ GEMM_SHAPES = [(128, 128, 64), (256, 256, 128), (300, 200, 192), (512, 384, 1152
 @pytest.mark.parametrize("shape", GEMM_SHAPES)
 def test_gemm_plain(ops, variant, shape):
     M, N, K = shape
-    if K % 64 and variant in (2, 7, 9, 11):
-        pytest.skip("LDS-DMA variants need K % 64 == 0")
     a, b = rnd(M, K, seed=1), rnd(N, K, seed=2)
+    if K % 64 and variant in (2, 7, 9, 11):
+        # the LDS-DMA variants stage whole 64-wide K tiles: a ragged K is refused with MM355_EUNSUPPORTED (-2), never approximated
+        from metamorph_amd.lib import Mm355Error
+        with pytest.raises(Mm355Error, match=r"\(-2\)$"):
+            ops.gemm(a.to(DEV), b.to(DEV), variant=variant)
+        return
     ref = a.float() @ b.float().t()
     out = ops.gemm(a.to(DEV), b.to(DEV), variant=variant)
     close(out, ref, 1e-2, 0.02 * math.sqrt(K), f"gemm v{variant} {shape}")
@@ -338,7 +342,10 @@ def test_transpose_and_colsum(ops):
 
 # ------------------------------------------------------------------------------------------------ norms
 
-@pytest.mark.parametrize("h", [256, 1152, 4096])
+RMS_WIDTHS = [2048, 2056, 4104, 8192, 16384]   # row-kernel VPT classes (dispatch_vpt: 8 / 16 / 32 / 64 columns per thread): edges and the maximum
+
+
+@pytest.mark.parametrize("h", [256, 1152, 4096] + RMS_WIDTHS)
 def test_rmsnorm_fwd_bwd(ops, h):
     M = 37
     x, w, dy, dres = rnd(M, h, seed=1), (1 + 0.1 * rnd(h, seed=2).float()).bfloat16(), rnd(M, h, seed=3), rnd(M, h, seed=4)
@@ -368,13 +375,143 @@ def test_rmsnorm_bwd_large_deterministic(ops):
     close(outs[0], (dy.float() * xh).sum(0), 1e-3, 1e-3 * math.sqrt(M), "rmsnorm dw two-stage")
 
 
+@pytest.mark.parametrize("h", RMS_WIDTHS)
+def test_rmsnorm_fwd_against_fp64_across_row_classes(ops, h):
+    """rmsnorm_fwd at the VPT class edges, LLaMA-70B's width and the widest row, against fp64: rstd to 1e-6, y = bf16(w * bf16(x * rstd))
+    within two bf16 steps everywhere and bit-equal on >= 99 % of the elements; the want_rstd form writes the bits of the plain call."""
+    M, eps = 64, 1e-5
+    x, w = rnd(M, h, seed=h, scale=1.5), (1 + 0.1 * rnd(h, seed=h + 1).float()).bfloat16()
+    y, rstd = ops.rmsnorm_fwd(x.to(DEV), w.to(DEV), eps, want_rstd=True)
+    assert torch.equal(y, ops.rmsnorm_fwd(x.to(DEV), w.to(DEV), eps))
+    x64 = x.double()
+    rstd64 = torch.rsqrt((x64 * x64).mean(-1) + eps)
+    # fp32 sum of squares along a chain of <= 8 VPT + 8 adds (one per thread, then the wave / workgroup tree): random-walk error
+    # ~ sqrt(72) 2^-24 = 5e-7 relative at h = 16384, halved by the rsqrt, plus <= 1 ulp of v_rsq_f32; a dropped vector is 1/2048
+    rel = float(((rstd.double().cpu() - rstd64) / rstd64).abs().max())
+    assert rel <= 1e-6, (h, rel)
+    xn = (x64 * rstd64[:, None]).float().bfloat16()                             # the inner rounding, from the fp64 rstd
+    want = (w.float() * xn.float()).bfloat16().float()                          # bf16 x bf16 is exact in fp32: one rounding
+    got = y.float().cpu()
+    # where x * rstd sits within fp32 noise of a bf16 rounding boundary the inner rounding may go the other way: <= 1 bf16 step of xn, i.e.
+    # <= 2 steps (2^-7 relative) of y after the outer rounding
+    bad = (got - want).abs() > 2.0 ** -7 * want.abs()
+    assert not bool(bad.any()), (h, int(bad.sum()), float((got - want).abs().max()))
+    same = float((got == want).float().mean())
+    assert same >= 0.99, (h, same)
+
+
+def test_rmsnorm_rows_wider_than_16384_are_refused(ops):
+    """dispatch_vpt holds at most 64 columns per thread in registers (h <= 16384): a wider row is MM355_EUNSUPPORTED (-2) in every
+    row kernel, never a partial row."""
+    from metamorph_amd.lib import Mm355Error
+    h = 16392
+    x, w, dy = rnd(2, h, seed=1).to(DEV), rnd(h, seed=2).to(DEV), rnd(2, h, seed=3).to(DEV)
+    for call in (lambda: ops.rmsnorm_fwd(x, w, 1e-5), lambda: ops.rmsnorm_fwd(x, w, 1e-5, want_rstd=True),
+                 lambda: ops.rmsnorm_bwd(dy, x, w, 1e-5, dw_f32=torch.zeros(h, device=DEV)),
+                 lambda: ops.rmsnorm_bwd_wgrad(dy, x, w, 1e-5, torch.zeros(h, device=DEV, dtype=torch.bfloat16), True),
+                 lambda: ops.layernorm_fwd(x, w, w, 1e-6)):
+        with pytest.raises(Mm355Error, match=r"\(-2\)$"):
+            call()
+
+
+def _rms_rows_per_wg(L, M, h, two_stage):
+    """rmsnorm_bwd_rows_per_block (csrc/rowwise.hip): rows per workgroup and workgroup count; the two-stage count is cross-checked against
+    the workspace size the library asks for."""
+    rpb = (32 if M >= 8192 else 8 if M >= 1024 else 1) if two_stage else (16 if M >= 8192 else 4 if M >= 1024 else 1)
+    G = (M + rpb - 1) // rpb
+    if two_stage:
+        assert int(L.mm355_rmsnorm_bwd_ws_floats(M, h)) == G * h
+    return rpb, G
+
+
+def _rms_dw_ref(x, dy, eps):
+    """fp64 weight gradient sum_r dy * bf16(x * rstd) (HF: the gradient of w * bf16(xhat)), sum_r |dy * bf16(xhat)|, and per column the sum
+    of |dy| * one bf16 step over the elements whose x * rstd lies within 2^-19 (relative) of a bf16 rounding boundary: there the kernel's
+    fp32 x * rstd (rstd <= 1e-6 off, see above) may round to the neighbouring value."""
+    x64, dy64 = x.double(), dy.double()
+    xh = x64 * torch.rsqrt((x64 * x64).mean(-1, keepdim=True) + eps)
+    xb = xh.float().bfloat16().double()
+    lo, hi = (xh * (1 - 2.0 ** -19)).float().bfloat16().double(), (xh * (1 + 2.0 ** -19)).float().bfloat16().double()
+    t = dy64 * xb
+    return t.sum(0), t.abs().sum(0), (dy64.abs() * (hi - lo).abs()).sum(0)
+
+
+@pytest.mark.parametrize("M", [1023, 1024, 1025, 8191, 8193])
+def test_rmsnorm_bwd_rows_per_block_classes(ops, M):
+    """mm355_rmsnorm_bwd in each rows-per-workgroup class (1 / 8 / 32 rows two-stage, 1 / 4 / 16 with fp32 atomics; edges at M = 1024 and
+    8192), every class with a ragged last workgroup: dx against fp64 autograd, dw (accumulated onto a prefill) against the fp64 sum."""
+    from metamorph_amd import lib as mmlib
+    h, eps = 1152, 1e-5
+    x, dy, dres = rnd(M, h, seed=M, scale=1.5), rnd(M, h, seed=M + 1), rnd(M, h, seed=M + 2)
+    w = (1 + 0.1 * rnd(h, seed=M + 3).float()).bfloat16()
+    xf = x.double().requires_grad_(True)
+    R.rmsnorm(xf, w.double(), eps).backward(dy.double())
+    dx_ref = xf.grad + dres.double()
+    x64, g64 = x.double(), dy.double() * w.double()
+    rstd = torch.rsqrt((x64 * x64).mean(-1, keepdim=True) + eps)
+    # bf16 output: <= 2^-9 relative; fp32 inside: rstd (<= 1e-6) and the row dot product (a chain of <= 8 VPT + 9 adds: 1e-6 of its absolute
+    # sum D) move dx by < 4e-6 T, T = rstd (|dy w| + |xhat| D); 2^-16 T is 4x that, and 1/1000 of what one wrong row term does
+    D = (g64 * x64 * rstd).abs().mean(-1, keepdim=True)
+    tol_dx = 2.0 ** -8 * dx_ref.abs() + 2.0 ** -16 * rstd * (g64.abs() + (x64 * rstd).abs() * D)
+    dw_ref, dw_abs, dw_flip = _rms_dw_ref(x, dy, eps)
+    L = mmlib.load()
+    for two_stage in (True, False):
+        rpb, G = _rms_rows_per_wg(L, M, h, two_stage)
+        dw = torch.full((h,), 0.5, device=DEV)
+        dx = ops.rmsnorm_bwd(dy.to(DEV), x.to(DEV), w.to(DEV), eps, dres=dres.to(DEV), dw_f32=dw, atomic=not two_stage)
+        err = (dx.double().cpu() - dx_ref).abs()
+        assert bool((err <= tol_dx).all()), (M, two_stage, int((err > tol_dx).sum()), float(err.max()))
+        # fp32 sum of M exact products (bf16 x bf16), rpb in registers, then <= G partials (fixed tree or atomics) and the prefill: at
+        # most n = rpb + G + 34 rounded adds, each <= 2^-24 of the running absolute sum
+        bound = (rpb + G + 34) * 2.0 ** -24 * (dw_abs + 0.5) + dw_flip
+        err = (dw.double().cpu() - (dw_ref + 0.5)).abs()
+        assert bool((err <= bound).all()), (M, two_stage, int((err > bound).sum()), float(err.max()))
+
+
+@pytest.mark.parametrize("M,h", [(37, 16384), (1025, 1152), (8193, 2056)])
+def test_rmsnorm_bwd_wgrad(ops, M, h):
+    """mm355_rmsnorm_bwd_wgrad (both RMSNorm weight gradients of every training step) writes the two-stage fixed-order sum straight into a
+    bf16 gradient buffer: dx is rmsnorm_bwd's, the gradient is bf16 of the fp32 value the two-stage mm355_rmsnorm_bwd computes from
+    float(prev) (accumulate) or from 0 (a NaN prefill must not leak), two calls give the same bits, and that fp32 value is held to fp64."""
+    eps = 1e-5
+    xh_, dyh, dresh = rnd(M, h, seed=M, scale=1.5), rnd(M, h, seed=M + 1), rnd(M, h, seed=M + 2)
+    wh = (1 + 0.1 * rnd(h, seed=M + 3).float()).bfloat16()
+    prevh = rnd(h, seed=M + 4, scale=4.0)
+    x, dy, dres, w, prev = xh_.to(DEV), dyh.to(DEV), dresh.to(DEV), wh.to(DEV), prevh.to(DEV)
+    dx_ref = ops.rmsnorm_bwd(dy, x, w, eps, dres=dres)
+    g1 = prev.clone()
+    dx1 = ops.rmsnorm_bwd_wgrad(dy, x, w, eps, g1, True, dres=dres)
+    assert torch.equal(dx1, dx_ref)
+    f1 = prev.float()
+    ops.rmsnorm_bwd(dy, x, w, eps, dres=dres, dw_f32=f1)
+    assert torch.equal(g1, f1.bfloat16()), (M, h, int((g1 != f1.bfloat16()).sum()))
+    g0 = torch.full((h,), float("nan"), device=DEV, dtype=torch.bfloat16)
+    ops.rmsnorm_bwd_wgrad(dy, x, w, eps, g0, False, dres=dres)
+    assert bool(torch.isfinite(g0.float()).all())
+    f0 = torch.zeros(h, device=DEV)
+    ops.rmsnorm_bwd(dy, x, w, eps, dres=dres, dw_f32=f0)
+    assert torch.equal(g0, f0.bfloat16()), (M, h, int((g0 != f0.bfloat16()).sum()))
+    g0b = torch.full((h,), float("nan"), device=DEV, dtype=torch.bfloat16)
+    ops.rmsnorm_bwd_wgrad(dy, x, w, eps, g0b, False, dres=dres)
+    assert torch.equal(g0, g0b)
+    # the fp32 sums against fp64 (as in test_rmsnorm_bwd_rows_per_block_classes: <= rpb + G + 34 rounded adds, plus the boundary budget)
+    from metamorph_amd import lib as mmlib
+    rpb, G = _rms_rows_per_wg(mmlib.load(), M, h, True)
+    dw_ref, dw_abs, dw_flip = _rms_dw_ref(xh_, dyh, eps)
+    for got, start in ((f0, torch.zeros(h, dtype=torch.float64)), (f1, prevh.double())):
+        bound = (rpb + G + 34) * 2.0 ** -24 * (dw_abs + start.abs()) + dw_flip
+        err = (got.double().cpu() - (dw_ref + start)).abs()
+        assert bool((err <= bound).all()), (M, h, int((err > bound).sum()), float(err.max()))
+
+
 def test_layernorm_fwd(ops):
-    x, w, b = rnd(50, 1152, seed=1), (1 + 0.1 * rnd(1152, seed=2).float()).bfloat16(), rnd(1152, seed=3, scale=0.1)
-    y = ops.layernorm_fwd(x.to(DEV), w.to(DEV), b.to(DEV), 1e-6)
-    close(y, R.layernorm(x.float(), w.float(), b.float(), 1e-6), 8e-3, 1e-2, "layernorm")
+    for h in (1152, 8192):                                      # (8192: four vectors per thread)
+        x, w, b = rnd(50, h, seed=1), (1 + 0.1 * rnd(h, seed=2).float()).bfloat16(), rnd(h, seed=3, scale=0.1)
+        y = ops.layernorm_fwd(x.to(DEV), w.to(DEV), b.to(DEV), 1e-6)
+        close(y, R.layernorm(x.float(), w.float(), b.float(), 1e-6), 8e-3, 1e-2, f"layernorm h={h}")
 
 
-@pytest.mark.parametrize("Mh", [(50, 1152), (9000, 1152), (37, 256)])
+@pytest.mark.parametrize("Mh", [(50, 1152), (9000, 1152), (37, 256), (50, 8192)])
 def test_layernorm_bwd(ops, Mh):
     M, h = Mh
     x, dy, dres = rnd(M, h, seed=1), rnd(M, h, seed=2), rnd(M, h, seed=3)
@@ -446,6 +583,125 @@ def test_rope_table_freq_matches_hf_recorded_tables(ops):
     cf, sf = ops.rope_table_freq(4096, 128, g["default::inv_freq"], 1.0, DEV)
     assert float((cd != cf).float().mean()) < 5e-3 and float((cd.float() - cf.float()).abs().max()) <= 8e-3
     assert float((sd_ != sf).float().mean()) < 5e-3
+
+
+def _hf_rope_rows(x, cos, sin, d):
+    """HF's x * cos + rotate_half(x) * sin on bf16 tensors (R.rope_apply: each product rounded to bf16, then the sum): x [M, H*d],
+    cos / sin [M, d] (the table row of each x row)."""
+    M = x.shape[0]
+    return R.rope_apply(x.view(M, -1, 1, d), cos.view(M, 1, d), sin.view(M, 1, d)).reshape(M, -1)
+
+
+def _inverse_rope_rows(x, cos, sin, d):
+    """Inverse rotation y1 = x1 c + x2 s, y2 = x2 c - x1 s of bf16 rows: the products of bf16 values are exact in fp64 and so is their sum;
+    then fp32, then bf16 -- the kernel's fp32 result (one rounding of the exact value) rounded once more."""
+    M, h = x.shape[0], d // 2
+    x = x.double().view(M, -1, d)
+    c, s = cos.double()[:, None, :h], sin.double()[:, None, :h]
+    x1, x2 = x[..., :h], x[..., h:]
+    return torch.cat([x1 * c + x2 * s, x2 * c - x1 * s], -1).float().bfloat16().reshape(M, -1)
+
+
+def _assert_halves_equal(cos, sin, d):
+    """The kernels read only the first half of a table row; the bit-exact references use the whole row, so the halves must agree."""
+    assert torch.equal(cos[:, :d // 2], cos[:, d // 2:]) and torch.equal(sin[:, :d // 2], sin[:, d // 2:])
+
+
+@pytest.mark.parametrize("d,Hq,Hkv", [(64, 4, 0), (80, 3, 3), (128, 8, 2)])
+def test_rope_qk_bit_exact_with_position_offsets(ops, d, Hq, Hkv):
+    """mm355_rope_qk_pos (left-padded training batches) and mm355_rope_qk against host references, bit for bit: the forward in HF's rounding
+    order, the inverse (backward) from the exact fp64 value; per-sample offsets 0 .. L reach the last row of a 2L table; q only (Hkv = 0),
+    MHA and GQA; qkv is a column block of a wider buffer, and the v block and the columns outside the view keep their bits."""
+    B, L = 3, 37
+    n_rot, n = (Hq + Hkv) * d, (Hq + 2 * Hkv) * d
+    c0, width = 24, n + 56                                                    # the view: columns [24, 24 + n) of rows `width` apart
+    big = rnd(B * L, width, seed=d + Hkv)
+    cos, sin = ops.rope_table(2 * L, d, 500000.0, DEV)
+    _assert_halves_equal(cos, sin, d)
+    ct, st = cos.cpu(), sin.cpu()
+    offsets = [0, L, 11]
+    pos = (torch.arange(L)[None] + torch.tensor(offsets)[:, None]).reshape(-1)          # table row of every qkv row
+    assert int(pos.max()) == 2 * L - 1
+    for inverse in (False, True):
+        for po in (torch.tensor(offsets, dtype=torch.int32, device=DEV), None):
+            p = pos if po is not None else torch.arange(L).repeat(B)
+            dev = big.to(DEV)
+            ops.rope_qk_(dev[:, c0:c0 + n], B, L, Hq, Hkv, d, cos, sin, inverse=inverse, pos_offset=po)
+            got = dev.cpu()
+            blk = big[:, c0:c0 + n_rot]
+            want = (_inverse_rope_rows if inverse else _hf_rope_rows)(blk, ct[p], st[p], d)
+            what = f"rope_qk d={d} Hq={Hq} Hkv={Hkv} inverse={inverse} offsets={po is not None}"
+            assert torch.equal(got[:, c0:c0 + n_rot], want), (what, int((got[:, c0:c0 + n_rot] != want).sum()))
+            assert torch.equal(got[:, :c0], big[:, :c0]) and torch.equal(got[:, c0 + n_rot:], big[:, c0 + n_rot:]), (what, "outside q|k")
+
+
+@pytest.mark.parametrize("table", ["theta", "llama31_8b", "llama32_1b"])
+def test_rope_kv_append_bit_exact(ops, table):
+    """mm355_rope_kv_append (every decode step; the prompt pass with batch stride 0) against the HF rotation on the host, bit for bit: q in
+    place, rotated k and v in cache row positions[b]; the k / v columns of qkv are not written and every other cache row keeps its bits.
+    Decode form: positions 0, interior and the last cache row, ld_kv > Hkv d, batch stride > Lmax ld_kv.  Prompt form (functional.py's
+    as_strided cache view): L rows of one sequence at rows row0 .. row0 + L - 1, row0 > 0.  Tables from the theta entry point and from
+    LLaMA-3.1 / 3.2 inverse frequencies (tests/golden/r6_rope_tables.npz)."""
+    from conftest import GOLDEN
+    Hq, Hkv, Lmax = 8, 2, 50
+    if table == "theta":
+        d = 128
+        cos, sin = ops.rope_table(Lmax, d, 500000.0, DEV)
+    else:
+        g = np.load(os.path.join(GOLDEN, "r6_rope_tables.npz"))
+        inv = g[f"{table}::inv_freq"]
+        d = 2 * inv.shape[0]
+        cos, sin = ops.rope_table_freq(Lmax, d, inv, float(g[f"{table}::attention_scaling"]), DEV)
+    _assert_halves_equal(cos, sin, d)
+    ct, st = cos.cpu(), sin.cpu()
+    nq, nk, n = Hq * d, Hkv * d, (Hq + 2 * Hkv) * d
+    ld_kv = nk + 24
+
+    def run(B, positions, bs, nbuf, qkv):
+        """one call on caches laid out as [B, Lmax, Hkv d] views (strides bs, ld_kv, 1) of flat buffers of nbuf elements"""
+        kbuf, vbuf = rnd(nbuf, seed=B + 5), rnd(nbuf, seed=B + 6)
+        kd, vd = kbuf.to(DEV), vbuf.to(DEV)
+        kc, vc = (t.as_strided((B, Lmax, nk), (bs, ld_kv, 1)) for t in (kd, vd))
+        dev = qkv.to(DEV)
+        ops.rope_kv_append_(dev, Hq, Hkv, d, cos, sin, torch.tensor(positions, dtype=torch.int32, device=DEV), kc, vc)
+        got, kgot, vgot = dev.cpu(), kd.cpu(), vd.cpu()
+        p = torch.tensor(positions).long()
+        rot = _hf_rope_rows(qkv[:, :nq + nk], ct[p], st[p], d)
+        assert torch.equal(got[:, :nq], rot[:, :nq]), ("q", table, B, int((got[:, :nq] != rot[:, :nq]).sum()))
+        assert torch.equal(got[:, nq:], qkv[:, nq:]), ("k / v columns of qkv written", table, B)
+        kwant, vwant, written = kbuf.clone(), vbuf.clone(), torch.zeros(nbuf, dtype=torch.bool)
+        for b, pb in enumerate(positions):
+            o = b * bs + pb * ld_kv
+            kwant[o:o + nk], vwant[o:o + nk] = rot[b, nq:], qkv[b, nq + nk:]
+            written[o:o + nk] = True
+        assert torch.equal(kgot[written], kwant[written]) and torch.equal(vgot[written], vwant[written]), ("cache rows", table, B, positions)
+        assert torch.equal(kgot[~written], kbuf[~written]) and torch.equal(vgot[~written], vbuf[~written]), ("other cache rows", table, B)
+
+    # decode: one row per sequence
+    B = 4
+    bs = Lmax * ld_kv + 40
+    run(B, [0, 23, Lmax - 1, 7], bs, B * bs, rnd(B, n, seed=d))
+    # prompt pass: one sequence, batch stride 0, L rows at row0 .. row0 + L - 1 (the last one the last cache row)
+    L = 9
+    run(L, list(range(Lmax - L, Lmax)), 0, Lmax * ld_kv, rnd(L, n, seed=d + 1))
+
+
+def test_rope_rejects_unsupported_head_dims_and_strides(ops):
+    """rope_qk / rope_kv_append rotate 8-element vectors of each half head: d % 16 != 0 or a row stride that is not a multiple of 8 is
+    refused (Mm355Error), not rounded down."""
+    from metamorph_amd.lib import Mm355Error
+    Hq, Hkv = 2, 1
+    for d, extra in ((72, 0), (64, 4)):
+        n = (Hq + 2 * Hkv) * d
+        qkv = rnd(4, n + extra, seed=d).to(DEV)[:, :n]
+        assert qkv.stride(0) == n + extra
+        cos, sin = ops.rope_table(16, d, 10000.0, DEV)
+        kc, vc = torch.zeros(4, 16, Hkv * d, device=DEV, dtype=torch.bfloat16), torch.zeros(4, 16, Hkv * d, device=DEV, dtype=torch.bfloat16)
+        for call in (lambda: ops.rope_qk_(qkv, 2, 2, Hq, Hkv, d, cos, sin),
+                     lambda: ops.rope_qk_(qkv, 2, 2, Hq, Hkv, d, cos, sin, inverse=True, pos_offset=torch.zeros(2, dtype=torch.int32, device=DEV)),
+                     lambda: ops.rope_kv_append_(qkv, Hq, Hkv, d, cos, sin, torch.zeros(4, dtype=torch.int32, device=DEV), kc, vc)):
+            with pytest.raises(Mm355Error):
+                call()
 
 
 # ------------------------------------------------------------------------------------------------ attention
@@ -824,6 +1080,34 @@ def test_loss_scalars_are_bit_reproducible(ops):
     close(ls_a, first[0], 1e-5, 0, "atomics vs fixed order")
 
 
+@pytest.mark.parametrize("n", [1, 1023, 1024, 1025, 100003])
+def test_sum_rows_f32_through_ctypes(n):
+    """mm355_sum_rows_f32 (the fixed-order reduction behind ce_rows and the losses' row_ws; no Python wrapper) through ctypes on device
+    buffers: out = scale * sum (accumulate 0: a NaN in out must not leak) and out += scale * sum (accumulate 1) against fp64, and the
+    same bits from two calls."""
+    import ctypes
+    from metamorph_amd import lib as mmlib
+    L = mmlib.load()
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    v = torch.randn(n, generator=torch.Generator().manual_seed(n)) * 3.0 + 0.5
+    vd = v.to(DEV)
+    scale, prev = 0.37, -2.75
+    s64, a64 = float(v.double().sum()), float(v.double().abs().sum())
+    # thread t sums v[t], v[t + 1024], ... (ceil(n / 1024) adds), then 10 tree levels (wave of 64, 16 waves), the scale and the prefill:
+    # <= ceil(n / 1024) + 12 rounded operations, each <= 2^-24 of the running absolute sum
+    bound = (-(-n // 1024) + 12) * 2.0 ** -24 * (scale * a64 + abs(prev))
+    for accumulate, start in ((0, float("nan")), (1, prev)):
+        outs = []
+        for _ in range(2):
+            out = torch.full((1,), start, device=DEV)
+            assert L.mm355_sum_rows_f32(vd.data_ptr(), n, scale, out.data_ptr(), accumulate, stream) == 0
+            torch.cuda.synchronize()
+            outs.append(out.cpu())
+        assert torch.equal(outs[0], outs[1]), (n, accumulate)
+        want = scale * s64 + (prev if accumulate else 0.0)
+        assert abs(float(outs[0]) - want) <= bound, (n, accumulate, float(outs[0]), want, bound)
+
+
 def test_gemm_small_m_tiles_are_bit_identical_and_selected_for_prompt_shapes(ops):
     """Round 6: 64 x 128 tiles (variant 9) for prompt-pass shapes -- a few hundred rows against N = 4096 .. 6144, where 128 x 128 tiles leave
     half of the CUs without a workgroup.  Same K order per output element as every other tiling: bit-identical to variants 2 and 11, with
@@ -989,10 +1273,11 @@ def test_swiglu_bwd_transposed_outputs(ops):
 
 # ------------------------------------------------------------------------------------------------ decode shape (row N1)
 
-@pytest.mark.parametrize("M", [1, 2, 3, 8, 16])
+@pytest.mark.parametrize("M", [1, 2, 3, 4, 5, 7, 8, 13, 16])
 @pytest.mark.parametrize("NK", [(64, 512), (130, 1032), (6144, 4096), (1000, 14336), (4096, 64), (40, 16896)])
 def test_gemv(ops, M, NK):
-    """(K = 14336 / 16896: the x rows pass through LDS in windows of 4096 columns)"""
+    """(K = 14336 / 16896: the x rows pass through LDS in windows of 4096 columns.  M = 4: the largest vector-ALU form, the four-sequence
+    decode step; 5, 7, 13: odd fills of the 16 x-row MFMA operand)"""
     N, K = NK
     x, w, b, r = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=0.05), rnd(N, seed=3), rnd(M, N, seed=4)
     ref = x.float() @ w.float().t()
@@ -1200,7 +1485,7 @@ def test_ce_rows_with_logits_of_80(ops):
     assert float(dev[:, V:].float().abs().max()) == 0 and float(dev[7].float().abs().max()) == 0
 
 
-@pytest.mark.parametrize("M", [1, 2, 3, 5, 8, 16])
+@pytest.mark.parametrize("M", [1, 2, 3, 4, 5, 8, 16])
 @pytest.mark.parametrize("IK", [(64, 512), (14336, 4096), (1000, 1032), (64, 8192), (48, 5120)])
 def test_gemv_swiglu_fused_equals_the_launch_sequence(ops, M, IK):
     """mm355_gemv_swiglu_bf16 (RMSNorm in the operand read, SiLU(g) * u in the epilogue) == rmsnorm_fwd -> gemv -> swiglu_fwd, bit for bit;
@@ -1221,7 +1506,7 @@ def test_gemv_swiglu_fused_equals_the_launch_sequence(ops, M, IK):
 
 
 @pytest.mark.parametrize("geo", [(1, 8, 2, 128, 512), (3, 4, 4, 64, 1032), (2, 32, 8, 128, 4096), (8, 2, 1, 80, 256), (8, 32, 8, 128, 4096), (16, 8, 2, 128, 1024),
-                                 (5, 8, 2, 128, 8192), (2, 4, 4, 64, 5120), (1, 8, 2, 128, 12288)])
+                                 (5, 8, 2, 128, 8192), (2, 4, 4, 64, 5120), (1, 8, 2, 128, 12288), (4, 32, 8, 128, 4096), (4, 8, 2, 128, 8192)])
 def test_gemv_rope_append_fused_equals_the_launch_sequence(ops, geo):
     """mm355_gemv_rope_append_bf16 == rmsnorm_fwd -> gemv -> rope_kv_append: the q columns of the row buffer and the cache rows written
     (and ONLY those cache rows) carry the same bits; positions differ per sample and come from device memory."""
@@ -1238,6 +1523,77 @@ def test_gemv_rope_append_fused_equals_the_launch_sequence(ops, geo):
         got = ops.gemv_rope_append(x, w, Hq, Hkv, d, cos, sin, pos, k1, v1, norm_w=nw if norm else None, eps=1e-5)
         assert torch.equal(got[:, :Hq * d], qkv[:, :Hq * d]), "q rows"
         assert torch.equal(k1, k0) and torch.equal(v1, v0), "cache rows"
+
+
+@pytest.mark.parametrize("M", [1, 4, 5, 16])
+@pytest.mark.parametrize("d", [68, 72, 100])
+def test_gemv_rope_append_head_dims_not_multiple_of_16(ops, d, M):
+    """mm355_gemv_rope_append_bf16 takes any d % 4 == 0 (rotation partners in pairs), which rope_kv_append refuses: so the reference is
+    the HF rotation on the host of the projection's bits (gemv of the -- optionally normalised -- rows; test_gemv_rope_append_fused_equals_
+    the_launch_sequence shows those are the pre-rotation values): q columns and the cache rows written bit for bit, no other cache row
+    touched; vector-ALU (M <= 4) and MFMA (5 .. 16) forms, K with a tail step."""
+    Hq, Hkv, K, Lmax = 4, 2, 1032, 40
+    nq, nk, N = Hq * d, Hkv * d, (Hq + 2 * Hkv) * d
+    x, w, nw = rnd(M, K, seed=d).to(DEV), rnd(N, K, seed=d + 1, scale=0.05).to(DEV), (1.0 + 0.1 * rnd(K, seed=d + 2)).bfloat16().to(DEV)
+    cos, sin = ops.rope_table(Lmax, d, 10000.0, DEV)
+    _assert_halves_equal(cos, sin, d)
+    positions = [(7 * m + 3) % Lmax for m in range(M)]
+    positions[-1] = Lmax - 1
+    pos = torch.tensor(positions, dtype=torch.int32, device=DEV)
+    base_k, base_v = rnd(M, Lmax, nk, seed=d + 3), rnd(M, Lmax, nk, seed=d + 4)
+    p = torch.tensor(positions).long()
+    for norm in (True, False):
+        pre = ops.gemv(ops.rmsnorm_fwd(x, nw, 1e-5) if norm else x, w).cpu()
+        rot = _hf_rope_rows(pre[:, :nq + nk], cos.cpu()[p], sin.cpu()[p], d)
+        kc, vc = base_k.to(DEV), base_v.to(DEV)
+        got = ops.gemv_rope_append(x, w, Hq, Hkv, d, cos, sin, pos, kc, vc, norm_w=nw if norm else None, eps=1e-5).cpu()
+        what = f"d={d} M={M} norm={norm}"
+        assert torch.equal(got[:, :nq], rot[:, :nq]), (what, "q", int((got[:, :nq] != rot[:, :nq]).sum()))
+        kwant, vwant = base_k.clone(), base_v.clone()
+        for m, pm in enumerate(positions):
+            kwant[m, pm], vwant[m, pm] = rot[m, nq:], pre[m, nq + nk:]
+        kgot, vgot = kc.cpu(), vc.cpu()
+        assert torch.equal(kgot, kwant), (what, "k cache", int((kgot != kwant).sum()))
+        assert torch.equal(vgot, vwant), (what, "v cache", int((vgot != vwant).sum()))
+
+
+def test_gemv_plain_stream_beyond_32bit_offsets(ops):
+    """A weight whose rows lie more than 0xf0000000 bytes apart end to end (a row-strided view over one 4.25 GiB allocation) is beyond the
+    32-bit buffer offsets of the vector-ALU and MFMA GEMVs: up to four rows take the plain gemv_kernel stream (K split over four waves for
+    N <= 8192 with K >= 8192, else one), which must match fp64 with test_gemv's bounds, epilogues included; five rows, the SwiGLU and the
+    RoPE-append GEMVs are refused (MM355_EUNSUPPORTED), the callers take the GEMM."""
+    from metamorph_amd.lib import Mm355Error
+    total = (1 << 31) + (1 << 27)                                         # elements of the one allocation (4.25 GiB)
+    buf = torch.empty(total, device=DEV, dtype=torch.bfloat16)
+    for (N, K) in ((64, 8192), (130, 1032)):                              # K split 4 / K split 1
+        ldw = (0x78000000 // (N - 1) // 8 + 1) * 8                        # (N - 1) ldw 2 > 0xf0000000
+        assert (N - 1) * ldw * 2 + 2 * K > 0xf0000000 and (N - 1) * ldw + K <= total
+        wh = rnd(N, K, seed=N, scale=0.05)
+        w = buf.as_strided((N, K), (ldw, 1))
+        w.copy_(wh.to(DEV))
+        for M in (1, 2, 3, 4):
+            x, b, r = rnd(M, K, seed=M), rnd(N, seed=M + 1), rnd(M, N, seed=M + 2)
+            xd = x.to(DEV)
+            ref = x.double() @ wh.double().t()
+            what = f"gemv beyond 32-bit offsets {M}x{N}x{K}"
+            close(ops.gemv(xd, w), ref, 1e-2, 0.02, what)
+            close(ops.gemv(xd, w, bias=b.to(DEV), gelu="erf"), R.gelu_erf(ref + b.double()), 1e-2, 0.02, what + " bias+gelu")
+            close(ops.gemv(xd, w, residual=r.to(DEV)), ref + r.double(), 1e-2, 0.03, what + " residual")
+            of = torch.empty(M, N, device=DEV, dtype=torch.float32)
+            close(ops.gemv(xd, w, out=of), ref, 1e-4, 2e-3, what + " f32")
+        x5 = rnd(5, K, seed=5).to(DEV)
+        assert not ops.gemv_supported(x5, w)
+        with pytest.raises(Mm355Error, match=r"\(-2\)$"):
+            ops.gemv(x5, w)
+        if N == 64:
+            # the same view as a fused gate|up (I = 32) and q|k|v (2 query heads, 1 KV head of 16) weight: no fused form beyond 32-bit offsets
+            x = rnd(2, K, seed=9).to(DEV)
+            with pytest.raises(Mm355Error, match=r"\(-2\)$"):
+                ops.gemv_swiglu(x, w, 32)
+            cos, sin = ops.rope_table(8, 16, 10000.0, DEV)
+            kc = torch.zeros(2, 8, 16, device=DEV, dtype=torch.bfloat16)
+            with pytest.raises(Mm355Error, match=r"\(-2\)$"):
+                ops.gemv_rope_append(x, w, 2, 1, 16, cos, sin, torch.zeros(2, dtype=torch.int32, device=DEV), kc, kc.clone())
 
 
 @pytest.mark.parametrize("variant,lens", [(0, [2700, 300]), (0, [700, 300]), (0, [100, 3000]), (1, [700, 300])])
