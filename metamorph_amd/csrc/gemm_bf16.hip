@@ -274,10 +274,7 @@ MM_DEV void gemm_epilogue_rope(f32x4 (&acc)[8][4], const GemmArgs& a, unsigned c
     }
 }
 
-// TNL = true: both operands are stored contraction-major ("TN": A = At[K][M], B = Bt[K][N], C = At^T Bt), which is the
-// weight-gradient form dW = dY^T X on the activations as they lie in memory -- no transposed copies.  LDS tiles are then
-// [64 k][256] with the MFMA fragments gathered by ds_read_b64_tr_b16 (hardware 4x16 transpose read).
-template <int BM, int BN, int WM, int WN, bool GLDS, int PIPE = 0, bool TNL = false>
+template <int BM, int BN, int WM, int WN, bool GLDS, int PIPE = 0>
 __global__ __launch_bounds__(WM* WN * 64) void gemm_nt_kernel(GemmArgs a) {
     constexpr int NT = WM * WN * 64, NW = WM * WN;
     constexpr int TM = BM / WM, TN = BN / WN, FM = TM / 16, FN = TN / 16;
@@ -311,8 +308,8 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_nt_kernel(GemmArgs a) {
     // split-K: slice blockIdx.y of K (prompt-pass shapes: a few hundred rows against one weight -- the K loop is a latency chain of one
     // LDS-DMA round trip per 64-wide tile; S slices run as S times as many workgroups side by side); C = fp32 partials [slice][M][ldc]
     const int sl = a.kslice ? (int)blockIdx.y : 0;
-    const uint16_t* Ab = a.A + (TNL ? (int64_t)sl * a.kslice * a.lda : (int64_t)sl * a.kslice);
-    const uint16_t* Bb = a.B + (TNL ? (int64_t)sl * a.kslice * a.ldb : (int64_t)sl * a.kslice);
+    const uint16_t* Ab = a.A + (int64_t)sl * a.kslice;
+    const uint16_t* Bb = a.B + (int64_t)sl * a.kslice;
     const int M = a.M, N = a.N, K = a.kslice ? min(a.kslice, a.K - sl * a.kslice) : a.K;
     const int nk = (K + 63) >> 6;
 
@@ -362,7 +359,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_nt_kernel(GemmArgs a) {
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);
     const uint16_t* srcA[AI];
     const uint16_t* srcB[BI];
-    if constexpr (!TNL) {
+    {
         const int rin = lane >> 3;                           // row inside the 8-row piece
         const int c = (lane & 7) ^ rin;                      // source chunk that belongs in LDS slot (lane & 7)
 #pragma unroll
@@ -371,34 +368,16 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_nt_kernel(GemmArgs a) {
 #pragma unroll
         for (int i = 0; i < BI; ++i)
             srcB[i] = Bb + (int64_t)min(n0 + (i * NW + wave_s) * 8 + rin, N - 1) * a.ldb + c * 8;
-    } else {
-        // [64 k][256 cols] tiles, 512-B rows: a 1-KiB piece is 2 k-rows; physical 16-B chunk = logical ^ f(row) with
-        // f(row) = 2*(row & 3) + 8*((row >> 3) & 1) so that the 8 rows x 2 chunks of one tr-read half-wave hit 16 distinct slots
-        static_assert(!TNL || (BM == 256 && BN == 256), "TN layout: 256x256 tile only");
-        const int rinT = lane >> 5, pcT = lane & 31;
-#pragma unroll
-        for (int i = 0; i < AI; ++i) {
-            const int row = (i * NW + wave_s) * 2 + rinT;
-            const int c = pcT ^ (2 * (row & 3) + 8 * ((row >> 3) & 1));
-            srcA[i] = Ab + (int64_t)row * a.lda + min(m0 + c * 8, M - 8);
-        }
-#pragma unroll
-        for (int i = 0; i < BI; ++i) {
-            const int row = (i * NW + wave_s) * 2 + rinT;
-            const int c = pcT ^ (2 * (row & 3) + 8 * ((row >> 3) & 1));
-            srcB[i] = Bb + (int64_t)row * a.ldb + min(n0 + c * 8, N - 8);
-        }
     }
     auto gdma = [&](int kt, int buf) {
-        const int k0 = kt << 6;
-        const int64_t ka = TNL ? (int64_t)k0 * a.lda : (int64_t)k0, kb = TNL ? (int64_t)k0 * a.ldb : (int64_t)k0;
+        const int64_t k0 = kt << 6;
         unsigned char* sb = smem + buf * STAGE + wave_s * 1024;
 #pragma unroll
         for (int i = 0; i < AI; ++i)
-            __builtin_amdgcn_global_load_lds((gptr_t)(srcA[i] + ka), (lptr_t)(sb + i * NW * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gptr_t)(srcA[i] + k0), (lptr_t)(sb + i * NW * 1024), 16, 0, 0);
 #pragma unroll
         for (int i = 0; i < BI; ++i)
-            __builtin_amdgcn_global_load_lds((gptr_t)(srcB[i] + kb), (lptr_t)(sb + A_BYTES + i * NW * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gptr_t)(srcB[i] + k0), (lptr_t)(sb + A_BYTES + i * NW * 1024), 16, 0, 0);
     };
 
     // ---- main loop -----------------------------------------------------------------------------
@@ -451,47 +430,17 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_nt_kernel(GemmArgs a) {
         // four 16-MFMA units per K tile: (k-step, A half) = (0,lo) (0,hi) (1,lo) (1,hi); two rotating A register
         // sets X/Y and two B sets P/Q, each refilled from LDS one unit before it is consumed.
         bf16x8 X[HM], Y[HM], P[FN], Q[FN];
-        // TN layout: per-lane byte offsets of the 8-byte transposed-read granules (excluding the k-step immediate)
-        int toA[TNL ? FM : 1], toB[TNL ? FN : 1];
-        if constexpr (TNL) {
-            const int j4 = fr >> 2, q = fr & 3, f = 2 * j4 + 8 * (fq & 1);
-#pragma unroll
-            for (int i = 0; i < FM; ++i)
-                toA[i] = (fq * 8 + j4) * 512 + ((((wm * TM) >> 3) + i * 2 + (q >> 1)) ^ f) * 16 + (q & 1) * 8;
-#pragma unroll
-            for (int j = 0; j < FN; ++j)
-                toB[j] = A_BYTES + (fq * 8 + j4) * 512 + ((((wn * TN) >> 3) + j * 2 + (q >> 1)) ^ f) * 16 + (q & 1) * 8;
-        }
-        typedef __attribute__((ext_vector_type(4))) short s16x4;
-        typedef __attribute__((address_space(3))) s16x4* lds4_t;
-        auto trfrag = [&](const unsigned char* p) -> bf16x8 {
-            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4_t)p);
-            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4_t)(p + 4 * 512));
-            return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        };
         auto rdA = [&](bf16x8 (&af)[HM], int buf, int half, int kk) {
             const int sw = kk ? sw1 : sw0;
-            if constexpr (TNL) {
-                const unsigned char* sb = smem + buf * STAGE + kk * 32 * 512;
+            const unsigned char* sb = smem + buf * STAGE + a_off + half * HM * 2048 + sw;
 #pragma unroll
-                for (int i = 0; i < HM; ++i) af[i] = trfrag(sb + toA[half * HM + i]);
-            } else {
-                const unsigned char* sb = smem + buf * STAGE + a_off + half * HM * 2048 + sw;
-#pragma unroll
-                for (int i = 0; i < HM; ++i) af[i] = *(const bf16x8*)(sb + i * 2048);
-            }
+            for (int i = 0; i < HM; ++i) af[i] = *(const bf16x8*)(sb + i * 2048);
         };
         auto rdB = [&](bf16x8 (&bf)[FN], int buf, int kk) {
             const int sw = kk ? sw1 : sw0;
-            if constexpr (TNL) {
-                const unsigned char* sb = smem + buf * STAGE + kk * 32 * 512;
+            const unsigned char* sb = smem + buf * STAGE + b_off + sw;
 #pragma unroll
-                for (int j = 0; j < FN; ++j) bf[j] = trfrag(sb + toB[j]);
-            } else {
-                const unsigned char* sb = smem + buf * STAGE + b_off + sw;
-#pragma unroll
-                for (int j = 0; j < FN; ++j) bf[j] = *(const bf16x8*)(sb + j * 2048);
-            }
+            for (int j = 0; j < FN; ++j) bf[j] = *(const bf16x8*)(sb + j * 2048);
         };
         auto mm = [&](const bf16x8 (&af)[HM], const bf16x8 (&bf)[FN], int half) {
             __builtin_amdgcn_s_setprio(1);
@@ -578,9 +527,8 @@ template <int N> MM_DEV void wait_vmcnt() {
 
 // body of one 256x256 output tile; `bid` = index of the workgroup within ITS problem (the pair kernel below runs two problems
 // in one grid)
-template <bool TA, bool TB, int ABL = 0, bool SWI = false, bool SWB = false, bool ROPE = false>
+template <int ABL = 0, bool SWI = false, bool SWB = false, bool ROPE = false>
 MM_DEV void gemm_pp_tile(const GemmArgs& a, const int bid, unsigned char* smem) {
-    static_assert(!(SWI || SWB || ROPE) || (!TA && !TB), "fused epilogues: row-major operands");
     constexpr int BM = 256, BN = 256, TM = 128, TN = 64, FM = 8, FN = 4;
     constexpr int BUF = (BM + BN) * 128;                    // 64 KiB per K tile
     constexpr int A_BYTES = BM * 128;
@@ -631,17 +579,12 @@ MM_DEV void gemm_pp_tile(const GemmArgs& a, const int bid, unsigned char* smem) 
         for (int kd = 0; kd < 4; ++kd) {
             const bool isA = kd == 0 || kd == 3;
             const int blk = isA ? (kd == 3) : (kd - 1);      // rows / cols block 0 or 1 of the wave tile
-            if (isA && !TA) {                                // [256 m][64 k] image, piece = 8 rows x 128 B
+            if (isA) {                                       // [256 m][64 k] image, piece = 8 rows x 128 B
                 const int rin = lane >> 3, c = (lane & 7) ^ rin;
                 const int row = h * 128 + blk * 64 + wave_s * 8;
                 src[kd][h] = (uint32_t)((int64_t)(min(m0 + row + rin, M - 1) - m0) * a.lda * 2 + c * 16);   // from row m0
                 dst[kd][h] = row * 128;
-            } else if (isA && TA) {                          // four [64 k][64 m] images (128-B rows), piece = 8 k rows
-                const int krow = wave_s * 8 + (lane >> 3);
-                const int c = (lane & 7) ^ (2 * ((krow >> 1) & 1) + 4 * ((krow >> 3) & 1));
-                src[kd][h] = (uint32_t)((int64_t)krow * a.lda * 2 + min(m0 + h * 128 + blk * 64 + c * 8, M - 8) * 2);
-                dst[kd][h] = (h * 2 + blk) * 8192 + wave_s * 1024;
-            } else if (!TB) {                                // [256 n][64 k] image
+            } else {                                         // [256 n][64 k] image
                 const int rin = lane >> 3, c = (lane & 7) ^ rin;
                 const int row = (q >> 2) * 64 + blk * 32 + (q & 3) * 8;
                 if constexpr (SWI) {
@@ -658,87 +601,45 @@ MM_DEV void gemm_pp_tile(const GemmArgs& a, const int bid, unsigned char* smem) 
                     src[kd][h] = (uint32_t)((int64_t)(min(n0 + row + rin, N - 1) - n0) * a.ldb * 2 + c * 16);   // from row n0
                 }
                 dst[kd][h] = A_BYTES + row * 128;
-            } else {                                         // eight [64 k][32 n] images (64-B rows), piece = 16 k rows
-                const int krow = (q & 3) * 16 + (lane >> 2);
-                const int c = (lane & 3) ^ (2 * ((krow >> 3) & 1));
-                src[kd][h] = (uint32_t)((int64_t)krow * a.ldb * 2 + min(n0 + (q >> 2) * 64 + blk * 32 + c * 8, N - 8) * 2);
-                dst[kd][h] = A_BYTES + ((q >> 2) * 2 + blk) * 4096 + (q & 3) * 1024;
             }
         }
     }
     // buffer-addressed DMA (resource in SGPRs + 32-bit lane offset + scalar K offset): no 64-bit per-lane address arithmetic.
-    // A row-major operand is based at the tile's first row (one scalar 64-bit multiply-add per workgroup), so the 31-bit
-    // offsets only span 256 rows + the K extent and the operand itself may be of any size; contraction-major operands are
-    // based at the matrix (their offsets run over K rows: pp_eligible keeps those below 2 GiB).
-    const uint16_t* baseA = TA ? a.A : a.A + (int64_t)m0 * a.lda;
-    const uint16_t* baseB = (TB || SWI) ? a.B : a.B + (int64_t)n0 * a.ldb;
+    // An operand is based at the tile's first row (one scalar 64-bit multiply-add per workgroup), so the 31-bit offsets only
+    // span 256 rows + the K extent and the operand itself may be of any size (SWI: the fused weight, based at its row 0).
+    const uint16_t* baseA = a.A + (int64_t)m0 * a.lda;
+    const uint16_t* baseB = SWI ? a.B : a.B + (int64_t)n0 * a.ldb;
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)baseA, 0, 0x7fffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)baseB, 0, 0x7fffffff, 0x00020000);
-    const int kstepA = TA ? (int)(a.lda * 128) : 128, kstepB = TB ? (int)(a.ldb * 128) : 128;   // bytes per K tile
     auto issue = [&](int kd, int tile) {                     // quarter kd of K tile `tile`
         unsigned char* sb = smem + (tile & 1) * BUF;
         const bool isA = kd == 0 || kd == 3;
 #pragma unroll
         for (int h = 0; h < 2; ++h)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(isA ? rsA : rsB, (lptr_t)(sb + dst[kd][h]), 16, src[kd][h],
-                                                     (ABL == 3 ? (tile & 1) : tile) * (isA ? kstepA : kstepB), 0, 0);   // ABL 3: K tiles 0 / 1 over and over
+                                                     (ABL == 3 ? (tile & 1) : tile) * 128, 0, 0);   // 128 B per K tile; ABL 3: K tiles 0 / 1 over and over
     };
 
-    // ---- fragments: row-major operands by ds_read_b128, contraction-major ones by two ds_read_b64_tr_b16 (k rows j..j+3 and
-    //      j+4..j+7 of a [k][16 cols] block; chunk swizzles f(k) chosen so that a 32-lane gather touches every bank once)
+    // ---- fragments by ds_read_b128
     const int sw0 = ((fq) ^ (fr & 7)) << 4;
     const int sw1 = ((4 + fq) ^ (fr & 7)) << 4;
     const int a_off = (wm * TM + fr) * 128;
     const int b_off = A_BYTES + (wn * TN + fr) * 128;
-    int toA[4], toB[2];
-    {
-        const int j4 = fr >> 2, q = fr & 3;
-        const int fa = 2 * ((j4 >> 1) & 1) + 4 * (fq & 1), fb = 2 * (fq & 1);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) toA[i] = (fq * 8 + j4) * 128 + (((i * 2 + (q >> 1)) ^ fa) << 4) + (q & 1) * 8;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) toB[j] = (fq * 8 + j4) * 64 + (((j * 2 + (q >> 1)) ^ fb) << 4) + (q & 1) * 8;
-    }
-    typedef __attribute__((ext_vector_type(4))) short s16x4;
-    typedef __attribute__((address_space(3))) s16x4* lds4_t;
-    auto trfrag = [&](const unsigned char* p, int hi_off) -> bf16x8 {
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4_t)p);
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4_t)(p + hi_off));
-        return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    };
     bf16x8 A[2][4][2], B[2][2][2];
     auto rdA = [&](int ah, int tile) {
-        if constexpr (!TA) {
-            const unsigned char* sb = smem + (tile & 1) * BUF + a_off + ah * 8192;
+        const unsigned char* sb = smem + (tile & 1) * BUF + a_off + ah * 8192;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                A[ah][i][0] = *(const bf16x8*)(sb + i * 2048 + sw0);
-                A[ah][i][1] = *(const bf16x8*)(sb + i * 2048 + sw1);
-            }
-        } else {
-            const unsigned char* sb = smem + (tile & 1) * BUF + (wm * 2 + ah) * 8192;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                A[ah][i][0] = trfrag(sb + toA[i], 4 * 128);
-                A[ah][i][1] = trfrag(sb + toA[i] + 32 * 128, 4 * 128);
-            }
+        for (int i = 0; i < 4; ++i) {
+            A[ah][i][0] = *(const bf16x8*)(sb + i * 2048 + sw0);
+            A[ah][i][1] = *(const bf16x8*)(sb + i * 2048 + sw1);
         }
     };
     auto rdB = [&](int bh, int tile) {
-        if constexpr (!TB) {
-            const unsigned char* sb = smem + (tile & 1) * BUF + b_off + bh * 4096;
+        const unsigned char* sb = smem + (tile & 1) * BUF + b_off + bh * 4096;
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                B[bh][j][0] = *(const bf16x8*)(sb + j * 2048 + sw0);
-                B[bh][j][1] = *(const bf16x8*)(sb + j * 2048 + sw1);
-            }
-        } else {
-            const unsigned char* sb = smem + (tile & 1) * BUF + A_BYTES + (wn * 2 + bh) * 4096;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                B[bh][j][0] = trfrag(sb + toB[j], 4 * 64);
-                B[bh][j][1] = trfrag(sb + toB[j] + 32 * 64, 4 * 64);
-            }
+        for (int j = 0; j < 2; ++j) {
+            B[bh][j][0] = *(const bf16x8*)(sb + j * 2048 + sw0);
+            B[bh][j][1] = *(const bf16x8*)(sb + j * 2048 + sw1);
         }
     };
 #if defined(MM355_SWB_ABL) && MM355_SWB_ABL == 3
@@ -882,30 +783,30 @@ MM_DEV void gemm_pp_tile(const GemmArgs& a, const int bid, unsigned char* smem) 
 
 __global__ __launch_bounds__(512) void gemm_pp_swiglu_kernel(GemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    gemm_pp_tile<false, false, 0, true>(a, blockIdx.x, smem);
+    gemm_pp_tile<0, true>(a, blockIdx.x, smem);
 }
 
 __global__ __launch_bounds__(512) void gemm_pp_rope_kernel(GemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    gemm_pp_tile<false, false, 0, false, false, true>(a, blockIdx.x, smem);
+    gemm_pp_tile<0, false, false, true>(a, blockIdx.x, smem);
 }
 
 __global__ __launch_bounds__(512) void gemm_pp_swiglu_bwd_kernel(GemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    gemm_pp_tile<false, false, 0, false, true>(a, blockIdx.x, smem);
+    gemm_pp_tile<0, false, true>(a, blockIdx.x, smem);
 }
 
-template <bool TA, bool TB, int ABL = 0>
+template <int ABL = 0>
 __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 #ifdef MM355_PP_PERSIST                                      // TIMING experiment (tools/build_pp_persist.sh): one workgroup per CU walks the tiles
     const int total = a.ntm * a.ntn;
     for (int bid = blockIdx.x; bid < total; bid += gridDim.x) {
-        gemm_pp_tile<TA, TB, ABL>(a, bid, smem);
+        gemm_pp_tile<ABL>(a, bid, smem);
         __syncthreads();
     }
 #else
-    gemm_pp_tile<TA, TB, ABL>(a, blockIdx.x, smem);
+    gemm_pp_tile<ABL>(a, blockIdx.x, smem);
 #endif
 }
 
@@ -915,15 +816,14 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs a) {
 __global__ __launch_bounds__(512) void gemm_pp_pair_kernel(GemmArgs a0, GemmArgs a1, int n0) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int bid = blockIdx.x;
-    if (bid < n0) gemm_pp_tile<false, false>(a0, bid, smem);
-    else gemm_pp_tile<false, false>(a1, bid - n0, smem);
+    if (bid < n0) gemm_pp_tile(a0, bid, smem);
+    else gemm_pp_tile(a1, bid - n0, smem);
 }
 
-template <int BM, int BN, int WM, int WN, bool GLDS, int PIPE, bool TNL>
+template <int BM, int BN, int WM, int WN, bool GLDS, int PIPE>
 int launch_gemm(GemmArgs a, hipStream_t s);
 
-// TA / TB: operand given contraction-major ([K][M] / [K][N]); eligibility of the K extent and the 31-bit byte offsets is the
-// caller's business (pp_eligible)
+// eligibility of the K extent and the 31-bit byte offsets is the caller's business (pp_eligible)
 constexpr int PP_LDS = 2 * (256 + 256) * 128;               // 128 KiB
 
 // tile grid + raster knobs of one ping-pong problem; returns its tile count (<= 0: not launchable)
@@ -934,16 +834,16 @@ int64_t pp_prepare(GemmArgs& a) {
     return (int64_t)a.ntm * a.ntn;
 }
 
-template <bool TA, bool TB, int ABL = 0>
+template <int ABL = 0>
 int launch_gemm_pp_t(GemmArgs a, hipStream_t s) {
     static std::atomic<uint64_t> lds_ok{0};              // per-device opt-in to > 64 KiB of dynamic LDS
-    if (mm_ensure_dynamic_lds((const void*)gemm_pp_kernel<TA, TB, ABL>, PP_LDS, lds_ok) != MM355_OK) return MM355_ELAUNCH;
+    if (mm_ensure_dynamic_lds((const void*)gemm_pp_kernel<ABL>, PP_LDS, lds_ok) != MM355_OK) return MM355_ELAUNCH;
     const int64_t total = pp_prepare(a);
     if (total <= 0 || total > 0x7fffffff) return MM355_EINVAL;
 #ifdef MM355_PP_PERSIST
-    hipLaunchKernelGGL((gemm_pp_kernel<TA, TB, ABL>), dim3((unsigned)std::min<int64_t>(total, MM355_PP_PERSIST)), dim3(512), PP_LDS, s, a);
+    hipLaunchKernelGGL((gemm_pp_kernel<ABL>), dim3((unsigned)std::min<int64_t>(total, MM355_PP_PERSIST)), dim3(512), PP_LDS, s, a);
 #else
-    hipLaunchKernelGGL((gemm_pp_kernel<TA, TB, ABL>), dim3((unsigned)total), dim3(512), PP_LDS, s, a);
+    hipLaunchKernelGGL((gemm_pp_kernel<ABL>), dim3((unsigned)total), dim3(512), PP_LDS, s, a);
 #endif
     return mm_launch_status();
 }
@@ -957,27 +857,24 @@ int launch_gemm_pp_pair(GemmArgs a0, GemmArgs a1, hipStream_t s) {
     return mm_launch_status();
 }
 
-// whole pairs of K tiles, and every source byte offset below 2 GiB: (K rows * ld + M) for a contraction-major operand, based
-// at the matrix; (256 rows * ld + K) for a row-major one, based at the tile's first row
-bool pp_eligible(const GemmArgs& a, bool ta, bool tb) {
+// whole pairs of K tiles, and every source byte offset below 2 GiB: 256 rows * ld + K, based at the tile's first row
+bool pp_eligible(const GemmArgs& a) {
     if (a.K < 128 || (a.K & 127)) return false;
-    const int64_t ea = ta ? ((int64_t)a.K * a.lda + a.M) * 2 : (256 * a.lda + a.K) * 2;
-    const int64_t eb = tb ? ((int64_t)a.K * a.ldb + a.N) * 2 : (256 * a.ldb + a.K) * 2;
-    if (ta && (a.M < 8 || (a.M & 7))) return false;
-    if (tb && (a.N < 8 || (a.N & 7))) return false;
+    const int64_t ea = (256 * a.lda + a.K) * 2;
+    const int64_t eb = (256 * a.ldb + a.K) * 2;
     return ea < 0x7fffffffLL && eb < 0x7fffffffLL;
 }
 
 int launch_gemm_pp(GemmArgs a, hipStream_t s) {
-    if (!pp_eligible(a, false, false)) return launch_gemm<256, 256, 2, 4, true, 1, false>(a, s);
-    return launch_gemm_pp_t<false, false>(a, s);
+    if (!pp_eligible(a)) return launch_gemm<256, 256, 2, 4, true, 1>(a, s);
+    return launch_gemm_pp_t(a, s);
 }
 
-template <int BM, int BN, int WM, int WN, bool GLDS, int PIPE = 0, bool TNL = false>
+template <int BM, int BN, int WM, int WN, bool GLDS, int PIPE = 0>
 int launch_gemm(GemmArgs a, hipStream_t s) {
     constexpr int STAGE = (BM + BN) * 128;
     constexpr int LDS = 2 * STAGE;
-    auto kern = gemm_nt_kernel<BM, BN, WM, WN, GLDS, PIPE, TNL>;
+    auto kern = gemm_nt_kernel<BM, BN, WM, WN, GLDS, PIPE>;
     static std::atomic<uint64_t> lds_ok{0};              // per-device opt-in to > 64 KiB of dynamic LDS
     if (mm_ensure_dynamic_lds((const void*)kern, LDS, lds_ok) != MM355_OK) return MM355_ELAUNCH;
     a.ntm = (a.M + BM - 1) / BM;
@@ -1266,13 +1163,13 @@ static int splitk_partials(const mm355_bf16* A, int64_t lda, const mm355_bf16* B
     a.ntn = (int)((N + BN - 1) / BN);
     slices = (int)((K + a.kslice - 1) / a.kslice);
     if (M <= 32) {
-        auto kern = gemm_nt_kernel<32, BN, 1, 4, true, 0, false>;
+        auto kern = gemm_nt_kernel<32, BN, 1, 4, true, 0>;
         static std::atomic<uint64_t> lds_ok{0};
         if (mm_ensure_dynamic_lds((const void*)kern, LDS, lds_ok) != MM355_OK) return MM355_ELAUNCH;
         a.ntm = 1;
         hipLaunchKernelGGL(kern, dim3((unsigned)(a.ntm * a.ntn), (unsigned)slices), dim3(256), 2 * (32 + BN) * 128, stream, a);
     } else {
-        auto kern = gemm_nt_kernel<64, BN, 1, 4, true, 0, false>;
+        auto kern = gemm_nt_kernel<64, BN, 1, 4, true, 0>;
         static std::atomic<uint64_t> lds_ok{0};
         if (mm_ensure_dynamic_lds((const void*)kern, LDS, lds_ok) != MM355_OK) return MM355_ELAUNCH;
         a.ntm = (int)((M + 63) / 64);
@@ -1417,9 +1314,9 @@ extern "C" int mm355_gemm_bf16(const mm355_bf16* A, int64_t lda, const mm355_bf1
         case 9: return launch_gemm<64, 128, 1, 4, true>(a, s);    // 64 x 128 tiles, four waves side by side (small-M / prompt-pass shapes)
         case 11: return launch_gemm_pp(a, s);
 #ifdef MM355_ABLATIONS                                       // TIMING-ONLY builds (tools/build_ablation.sh ... -DMM355_ABLATIONS): wrong results on purpose
-        case 91: return launch_gemm_pp_t<false, false, 1>(a, s);     // no DMA
-        case 92: return launch_gemm_pp_t<false, false, 2>(a, s);     // no fragment reads
-        case 93: return launch_gemm_pp_t<false, false, 3>(a, s);     // every DMA issued, but always K tiles 0 / 1 (L2-resident sources)
+        case 91: return launch_gemm_pp_t<1>(a, s);     // no DMA
+        case 92: return launch_gemm_pp_t<2>(a, s);     // no fragment reads
+        case 93: return launch_gemm_pp_t<3>(a, s);     // every DMA issued, but always K tiles 0 / 1 (L2-resident sources)
 #endif
         default: return MM355_EUNSUPPORTED;                // retired (3-6, 8, 10, 12-14) or unknown
     }
@@ -1436,7 +1333,7 @@ int pair_problem(GemmArgs& a, const mm355_bf16* A, int64_t lda, const mm355_bf16
     a.A = A; a.B = B; a.C = C; a.bias = nullptr; a.res = nullptr;
     a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldr = 0; a.res_mod = 0;
     a.M = (int)M; a.N = (int)N; a.K = (int)K; a.flags = flags; a.ntm = a.ntn = 0;
-    return pp_eligible(a, false, false) ? MM355_OK : MM355_EUNSUPPORTED;
+    return pp_eligible(a) ? MM355_OK : MM355_EUNSUPPORTED;
 }
 }  // namespace
 
@@ -1451,38 +1348,6 @@ extern "C" int mm355_gemm_pair_bf16(const mm355_bf16* A0, int64_t lda0, const mm
     rc = pair_problem(a1, A1, lda1, B1, ldb1, C1, ldc1, M1, N1, K1, flags1);
     if (rc != MM355_OK) return rc;
     return launch_gemm_pp_pair(a0, a1, (hipStream_t)stream);
-}
-
-extern "C" int mm355_gemm_tn_bf16(const mm355_bf16* At, int64_t lda, const mm355_bf16* Bt, int64_t ldb, void* C, int64_t ldc, int64_t M,
-                                  int64_t N, int64_t K, uint32_t flags, void* stream) {
-    (void)hipGetLastError();   // drop any stale, unrelated runtime status before we launch
-    if (!At || !Bt || !C || M < 8 || N < 8 || K <= 0) return MM355_EINVAL;
-    if ((M & 7) || (N & 7) || (lda & 7) || (ldb & 7) || !mm_aligned16(At) || !mm_aligned16(Bt) || !mm_aligned16(C)) return MM355_EINVAL;
-    if (K % 64) return MM355_EUNSUPPORTED;                  // contraction rows are DMA'd unmasked: whole 64-row tiles only
-    if (flags & ~(MM355_GEMM_ACCUMULATE | MM355_GEMM_OUT_F32)) return MM355_EINVAL;
-    if (M > 0x7fffffff || N > 0x7fffffff || K > 0x7fffffff) return MM355_EINVAL;
-    GemmArgs a = {};
-    a.A = At; a.B = Bt; a.C = C; a.bias = nullptr; a.res = nullptr;
-    a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldr = 0; a.res_mod = 0;
-    a.M = (int)M; a.N = (int)N; a.K = (int)K; a.flags = flags; a.ntm = a.ntn = 0;
-    if (pp_eligible(a, true, true)) return launch_gemm_pp_t<true, true>(a, (hipStream_t)stream);
-    return launch_gemm<256, 256, 2, 4, true, 1, true>(a, (hipStream_t)stream);
-}
-
-extern "C" int mm355_gemm_nn_bf16(const mm355_bf16* A, int64_t lda, const mm355_bf16* Bt, int64_t ldb, void* C, int64_t ldc, int64_t M,
-                                  int64_t N, int64_t K, const mm355_bf16* residual, int64_t ldr, uint32_t flags, void* stream) {
-    (void)hipGetLastError();   // drop any stale, unrelated runtime status before we launch
-    if (!A || !Bt || !C || M <= 0 || N < 8 || K <= 0) return MM355_EINVAL;
-    if ((N & 7) || (lda & 7) || (ldb & 7) || (ldc & 7) || !mm_aligned16(A) || !mm_aligned16(Bt) || !mm_aligned16(C)) return MM355_EINVAL;
-    if (flags & ~(MM355_GEMM_ACCUMULATE | MM355_GEMM_OUT_F32 | MM355_GEMM_RESIDUAL)) return MM355_EINVAL;
-    if ((flags & MM355_GEMM_RESIDUAL) && (!residual || !mm_aligned16(residual) || (ldr & 7))) return MM355_EINVAL;
-    if (M > 0x7fffffff || N > 0x7fffffff || K > 0x7fffffff) return MM355_EINVAL;
-    GemmArgs a = {};
-    a.A = A; a.B = Bt; a.C = C; a.bias = nullptr; a.res = residual;
-    a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldr = ldr; a.res_mod = 0;
-    a.M = (int)M; a.N = (int)N; a.K = (int)K; a.flags = flags; a.ntm = a.ntn = 0;
-    if (!pp_eligible(a, false, true)) return MM355_EUNSUPPORTED;   // caller: mm355_transpose_bf16 + mm355_gemm_bf16
-    return launch_gemm_pp_t<false, true>(a, (hipStream_t)stream);
 }
 
 extern "C" int mm355_transpose_bf16(const mm355_bf16* in, int64_t ld_in, int64_t rows, int64_t cols, mm355_bf16* out,

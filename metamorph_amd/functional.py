@@ -19,30 +19,21 @@ from . import ops
 BF16 = torch.bfloat16
 # Kernel-composition switches of the decoder layer.  The product runs the defaults (each one measured the winner on MI355X, DESIGN.md
 # section 4); tools/ and tests flip them through set_variant() for same-box A/B runs -- there is no environment switch.
-#   dw_tn           weight / input gradients on the operands as they lie in memory (contraction-major ping-pong GEMM, no transposed copies):
-#                   TN 1.04-1.10 PFLOP/s, NN 1.25-1.30 vs 1.45-1.5 for the row-major kernel + explicit transposes -> off
-#   dw_pair         down_proj and qkv weight gradients as ONE launch when that saves a wave of workgroups (896 + 384 tiles = 5 waves, not 4 + 2)
-#   norm_t          backward rebuilds the RMSNorm outputs contraction-major from the saved rstd in one pass (rmsnorm_apply_t)
 #   fuse_swiglu     SwiGLU in the gate|up GEMM's epilogue (same bits, one pass less)
 #   fuse_rope       RoPE in the q|k|v GEMM's epilogue / inverse RoPE in the attention backward epilogues (same bits)
 #   fuse_swiglu_bwd SwiGLU backward in the down_proj input-gradient GEMM's epilogue (same bits)
 #   decode_graph    the per-token decode step is captured once as a hipGraph and replayed
-VARIANTS = {"dw_tn": False, "dw_pair": True, "norm_t": True, "fuse_swiglu": True, "fuse_rope": True, "fuse_swiglu_bwd": True, "decode_graph": True, "decode_fused": True,
+VARIANTS = {"fuse_swiglu": True, "fuse_rope": True, "fuse_swiglu_bwd": True, "decode_graph": True, "decode_fused": True,
             # keep the transposed copies of the decoder weights (the B operands of the input-gradient GEMMs) from one backward call to
             # the next until the optimizer rewrites the parameters: under gradient accumulation the four transposes per layer are made
             # once per optimizer step instead of once per micro-batch (+2 bytes per decoder parameter while a window is open)
             "wt_cache": False,
             "decode_fold_rows": 4,                           # decode step: fold the RMSNorms into the GEMVs' operand reads up to this many rows
-            # one launch for an input-gradient GEMM and the weight-gradient GEMM that reads the same dy: (dn2, dW_gate_up) and (dX_o, dW_o)
-            # -- the mechanism of dw_pair (mm355_gemm_pair_bf16: same kernel body, same bits), saving one ramp and tail per pair
-            "dx_pair": True,
             # prompt pass of a cached decode: q|k|v, o and down projections through the split-K GEMM (a few hundred rows: the plain kernels are a
             # latency chain over K there)
             "prefill_splitk": True,
-            # decode step of MORE than 16 sequences: one pass over the weights through the split-K GEMM instead of one GEMV pass per 16 rows
-            "decode_wide_gemm": True,
-            # ... with RoPE + cache append, the two RMSNorms and SwiGLU folded into the reduce launches of the split projections (nine launches per
-            # layer instead of thirteen; same bits)
+            # decode step of MORE than 16 sequences (one pass over the weights through the split-K GEMM): RoPE + cache append, the two RMSNorms
+            # and SwiGLU folded into the reduce launches of the split projections (nine launches per layer instead of thirteen; same bits)
             "decode_wide_fused": True, "decode_wide_gu_gemv": True,
             # the prompt pass of ONE sequence (a few hundred rows): the same reduce launches (RoPE + the K / V rows straight into the cache, both
             # RMSNorms), attention reading K / V from the cache rows -- same bits as the prefill_splitk pass, five launches per layer less
@@ -231,15 +222,8 @@ def _dw_operands(dy2d, x2d, dyT=None, xT=None):
 
 
 def weight_grad_gemm(dy2d, x2d, out, accumulate, dyT=None, xT=None):
-    """out[N,K] (+)= dy[M,N]^T @ x[M,K].  Token counts that are whole pairs of 64-row tiles go straight through the
-    contraction-major ping-pong kernel (operands as they lie in memory, fragments gathered by ds_read_b64_tr_b16); ragged
-    or small problems fall back to explicit transposes.  Opt-in (MM355VARIANTS["dw_tn"]=1): see the note at the top."""
-    if dyT is None and xT is None and VARIANTS["dw_tn"]:
-        big = ((dy2d.shape[1] + 255) // 256) * ((x2d.shape[1] + 255) // 256) >= 128
-        if big and ops.gemm_tn_supported(dy2d, x2d) and ops.gemm_pp_operands_ok(dy2d.shape[0], dy2d, x2d):
-            ops.gemm_tn(dy2d, x2d, out, accumulate=accumulate)
-            return
-    # dyT / xT: contraction-major copies a producer already wrote (the row-major argument may then be None)
+    """out[N,K] (+)= dy[M,N]^T @ x[M,K] as the NT GEMM of the explicitly transposed operands.  dyT / xT: contraction-major
+    copies a producer already wrote (the row-major argument may then be None)."""
     a, b = _dw_operands(dy2d, x2d, dyT, xT)
     ops.gemm(a, b, out=out, accumulate=accumulate)
 
@@ -293,9 +277,7 @@ def _pairable(a0, b0, a1, b1):
 
 
 def input_grad_gemm(dy2d, w, out=None, residual=None):
-    """dx[M,K] = dy[M,N] @ w[N,K]  (+ residual); the weight is read untransposed whenever the ping-pong kernel applies"""
-    if VARIANTS["dw_tn"] and ops.gemm_nn_supported(dy2d, w):
-        return ops.gemm_nn(dy2d, w, out=out, residual=residual)
+    """dx[M,K] = dy[M,N] @ w[N,K]  (+ residual), the NT GEMM against the transposed weight"""
     return ops.gemm(dy2d, transposed_weight(w), out=out, residual=residual)
 
 
@@ -403,7 +385,7 @@ class DecoderLayerFn(Function):
         # ---- MLP ----
         gu_params = [mlp.gate_proj.weight, mlp.up_proj.weight]
         # full fine-tune on whole 64-row tiles: SwiGLU backward writes act^T and dgu^T itself (no transpose passes over them)
-        fused_t = (not VARIANTS["dw_tn"] and dy.shape[0] % 64 == 0 and m.I % 64 == 0 and mlp.down_proj.weight.requires_grad
+        fused_t = (dy.shape[0] % 64 == 0 and m.I % 64 == 0 and mlp.down_proj.weight.requires_grad
                    and all(p.requires_grad for p in gu_params))
         wdT = wdT_made = None
         if fused_t and VARIANTS["fuse_swiglu_bwd"]:
@@ -429,7 +411,7 @@ class DecoderLayerFn(Function):
         if mlp.down_proj.weight.requires_grad:
             wd = mlp.down_proj.weight
             buf, acc = grad_target(wd)
-            if (VARIANTS["dw_pair"] and not VARIANTS["dw_tn"] and all(p.requires_grad for p in qkv_params)
+            if (all(p.requires_grad for p in qkv_params)
                     and _pair_saves_a_wave(wd.shape[0], wd.shape[1], sum(p.shape[0] for p in qkv_params), h, dy.shape[0])):
                 held = _dw_operands(dy, act, xT=actT) + (buf, acc)
             else:
@@ -440,21 +422,17 @@ class DecoderLayerFn(Function):
         dn2 = None
         if any(p.requires_grad for p in gu_params):
             fb, acc, bufs = fused_grad_target(gu_params)
-            if VARIANTS["dw_tn"] or not VARIANTS["norm_t"]:
-                dn2 = input_grad_gemm(dgu, wgu)
-                weight_grad_gemm(dgu, ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, m.eps), fb, bool(acc), dyT=dguT)
-            else:                                                              # norm output, contraction-major, from the saved rstd
-                rp = dguT.shape[1] if dguT is not None else _padded_rows(x2.shape[0], long_k=True)
-                n2T = ops.rmsnorm_apply_t(x2, layer.post_attention_layernorm.weight, rstd2, rp)
-                a0, b0 = _dw_operands(dgu, None, dyT=dguT, xT=n2T)
-                wguT = transposed_weight(wgu, sources=gu_params)
-                if VARIANTS["dx_pair"] and not VARIANTS["dw_tn"] and _pairable(a0, b0, dgu, wguT):
-                    dn2 = torch.empty((dgu.shape[0], wguT.shape[0]), device=dev, dtype=BF16)
-                    ops.gemm_pair(a0, b0, fb, bool(acc), dgu, wguT, dn2, False)   # the weight gradient's long-K tiles first
-                else:
-                    dn2 = ops.gemm(dgu, wguT)
-                    ops.gemm(a0, b0, out=fb, accumulate=bool(acc))
-                del n2T, a0, b0, wguT
+            rp = dguT.shape[1] if dguT is not None else _padded_rows(x2.shape[0], long_k=True)
+            n2T = ops.rmsnorm_apply_t(x2, layer.post_attention_layernorm.weight, rstd2, rp)   # norm output, contraction-major, from the saved rstd
+            a0, b0 = _dw_operands(dgu, None, dyT=dguT, xT=n2T)
+            wguT = transposed_weight(wgu, sources=gu_params)
+            if _pairable(a0, b0, dgu, wguT):
+                dn2 = torch.empty((dgu.shape[0], wguT.shape[0]), device=dev, dtype=BF16)
+                ops.gemm_pair(a0, b0, fb, bool(acc), dgu, wguT, dn2, False)   # the weight gradient's long-K tiles first
+            else:
+                dn2 = ops.gemm(dgu, wguT)
+                ops.gemm(a0, b0, out=fb, accumulate=bool(acc))
+            del n2T, a0, b0, wguT
             commit_fused_grad(gu_params, fb, acc, bufs)
         if dn2 is None:
             dn2 = input_grad_gemm(dgu, wgu)                                     # [M, h]
@@ -466,18 +444,15 @@ class DecoderLayerFn(Function):
         do = None
         if att.o_proj.weight.requires_grad:
             buf, acc = grad_target(att.o_proj.weight)
-            if VARIANTS["dx_pair"] and not VARIANTS["dw_tn"]:
-                a0, b0 = _dw_operands(dx2, o)
-                woT = transposed_weight(att.o_proj.weight, sources=(att.o_proj.weight,))
-                if _pairable(a0, b0, dx2, woT):
-                    do = torch.empty((dx2.shape[0], woT.shape[0]), device=dev, dtype=BF16)
-                    ops.gemm_pair(a0, b0, buf, acc, dx2, woT, do, False)
-                else:
-                    do = ops.gemm(dx2, woT)
-                    ops.gemm(a0, b0, out=buf, accumulate=acc)
-                del a0, b0, woT
+            a0, b0 = _dw_operands(dx2, o)
+            woT = transposed_weight(att.o_proj.weight, sources=(att.o_proj.weight,))
+            if _pairable(a0, b0, dx2, woT):
+                do = torch.empty((dx2.shape[0], woT.shape[0]), device=dev, dtype=BF16)
+                ops.gemm_pair(a0, b0, buf, acc, dx2, woT, do, False)
             else:
-                weight_grad_gemm(dx2, o, buf, acc)
+                do = ops.gemm(dx2, woT)
+                ops.gemm(a0, b0, out=buf, accumulate=acc)
+            del a0, b0, woT
             commit_grad(att.o_proj.weight, buf)
         if do is None:
             do = input_grad_gemm(dx2, att.o_proj.weight)                        # [M, Hq*d]
@@ -495,18 +470,12 @@ class DecoderLayerFn(Function):
         if m.c2p is not None:
             dqkv = ops.rows_gather(dqkv, m.c2p)                # gradients of the compact q|k|v rows (tail rows: zeros)
         wqkv = fused_weight(qkv_params)
-        if VARIANTS["dw_tn"] and ops.gemm_nn_supported(dqkv, wqkv):
-            dn1 = ops.gemm_nn(dqkv, wqkv)
-        else:
-            dn1 = ops.gemm(dqkv, transposed_weight(wqkv, sources=qkv_params))
+        dn1 = ops.gemm(dqkv, transposed_weight(wqkv, sources=qkv_params))
         if any(p.requires_grad for p in qkv_params):
             fb, acc, bufs = fused_grad_target(qkv_params)
-            if VARIANTS["dw_tn"] or not VARIANTS["norm_t"]:
-                n1, n1T = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, m.eps), None
-            else:
-                n1, n1T = None, ops.rmsnorm_apply_t(x, layer.input_layernorm.weight, rstd1, _padded_rows(x.shape[0], long_k=True))
+            n1T = ops.rmsnorm_apply_t(x, layer.input_layernorm.weight, rstd1, _padded_rows(x.shape[0], long_k=True))
             if held is not None:
-                a1, b1 = _dw_operands(dqkv, n1, xT=n1T)
+                a1, b1 = _dw_operands(dqkv, None, xT=n1T)
                 if ops.gemm_pair_supported(held[0], held[1], a1, b1):
                     ops.gemm_pair(held[0], held[1], held[2], held[3], a1, b1, fb, bool(acc))
                 else:                                                          # e.g. an operand beyond 2 GiB
@@ -515,9 +484,9 @@ class DecoderLayerFn(Function):
                 held = None
                 del a1, b1
             else:
-                weight_grad_gemm(dqkv, n1, fb, bool(acc), xT=n1T)
+                weight_grad_gemm(dqkv, None, fb, bool(acc), xT=n1T)
             commit_fused_grad(qkv_params, fb, acc, bufs)
-            del n1, n1T
+            del n1T
         del dqkv
         dx = _rmsnorm_backward(dn1, x, layer.input_layernorm.weight, m.eps, dx2)
         if _LAYER_GRAD_HOOK is not None:                                       # every gradient of this layer is final now
@@ -995,11 +964,8 @@ def decoder_decode_row(x, layers, meta, cache, cos, sin, kv_bound=None):
         raise ValueError(f"decode bound {bound} is below the longest sequence + 1 ({cache.length + 1}); lengths change only through set_lengths")
     if B <= 16:
         y = _decode_rows16(x, layers, meta, cos, sin, cache.k, cache.v, cache.pos_dev, cache.len_dev, cache.ws, bound)
-    elif VARIANTS["decode_wide_gemm"]:
+    else:
         y = _decode_rows_gemm(x, layers, meta, cos, sin, cache.k, cache.v, cache.pos_dev, cache.len_dev, cache.ws, bound)
-    else:                                                    # (rounds 5: one pass over the weights per chunk of 16 rows)
-        y = torch.cat([_decode_rows16(x[c:c + 16], layers, meta, cos, sin, cache.k[:, c:c + 16], cache.v[:, c:c + 16], cache.pos_dev[c:c + 16],
-                                      cache.len_dev[c:c + 16], cache.ws, bound) for c in range(0, B, 16)], 0)
     cache.pos_dev.add_(1)
     cache.len_dev.add_(1)
     cache.lengths = [n + 1 for n in cache.lengths]

@@ -174,7 +174,7 @@ def gemm_splitk_rope_append(x, wqkv, Hq, Hkv, d, cos, sin, positions, k_cache, v
 def gemm_pair_supported(a0, b0, a1, b1):
     """Both problems fit mm355_gemm_pair_bf16 (plain NT operands, whole pairs of K tiles, 31-bit operand offsets)."""
     return (a0.shape[1] == b0.shape[1] and a1.shape[1] == b1.shape[1]
-            and gemm_pp_operands_ok(a0.shape[1], a0, b0, row_major=True) and gemm_pp_operands_ok(a1.shape[1], a1, b1, row_major=True))
+            and gemm_pp_operands_ok(a0.shape[1], a0, b0) and gemm_pp_operands_ok(a1.shape[1], a1, b1))
 
 
 def gemm_pair(a0, b0, out0, acc0, a1, b1, out1, acc1):
@@ -197,56 +197,10 @@ def gemm_pair(a0, b0, out0, acc0, a1, b1, out1, acc1):
     return out0, out1
 
 
-def gemm_tn(at, bt, out, accumulate=False):
-    """out[M,N] (+)= at[K,M]^T . bt[K,N]   (weight-gradient form, operands untransposed).  Raises Mm355Error(-2) when K % 64."""
-    _chk_dev(at, bt, out)
-    pa, K, M, lda = _rows2d(at)
-    pb, Kb, N, ldb = _rows2d(bt)
-    assert K == Kb and at.dtype == BF16 and bt.dtype == BF16
-    po, Mo, No, ldc = _rows2d(out)
-    assert (Mo, No) == (M, N)
-    flags = (GEMM_ACCUMULATE if accumulate else 0) | (GEMM_OUT_F32 if out.dtype == torch.float32 else 0)
-    _lib.check(_L().mm355_gemm_tn_bf16(pa, lda, pb, ldb, po, ldc, M, N, K, flags, _stream()), f"mm355_gemm_tn_bf16 M={M} N={N} K={K}")
-    return out
-
-
-def gemm_tn_supported(at, bt):
-    return at.shape[0] % 64 == 0 and at.shape[1] % 8 == 0 and bt.shape[1] % 8 == 0 and at.shape[1] >= 8 and bt.shape[1] >= 8
-
-
-def gemm_pp_operands_ok(K, *mats, row_major=False):
-    """The ping-pong 256x256 kernel wants whole pairs of 64-wide K tiles and 31-bit byte offsets: over the whole matrix for
-    contraction-major operands, over one 256-row panel for row-major ones (`row_major=True`)."""
-    span = (lambda m: 256 * m.stride(0) * 2) if row_major else (lambda m: m.shape[0] * m.stride(0) * 2)
-    return K >= 128 and K % 128 == 0 and all(span(m) < 2 ** 31 - 2 ** 20 for m in mats)
-
-
-def gemm_nn(a, bt, out=None, residual=None, accumulate=False):
-    """out[M,N] = a[M,K] . bt[K,N] (+ residual)   (input-gradient form: the weight is read as it lies in memory)."""
-    _chk_dev(a, bt, out, residual)
-    pa, M, K, lda = _rows2d(a)
-    pb, Kb, N, ldb = _rows2d(bt)
-    assert K == Kb and a.dtype == BF16 and bt.dtype == BF16
-    if out is None:
-        out = torch.empty((M, N), device=a.device, dtype=BF16)
-    po, Mo, No, ldc = _rows2d(out)
-    assert (Mo, No) == (M, N)
-    flags = (GEMM_ACCUMULATE if accumulate else 0) | (GEMM_OUT_F32 if out.dtype == torch.float32 else 0)
-    pr, ldr = 0, 0
-    if residual is not None:
-        pr, Mr, Nr, ldr = _rows2d(residual)
-        assert (Mr, Nr) == (M, N)
-        flags |= GEMM_RESIDUAL
-    _lib.check(_L().mm355_gemm_nn_bf16(pa, lda, pb, ldb, po, ldc, M, N, K, pr, ldr, flags, _stream()),
-               f"mm355_gemm_nn_bf16 M={M} N={N} K={K}")
-    return out
-
-
-def gemm_nn_supported(a, bt):
-    M, K = a.shape
-    N = bt.shape[1]
-    return (N % 8 == 0 and N >= 8 and gemm_pp_operands_ok(K, a, bt)
-            and ((M + 255) // 256) * ((N + 255) // 256) >= 128)
+def gemm_pp_operands_ok(K, *mats):
+    """The ping-pong 256x256 kernel wants whole pairs of 64-wide K tiles and 31-bit byte offsets over one 256-row panel of each
+    (row-major) operand."""
+    return K >= 128 and K % 128 == 0 and all(256 * m.stride(0) * 2 < 2 ** 31 - 2 ** 20 for m in mats)
 
 
 def gemv_supported(x, w):

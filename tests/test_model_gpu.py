@@ -414,7 +414,7 @@ def test_grad_accumulation_doubles():
             assert rel(p.grad, first[n]) < 1e-2, n
 
 
-def test_paired_weight_gradient_launch_matches_separate_launches(monkeypatch):
+def test_paired_weight_gradient_launch_matches_unpaired_run(monkeypatch):
     """DecoderLayerFn.backward sends the down_proj and qkv weight gradients out as one launch when that saves a wave of
     workgroups (LLaMA-3-8B); force that path on a tiny model (128 token rows) and compare every gradient with the unpaired run."""
     import metamorph_amd.functional as F
@@ -427,8 +427,7 @@ def test_paired_weight_gradient_launch_matches_separate_launches(monkeypatch):
     def grads(paired):
         calls = []
         orig = F.ops.gemm_pair
-        monkeypatch.setitem(F.VARIANTS, "dw_pair", paired)
-        monkeypatch.setattr(F, "_pair_saves_a_wave", lambda r0, c0, r1, c1, k: ((k + 7) // 8 * 8) % 128 == 0)
+        monkeypatch.setattr(F, "_pair_saves_a_wave", lambda r0, c0, r1, c1, k: paired and ((k + 7) // 8 * 8) % 128 == 0)
         monkeypatch.setattr(F.ops, "gemm_pair", lambda *a: (calls.append(1), orig(*a))[1])
         model = hip_model(cfg, sd)
         model.train()
