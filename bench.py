@@ -11,7 +11,8 @@ but the tower (reference stage 2), fused AdamW with ZeRO-2 sharding over RCCL.  
 backward + gradient reduce-scatter + AdamW shard update + parameter all-gather on one batch of synthetic samples;
 weights are random (no checkpoints can be downloaded), data is synthetic and resident in HBM.
 
-Prints ONE JSON line (rank 0).  `value` = total valid spliced tokens per second over all GPUs.
+Prints ONE JSON line (rank 0).  `value` = total valid spliced tokens per second over all GPUs.  A plain run does only what that
+line needs; `--full` adds what takes runs of its own after the timed steps (CPU baselines, the N-rank sync-vs-async A/B).
 """
 from __future__ import annotations
 
@@ -64,7 +65,10 @@ def parse():
                     "auto = from 8 %% padding")
     ap.add_argument("--alloc-roundup", type=int, default=0, metavar="DIV", help="experiment: torch caching allocator roundup_power2_divisions (sizes that "
                     "change from step to step under --compact-rows exact then fall into few block classes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need, after its timed steps: the CPU "
+                    "baselines (cpu_baseline, cpu_baseline_c1) and, at world > 1, the same-job sync-vs-async A/B.  Without it a run sets up, "
+                    "warms up, times its steps, writes --dump-outputs and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the LAST timed step handed back "
                     "(losses, gradient norm, fixed seeded samples of the returned hidden states, of the gradients and of the updated "
@@ -766,9 +770,10 @@ def main():
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         params_equal = bool(torch.equal(lo, hi))
         # same-job A/B of the asynchronous update / all-gather (hidden behind the next forward pass) against the synchronous one:
-        # 3 steps each AFTER the headline measurement (the timed region and the record above are closed; default at world > 1, where it
-        # is the only way to see the overlap on a node this build never runs on; MM355_BENCH_AB_ASYNC=1 forces it on one rank)
-        if args.zero == 2 and (world > 1 or os.environ.get("MM355_BENCH_AB_ASYNC", "0") == "1"):
+        # 3 steps each AFTER the headline measurement (the timed region and the record above are closed; with --full, by default at
+        # world > 1, where it is the only way to see the overlap on a node this build never runs on; MM355_BENCH_AB_ASYNC=1 forces it
+        # on one rank)
+        if args.full and args.zero == 2 and (world > 1 or os.environ.get("MM355_BENCH_AB_ASYNC", "0") == "1"):
             ab_async = {}
             for tag, on in (("sync_ms_per_step", False), ("async_ms_per_step", True)):
                 opt.set_async_update(on)
@@ -899,7 +904,7 @@ def main():
             rec["rccl"]["bus_bandwidth"] = bus_bandwidth(rec["rccl"], comm, world, bool(args.zero2_overlap) and getattr(opt, "overlap", True))
             if ab_async:
                 rec["zero2_async_ab"] = ab_async
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(args)
             rec["cpu_baseline_c1"] = cpu_baseline_c1()
         print(json.dumps(rec), flush=True)

@@ -1078,6 +1078,16 @@ def test_bench_refuses_zero_timed_steps(monkeypatch):
         b.parse()
 
 
+def test_bench_full_is_opt_in(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` leaves out what its line does not need; `--full` asks for it."""
+    b = _bench_module()
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = b.parse()
+    assert a.full is False and a.no_cpu_baseline is False
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2", "--full"])
+    assert b.parse().full is True
+
+
 def test_bench_dump_outputs_is_a_fixed_sample_within_the_size_limit(tmp_path):
     """bench.dump_outputs on stand-in objects: float32 / float64 .npy files, the same positions on every call, parameters and gradients
     sampled at the same positions, small tensors whole, at most 64 MB in all."""

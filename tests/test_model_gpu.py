@@ -968,15 +968,15 @@ def test_forward_with_host_mirrors_does_not_touch_the_device_for_its_plan():
 
 
 def test_bench_emits_the_driver_contract_on_device():
-    """`python bench.py --layers 2 --vit-layers 2 --steps 2 --warmup 1 --batch 2` really runs (a 2-layer debug geometry, NOT the headline
-    config) and its ONE stdout line carries the driver's contract: the required keys, value = tokens of the timed steps / their wall time,
-    `roofline` over ALL GEMM launches with the plain / fused split and the HBM-bound block, `cpu_baseline` with cores and sample."""
+    """`python bench.py --layers 2 --vit-layers 2 --steps 2 --warmup 1 --batch 2 --full` really runs (a 2-layer debug geometry, NOT the
+    headline config) and its ONE stdout line carries the driver's contract: the required keys, value = tokens of the timed steps / their
+    wall time, `roofline` over ALL GEMM launches with the plain / fused split and the HBM-bound block, `cpu_baseline` with cores and sample."""
     import json
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--layers", "2", "--vit-layers", "2", "--steps", "2", "--warmup", "1", "--batch", "2"],
-                       capture_output=True, text=True, timeout=900, cwd=repo)
+    p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--layers", "2", "--vit-layers", "2", "--steps", "2", "--warmup", "1", "--batch", "2",
+                        "--full"], capture_output=True, text=True, timeout=900, cwd=repo)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -1001,19 +1001,21 @@ def test_bench_emits_the_driver_contract_on_device():
 
 def test_bench_dumps_what_its_last_timed_step_computed(tmp_path):
     """`bench.py ... --steps 3 --dump-outputs DIR` times exactly 3 steps and writes the last one's results: the loss of the JSON line, the
-    loss terms, finite hidden-state / parameter / master-weight samples and non-zero gradients, float32 / float64, at most 64 MB."""
+    loss terms, finite hidden-state / parameter / master-weight samples and non-zero gradients, float32 / float64, at most 64 MB.  Without
+    `--full` the run measures nothing after its timed steps: no CPU baseline in its line."""
     import json
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     d = tmp_path / "dump"
     p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--layers", "2", "--vit-layers", "2", "--steps", "3", "--warmup", "1", "--batch", "2",
-                        "--no-cpu-baseline", "--no-kernel-timing", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900, cwd=repo)
+                        "--no-kernel-timing", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900, cwd=repo)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
     r = json.loads(lines[0])
     assert r["steps"] == 3 and r["ms_per_step"] > 0
+    assert "cpu_baseline" not in r and "cpu_baseline_c1" not in r
     names = {"loss", "loss_language", "loss_image_ar", "grad_norm", "hidden_states", "params", "grads", "master_weights"}
     assert set(r["dumped_outputs"]) == names and sorted(os.listdir(d)) == sorted(n + ".npy" for n in names)
     a = {n: np.load(d / f"{n}.npy") for n in names}

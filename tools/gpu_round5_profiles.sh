@@ -12,7 +12,7 @@ tests)
   (time timeout 1500 python -m pytest tests -m gpu -q --durations=12) > $OUT/gpu_tests.log 2>&1; echo "rc=$?" >> $OUT/gpu_tests.log
   (timeout 600 python -m pytest tests/test_attn_hostile_gpu.py -m gpu -q -s) > $OUT/attn_hostile_tests.log 2>&1; echo "rc=$?" >> $OUT/attn_hostile_tests.log ;;
 bench)
-  timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "rc=$?" >> $OUT/bench_default.err
+  timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "rc=$?" >> $OUT/bench_default.err
   (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/step -o step -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $R/$OUT/bench_profiled.json 2> $R/$OUT/bench_profiled.err)
   find $OUT/step -name "*kernel_stats.csv" -exec cp {} $OUT/step_b16_kernel_stats.csv \; ;;
 decode)
