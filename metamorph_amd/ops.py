@@ -464,17 +464,21 @@ def gemm_rope(x, wqkv, B, L, Hq, Hkv, d, cos, sin, pos_offset=None):
     return qkv
 
 
-def attn_fwd(q2d, k2d, v2d, B, L, Hq, Hkv, d, scale, causal, seqlens=None, out=None, variant=0):
+def attn_fwd(q2d, k2d, v2d, B, L, Hq, Hkv, d, scale, causal, seqlens=None, out=None, variant=0, lse=None):
     """q2d/k2d/v2d: [B*L, ld] views starting at the q / k / v column blocks (k and v share the leading dimension).
+    out / lse: optional destinations ([B*L, >= Hq*d] bf16 view, contiguous [B, Hq, L] fp32).
     variant != 0 (tests / tools only) picks the kernel generation: mm355_attn_fwd_variant in include/mm355.h."""
-    _chk_dev(q2d, k2d, v2d)
+    _chk_dev(q2d, k2d, v2d, out, lse)
     pq, M, _, ldq = _rows2d(q2d)
     pk, _, _, ldk = _rows2d(k2d)
     pv, _, _, ldv = _rows2d(v2d)
     assert ldv == ldk and M == B * L
     if out is None:
         out = torch.empty((M, Hq * d), device=q2d.device, dtype=BF16)
-    lse = torch.empty((B, Hq, L), device=q2d.device, dtype=torch.float32)
+    if lse is None:
+        lse = torch.empty((B, Hq, L), device=q2d.device, dtype=torch.float32)
+    else:
+        assert lse.shape == (B, Hq, L) and lse.dtype == torch.float32 and lse.is_contiguous()
     if variant:
         _lib.check(_L().mm355_attn_fwd_variant(pq, pk, pv, ldq, ldk, out.data_ptr(), out.stride(0), lse.data_ptr(), _p(seqlens),
                                                B, L, Hq, Hkv, d, scale, int(causal), int(variant), _stream()), "mm355_attn_fwd_variant")

@@ -149,33 +149,72 @@ def fp32_scores(q, k, b, hq, hk, scale):
 
 # ------------------------------------------------------------------------------------------------ adversarial inputs
 
-def _base(B, L, Hq, Hkv, seed, sigma):
+def _base(B, L, Hq, Hkv, seed, sigma, d=D):
     g = torch.Generator().manual_seed(seed)
-    q = (torch.randn(B, L, Hq, D, generator=g) * sigma).to(torch.bfloat16)
-    k = (torch.randn(B, L, Hkv, D, generator=g) * sigma).to(torch.bfloat16)
-    v = torch.randn(B, L, Hkv, D, generator=g).to(torch.bfloat16)
+    q = (torch.randn(B, L, Hq, d, generator=g) * sigma).to(torch.bfloat16)
+    k = (torch.randn(B, L, Hkv, d, generator=g) * sigma).to(torch.bfloat16)
+    v = torch.randn(B, L, Hkv, d, generator=g).to(torch.bfloat16)
     return q, k, v
 
 
-def hostile_inputs(kind, B, L, Hq, Hkv, seed=0):
-    """-> q [B, L, Hq, 128], k, v [B, L, Hkv, 128] bf16 whose scaled scores (scale = 128^-1/2) follow the named adversarial pattern.
-    The structured part of a score rides on ONE coordinate: q[..., c] = A, k[..., c] = g(key) -> s += scale * A * g(key)."""
-    scale = D ** -0.5
+def _split3(x):
+    """fp32 x -> three bf16 values whose exact sum is x, every partial sum exact in fp32 (a score that is the same fp32 number in any
+    summation order: three unit q coordinates against these three k coordinates)"""
+    k0 = x.to(torch.bfloat16).float()
+    r = x - k0
+    k1 = r.to(torch.bfloat16).float()
+    k2 = r - k1
+    assert float(k2.to(torch.bfloat16).float()) == float(k2) and float(k0) + float(k1) + float(k2) == float(x)
+    return float(k0), float(k1), float(k2)
+
+
+def threshold_scores(d):
+    """Raw scores (s0 at key 0, s1 at keys 70, 134, ...) of the three `threshold` samples at head size d != 128, for the generic kernels'
+    decision rule (attn2::fwd_kernel): a wave rescales when fp32(max s * c) > m + 6, with m = fp32(s0 * c) set by tile 0.  No bf16 pair
+    q0 * k0 lands exactly on 6 for any d in {16 .. 120} (fp32(q0 k0 c) skips it), so s1 is an exact three-term sum with fp32(s1 * c) = x
+    just above 6, and s0 places the threshold m + 6 one fp32 step above x (sample 0), exactly on x (sample 1) and one step below x
+    (sample 2): only sample 2 takes the branch.  -> [(s0, s1)] * 3, fp32 scalars."""
+    c = sl2_of(d ** -0.5)
+    six = f32(6.0)
+    up, down = f32(math.inf), f32(-math.inf)
+    s1 = six / c
+    while bool(s1 * c < torch.nextafter(torch.nextafter(six, up), up)):
+        s1 = torch.nextafter(s1, up)
+    x = s1 * c
+    out = []
+    for T in (torch.nextafter(x, up), x, torch.nextafter(x, down)):
+        s0 = (T - six) / c
+        for _ in range(64):                                       # m's grid is ~10^7 x finer than T's: a step or two at most
+            t = s0 * c + six
+            if bool(t == T):
+                break
+            s0 = torch.nextafter(s0, up if bool(t < T) else down)
+        assert bool(s0 * c + six == T) and bool(s0 > 0)
+        out.append((s0, s1))
+    return out
+
+
+def hostile_inputs(kind, B, L, Hq, Hkv, seed=0, d=D, wave_rows=None):
+    """-> q [B, L, Hq, d], k, v [B, L, Hkv, d] bf16 whose scaled scores (scale = d^-1/2) follow the named adversarial pattern.
+    The structured part of a score rides on ONE coordinate: q[..., c] = A, k[..., c] = g(key) -> s += scale * A * g(key).
+    wave_rows = query rows that share one rescale decision: 64 in the d == 128 stream (the default there), 16 in the generic kernels."""
+    scale = d ** -0.5
     A = 8.0
     unit = scale * A                                             # natural-log score units per unit of k[..., c]
+    W = wave_rows or (64 if d == D else 16)
     if kind == "rising":
         # every 64-key tile raises every row's maximum by 8 / unit * unit * log2 e = 8.16 log2 units: the branch fires at EVERY tile
-        q, k, v = _base(B, L, Hq, Hkv, seed, 0.5)
+        q, k, v = _base(B, L, Hq, Hkv, seed, 0.5, d)
         q[..., 0] = A
         tile = torch.arange(L) // 64
-        k[..., 0] = (8.0 * tile.float())[None, :, None].to(torch.bfloat16)
+        k[..., 0] = (8.0 * (D ** -0.5 / scale) * tile.float())[None, :, None].to(torch.bfloat16)
         return q, k, v
     if kind == "one_row":
-        # benign scores, except ONE query row per 64-row wave (row 17) that meets keys carrying +12 log2 units from key tile 3 on: the
+        # benign scores, except ONE query row per W-row wave (row 17 mod W) that meets keys carrying +12 log2 units from key tile 3 on: the
         # wave-wide branch fires because of a single row; every other row of the wave gets its own (tiny, or exactly 1) factor
-        q, k, v = _base(B, L, Hq, Hkv, seed, 0.5)
+        q, k, v = _base(B, L, Hq, Hkv, seed, 0.5, d)
         q[..., 1] = 0
-        q[:, 17::64, :, 1] = A
+        q[:, 17 % W::W, :, 1] = A
         k[..., 1] = 0
         late = torch.zeros(L)
         late[200::37] = 12.0 / (unit * LOG2E)
@@ -184,7 +223,7 @@ def hostile_inputs(kind, B, L, Hq, Hkv, seed=0):
     if kind == "sink":
         # attention sink: key 0 at +30 for every row, the rest N(0, 4): the first tile's maximum is never exceeded (stale maximum 43 log2
         # units above everything that follows: P down to 2^-60), except for rows that meet a second sink at key 300 (+45): one big rescale
-        q, k, v = _base(B, L, Hq, Hkv, seed, 2.0)
+        q, k, v = _base(B, L, Hq, Hkv, seed, 2.0, d)
         q[..., 0] = A
         k[..., 0] = 0
         k[:, 0, :, :] = 0
@@ -196,7 +235,7 @@ def hostile_inputs(kind, B, L, Hq, Hkv, seed=0):
     if kind == "cliff":
         # every score -40 except one key at +40 late in the sequence: the running maximum jumps by 115 log2 units (factor 2^-115 on O and l);
         # a second cliff of +110 later: the factor exp2(-101 log2 e ...) underflows fp32 to ZERO, O and l restart from the new tile alone
-        q, k, v = _base(B, L, Hq, Hkv, seed, 0.25)
+        q, k, v = _base(B, L, Hq, Hkv, seed, 0.25, d)
         q[..., 0] = A
         k[..., 0] = -40.0 / unit
         k[:, (L * 5) // 8, :, 0] = 40.0 / unit
@@ -207,20 +246,27 @@ def hostile_inputs(kind, B, L, Hq, Hkv, seed=0):
         # samples 0 / 1 / 2: ONE non-zero coordinate (q0, k0), every other zero, so s' = q0 * k0 is exact in fp32 (bf16 x bf16): 47.05078
         # (threshold - 0.0016), 47.0 and 47.0625 (threshold + 0.0101).  The condition is "growth > threshold": only sample 2 takes the branch;
         # samples 0 / 1 carry P = 2^5.9998 / 2^5.9933 against the stale maximum
+        # (d != 128: the generic kernels' rule "fp32(s * c) > m + 6" at its exact boundary, threshold_scores)
         assert B == 3
-        q = torch.zeros(B, L, Hq, D, dtype=torch.bfloat16)
-        k = torch.zeros(B, L, Hkv, D, dtype=torch.bfloat16)
+        q = torch.zeros(B, L, Hq, d, dtype=torch.bfloat16)
+        k = torch.zeros(B, L, Hkv, d, dtype=torch.bfloat16)
         g = torch.Generator().manual_seed(seed)
-        v = torch.randn(B, L, Hkv, D, generator=g).to(torch.bfloat16)
+        v = torch.randn(B, L, Hkv, d, generator=g).to(torch.bfloat16)
+        if d != D:
+            q[..., :3] = 1.0
+            for b, (s0, s1) in enumerate(threshold_scores(d)):
+                k[b, 0, :, :3] = torch.tensor(_split3(s0))
+                k[b, 70::64, :, :3] = torch.tensor(_split3(s1))
+            return q, k, v
         for b, (q0, k0) in enumerate(((1.140625, 41.25), (1.0, 47.0), (1.5, 31.375))):
             q[b, :, :, 0] = q0
             k[b, 70::64, :, 0] = k0                               # one such key in every tile from tile 1 on: growth happens once, at tile 1
         return q, k, v
     if kind == "benign":
-        return _base(B, L, Hq, Hkv, seed, 0.7)
+        return _base(B, L, Hq, Hkv, seed, 0.7, d)
     if kind == "wide":
         # trained-checkpoint-like: scores N(0, 9^2) (|s| to ~ 45 over a 2048 x 2048 head) with a few retrieval keys at +35 on top
-        q, k, v = _base(B, L, Hq, Hkv, seed, 3.0)
+        q, k, v = _base(B, L, Hq, Hkv, seed, 3.0, d)
         g = torch.Generator().manual_seed(seed + 7)
         q[..., 3] = A
         k[..., 3] = 0
