@@ -350,6 +350,36 @@ int mm355_attn_decode_variant(const mm355_bf16* q, int64_t ld_q, const mm355_bf1
                       float* workspace, int variant, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The decode GEMVs over weight-only FP8 (the reference serves its LLM in 8 bits through bitsandbytes: metamorph/model/builder.py:13-25,
+ * load_pretrained_model(..., load_8bit=True); this is a scheme of its own, not LLM.int8).  fmt MM355_W8_E4M3: W[N][K] stored as OCP e4m3fn
+ * bytes Wq[N][K] (the gfx950 encoding, not fnuz; row stride ldw_bytes), plus scale[N] fp32; dequantised value fp32(Wq[n][k]) * scale[n].
+ *   gemv_w8: y[m][n] = epilogue(scale[n] * sum_k fp32(Wq[n][k]) * fp32(x[m][k])), x bf16, fp32 accumulation, the scale applied once, after
+ *         the sum; flags and epilogue as mm355_gemv_bf16.  M <= 16 rows (more: MM355_EUNSUPPORTED -- mm355_dequant_w8_bf16 + the GEMM).  Up to
+ *         four rows on the vector ALU (v_cvt_pk_f32_fp8 + v_perm_b32 widen a pair of weights to packed bf16 for v_dot2c_f32_bf16), 5 .. 16 on
+ *         v_mfma_f32_16x16x32_bf16 with the bytes widened in registers; x rows parked in LDS windows, a register ring of weight loads.
+ *         fmt other than MM355_W8_E4M3, K % 16 != 0, ldw_bytes % 16 != 0, a NULL scale or misaligned pointers: MM355_EINVAL before any
+ *         launch.  32-bit byte offsets: N * ldw_bytes < 3.75 GiB, else MM355_EUNSUPPORTED.
+ *   gemv_swiglu_w8 / gemv_rope_append_w8: the twins of mm355_gemv_swiglu_bf16 / mm355_gemv_rope_append_bf16 (same row limits, same
+ *         MM355_EUNSUPPORTED cases: odd I, d % 4 != 0, norm_w with 5 .. 16 rows beyond 140 KiB of rows): the bits of mm355_gemv_w8 +
+ *         mm355_swiglu_fwd, of mm355_gemv_w8 + mm355_rope_kv_append, and with norm_w of mm355_rmsnorm_fwd in front.
+ *   dequant_w8_bf16: out[n][k] = bf16(fp32(Wq[n][k]) * scale[n]) (RNE), a plain streaming kernel: the prompt pass and batches over 16 rows
+ *         run the bf16 GEMMs on one layer's weights dequantised into a scratch buffer.  ld_out % 8 == 0, out 16-byte aligned.
+ * ------------------------------------------------------------------------------------------------ */
+#define MM355_W8_E4M3 1
+int mm355_gemv_w8(const mm355_bf16* x, int64_t ldx, const uint8_t* Wq, int64_t ldw_bytes, const float* scale, int fmt, void* y, int64_t ldy,
+                  int64_t M, int64_t N, int64_t K, const mm355_bf16* bias, const mm355_bf16* residual, int64_t ldr,
+                  uint32_t flags, void* stream);
+int mm355_gemv_swiglu_w8(const mm355_bf16* x, int64_t ldx, const uint8_t* Wq, int64_t ldw_bytes, const float* scale, int fmt,
+                         mm355_bf16* act, int64_t ld_act, int64_t M, int64_t I, int64_t K, const mm355_bf16* norm_w, float eps, void* stream);
+int mm355_gemv_rope_append_w8(const mm355_bf16* x, int64_t ldx, const uint8_t* Wq, int64_t ldw_bytes, const float* scale, int fmt,
+                              mm355_bf16* qkv, int64_t ld_qkv, int64_t M, int64_t Hq, int64_t Hkv, int64_t d, int64_t K,
+                              const mm355_bf16* norm_w, float eps, const mm355_bf16* cos_t, const mm355_bf16* sin_t,
+                              const int32_t* positions, mm355_bf16* k_cache, mm355_bf16* v_cache, int64_t ld_kv,
+                              int64_t batch_stride_kv, void* stream);
+int mm355_dequant_w8_bf16(const uint8_t* Wq, int64_t ldw_bytes, const float* scale, int fmt, mm355_bf16* out, int64_t ld_out,
+                          int64_t N, int64_t K, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Elementwise: SwiGLU (HF LlamaMLP; K12), GELU (projector / vision_head), scaling helpers.
  * gu = [M][2I] with gate in columns [0,I) and up in [I,2I).
  * ------------------------------------------------------------------------------------------------ */

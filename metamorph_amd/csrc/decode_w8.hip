@@ -1,0 +1,653 @@
+// Decode GEMVs over weight-only FP8 (gfx950): W[N][K] stored as OCP e4m3fn bytes Q[N][K] plus one fp32 scale per output row,
+// dequantised value fp32(Q[n][k]) * scale[n].  Cached decode is bound by the bytes of the weights and by nothing else; this halves them
+// (the capability the reference reaches through bitsandbytes: metamorph/model/builder.py:13-25, load_8bit=True).
+//   y[m][n] = epilogue(scale[n] * sum_k fp32(Q[n][k]) * fp32(x[m][k]))       x bf16, fp32 accumulation, the scale ONCE, after the sum
+// Every product bf16 x e4m3 is exact in fp32, so only the summation order separates these kernels from an exact evaluation.
+// The structure is that of decode.hip's round-5 kernels (gemv_deep_kernel / gemv_mfma_kernel), with 16 weights per 16-byte load:
+//   * the x rows (PRENORM: bf16(w * bf16(x * rstd)), rmsnorm_fwd_kernel's arithmetic and reduction order) are parked in LDS windows, so
+//     that once the stream runs only weight loads sit in the in-order vector-memory queue;
+//   * a register ring of weight trips; lanes behind the end of a row carry the out-of-range mark of the buffer descriptor (zeros, no
+//     memory access, no branch around a prefetch);
+//   * e4m3 -> fp32 is exact and its upper 16 bits ARE the bf16 value: v_cvt_pk_f32_fp8 + one v_perm_b32 per pair of weights gives the
+//     packed bf16 pair that v_dot2c_f32_bf16 (up to four rows) and v_mfma_f32_16x16x32_bf16 (5 .. 16 rows) take.  x stays bf16.
+//   * the epilogues (bias / GELU / residual; SiLU(g) u; RoPE + cache append) are those of decode.hip, applied to scale[n] * sum; a fused
+//     form and the launch sequence it replaces run the same stream in the same order: the same bits.
+#include "mm355_common.h"
+
+namespace {
+
+constexpr int NT = 256;
+constexpr uint32_t OOB = 0xf0000000u;                        // or-ed into a buffer offset: beyond num_records, the load returns zeros
+
+struct W8Args {
+    const uint16_t* x; int64_t ldx;
+    const uint8_t* W; int64_t ldw;                           // bytes
+    const float* scale;
+    int M, N, K;                                             // N = weight rows
+    const uint16_t* norm_w; float eps;                       // PRENORM
+    void* y; int64_t ldy;                                    // MODE 0
+    const uint16_t* bias; const uint16_t* res; int64_t ldr; uint32_t flags;
+    uint16_t* out; int64_t ld_out;                           // MODE 1: act [M][I]; MODE 2: qkv row buffer [M][N]
+    int I;                                                   // MODE 1
+    int Hq, Hkv, d;                                          // MODE 2
+    const uint16_t* cos_t; const uint16_t* sin_t; const int32_t* positions;
+    uint16_t* kc; uint16_t* vc; int64_t ld_kv, bs_kv;
+    int ks;                                                  // MFMA form: waves that share one group of 16 weight rows (1, 4)
+};
+
+// the four weight rows of a unit (decode.hip: unit_rows): plain = 4u .. 4u+3; SwiGLU = gate rows c, c+1 and up rows I+c, I+c+1; RoPE = the
+// rotation partners j, j+1, j+d/2, j+1+d/2 of one head (v rows: four neighbours)
+template <int MODE>
+MM_DEV void unit_rows(const W8Args& a, int unit, int (&rows)[4]) {
+    if constexpr (MODE == 0) {
+        rows[0] = unit * 4; rows[1] = rows[0] + 1; rows[2] = rows[0] + 2; rows[3] = rows[0] + 3;
+    } else if constexpr (MODE == 1) {
+        const int c = unit * 2;
+        rows[0] = c; rows[1] = c + 1; rows[2] = a.I + c; rows[3] = a.I + c + 1;
+    } else {
+        const int upd = a.d / 4, nrot = (a.Hq + a.Hkv) * upd;
+        if (unit < nrot) {
+            const int hd = unit / upd, j = (unit % upd) * 2;
+            rows[0] = hd * a.d + j; rows[1] = rows[0] + 1; rows[2] = rows[0] + a.d / 2; rows[3] = rows[2] + 1;
+        } else {
+            const int b0 = (a.Hq + a.Hkv) * a.d + (unit - nrot) * 4;
+            rows[0] = b0; rows[1] = b0 + 1; rows[2] = b0 + 2; rows[3] = b0 + 3;
+        }
+    }
+}
+template <int MODE>
+MM_DEV bool unit_live(const W8Args& a, const int (&rows)[4]) {
+    if constexpr (MODE == 0) return rows[0] < a.N;
+    else if constexpr (MODE == 1) return rows[1] < a.I;
+    else return rows[3] < a.N;
+}
+
+// four e4m3 bytes (k .. k+3) -> the packed bf16 pairs (k, k+1) and (k+2, k+3): exact
+MM_DEV void e4m3x4_to_bf16(uint32_t q, uint32_t& p01, uint32_t& p23) {
+    const mm_f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)q, false);
+    const mm_f32x2 b = __builtin_amdgcn_cvt_pk_f32_fp8((int)q, true);
+    p01 = __builtin_amdgcn_perm(__float_as_uint(a.y), __float_as_uint(a.x), 0x07060302u);
+    p23 = __builtin_amdgcn_perm(__float_as_uint(b.y), __float_as_uint(b.x), 0x07060302u);
+}
+
+// MODE 0: output (m, n) of the scaled sum v -- gemv_kernel's epilogue
+MM_DEV void plain_store(const W8Args& a, int m, int n, float v) {
+    const uint32_t flags = a.flags;
+    if (flags & MM355_GEMM_BIAS) v += bf2f(a.bias[n]);
+    if (flags & MM355_GEMM_GELU_ERF) v = gelu_erf_f(v);
+    if (flags & MM355_GEMM_GELU_TANH) v = gelu_tanh_f(v);
+    if (flags & MM355_GEMM_RESIDUAL) v += bf2f(a.res[(int64_t)m * a.ldr + n]);
+    if (flags & MM355_GEMM_OUT_F32) ((float*)a.y)[(int64_t)m * a.ldy + n] = v;
+    else ((uint16_t*)a.y)[(int64_t)m * a.ldy + n] = f2bf(v);
+}
+
+// MODE 1 / 2: the four outputs of one unit for x row m, already rounded to bf16 (what the unfused GEMV stores): swiglu_fwd_kernel's /
+// rope_kv_append_kernel's arithmetic, as in gemv_deep_kernel
+template <int MODE>
+MM_DEV void fused_store(const W8Args& a, const int (&rows)[4], int m, const float (&v4)[4]) {
+    if constexpr (MODE == 1) {
+        float o[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) o[e] = round_bf(v4[e] / (1.0f + __expf(-v4[e]))) * v4[2 + e];
+        *(uint32_t*)(a.out + (int64_t)m * a.ld_out + rows[0]) = pack2bf(o[0], o[1]);
+    } else {
+        const int nqk = (a.Hq + a.Hkv) * a.d;
+        const int pos = a.positions[m];
+        if (rows[0] < nqk) {
+            const int hd = rows[0] / a.d, j = rows[0] % a.d;
+            float y1[2], y2[2];
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const float c = bf2f(a.cos_t[(int64_t)pos * a.d + j + e]), sn = bf2f(a.sin_t[(int64_t)pos * a.d + j + e]);
+                y1[e] = round_bf(v4[e] * c) + round_bf(-v4[2 + e] * sn);
+                y2[e] = round_bf(v4[2 + e] * c) + round_bf(v4[e] * sn);
+            }
+            uint16_t* dst = hd < a.Hq ? a.out + (int64_t)m * a.ld_out + rows[0]
+                                      : a.kc + (int64_t)m * a.bs_kv + (int64_t)pos * a.ld_kv + (int64_t)(hd - a.Hq) * a.d + j;
+            *(uint32_t*)dst = pack2bf(y1[0], y1[1]);
+            *(uint32_t*)(dst + a.d / 2) = pack2bf(y2[0], y2[1]);
+        } else {
+            uint16_t* dst = a.vc + (int64_t)m * a.bs_kv + (int64_t)pos * a.ld_kv + (rows[0] - nqk);
+            *(u32x2*)dst = u32x2{pack2bf(v4[0], v4[1]), pack2bf(v4[2], v4[3])};
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ up to four rows: the vector ALU
+// A wave owns one unit (four weight rows) over the whole K.  A trip = 2048 columns x 4 rows = eight 16-byte loads per lane; NB trips ride in
+// the register ring.  The x rows pass through LDS in windows of WK columns (two buffers when a row is longer than one window).  Every
+// weight dword is widened once (two conversions, two permutes) and feeds MR dot2 chains.
+template <int MR, int MODE, bool PRENORM>
+__global__ __launch_bounds__(NT) void gemv_w8_valu_kernel(W8Args a) {
+    constexpr int R = 4, NB = 2;
+    constexpr int WK = MR == 4 ? 4096 : 8192;                // columns per x window
+    constexpr int WT = WK / 2048;                            // trips per window
+    constexpr int XV = WK / 8 / NT;                          // 16-byte x vectors per thread, row and window
+    static_assert(WT % NB == 0, "the ring position of a trip must not depend on the window");
+    extern __shared__ __attribute__((aligned(16))) unsigned char xs[];          // [1 or 2 windows][MR][wk] bf16
+    __shared__ float red[MR][NT / 64];
+    __shared__ float rstd_s[MR];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int unit = blockIdx.x * (NT / 64) + wave;
+    const int K = a.K, M = a.M;
+    const int ntrip = (K + 2047) >> 11, nwin = (ntrip + WT - 1) / WT, nv = K >> 3;
+    const int wk = min(ntrip, WT) << 11;                     // elements per window row in LDS
+    int rows[R];
+    unit_rows<MODE>(a, unit, rows);
+    const bool live = unit_live<MODE>(a, rows);
+    const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)a.W, 0, (uint32_t)((uint64_t)(a.N - 1) * a.ldw + (uint64_t)K), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, (uint32_t)((uint64_t)(M - 1) * a.ldx * 2 + (uint64_t)K * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsN = __builtin_amdgcn_make_buffer_rsrc((void*)(PRENORM ? a.norm_w : a.x), 0, (uint32_t)K * 2u, 0x00020000);
+    uint32_t wo[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) wo[r] = (uint32_t)min(rows[r], a.N - 1) * (uint32_t)a.ldw;
+    u32x4 xr[MR][XV], nr[XV];
+    auto stage_load = [&](int w) {                           // this thread's vectors v = t + 256 i of window w; beyond K: zeros, no access
+#pragma unroll
+        for (int i = 0; i < XV; ++i) {
+            const int v = w * (WK / 8) + threadIdx.x + NT * i;
+            const uint32_t sk = v < nv ? 0u : OOB;
+#pragma unroll
+            for (int m = 0; m < MR; ++m)
+                xr[m][i] = __builtin_amdgcn_raw_buffer_load_b128(rsX, ((uint32_t)min(m, M - 1) * (uint32_t)a.ldx * 2u + (uint32_t)v * 16u) | sk, 0, 0);
+            if constexpr (PRENORM) nr[i] = __builtin_amdgcn_raw_buffer_load_b128(rsN, ((uint32_t)v * 16u) | sk, 0, 0);
+        }
+    };
+    auto stage_store = [&](int w) {                          // -> LDS window buffer w & 1
+        unsigned char* dst = xs + (size_t)(w & 1) * MR * wk * 2;
+#pragma unroll
+        for (int i = 0; i < XV; ++i) {
+            const int v = threadIdx.x + NT * i;
+            if (v * 8 < wk) {
+#pragma unroll
+                for (int m = 0; m < MR; ++m) {
+                    u32x4 out = xr[m][i];
+                    if constexpr (PRENORM) {
+                        float xv[8], nw[8];
+                        unpack8(xr[m][i], xv);
+                        unpack8(nr[i], nw);
+                        const float rs = rstd_s[m];
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) xv[e] = nw[e] * round_bf(xv[e] * rs);
+                        out = pack8(xv);
+                    }
+                    *(u32x4*)(dst + ((size_t)m * wk + v * 8) * 2) = out;
+                }
+            }
+        }
+    };
+    auto issue = [&](u32x4 (&w)[2][R], int t) {
+#pragma unroll
+        for (int ch = 0; ch < 2; ++ch) {
+            const int k = (t * 2 + ch) * 1024 + lane * 16;
+            const uint32_t sk = (live && k < K) ? 0u : OOB;
+#pragma unroll
+            for (int r = 0; r < R; ++r) w[ch][r] = __builtin_amdgcn_raw_buffer_load_b128(rsW, (wo[r] + (uint32_t)k) | sk, 0, 2);
+        }
+    };
+    // rmsnorm_fwd_kernel's reduction (thread t sums elements 8 (t + 256 i) .. + 7 in order, block_sum<256>), all rows in one pass
+    auto finish_norm = [&](float (&ss)[MR]) {
+#pragma unroll
+        for (int m = 0; m < MR; ++m) {
+            const float w = wave_sum(ss[m]);
+            if (lane == 0) red[m][wave] = w;
+        }
+        __syncthreads();
+        if (threadIdx.x < MR) {
+            float t = 0.f;
+#pragma unroll
+            for (int i = 0; i < NT / 64; ++i) t += red[threadIdx.x][i];
+            rstd_s[threadIdx.x] = rsqrtf(t / (float)K + a.eps);
+        }
+        __syncthreads();
+    };
+    // ---- the first NB trips of the weight stream, then the x rows behind them (they are needed together)
+    u32x4 wb[NB][2][R];
+#pragma unroll
+    for (int j = 0; j < NB; ++j) issue(wb[j], j);
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (PRENORM) {
+        if (nwin > 1) {                                      // rows longer than a window: their sums of squares first (x from L2, read again below)
+            float ss[MR];
+#pragma unroll
+            for (int m = 0; m < MR; ++m) ss[m] = 0.f;
+            for (int v = threadIdx.x; v < nv; v += NT) {
+#pragma unroll
+                for (int m = 0; m < MR; ++m) {
+                    float xv[8];
+                    unpack8(*(const u32x4*)(a.x + (int64_t)min(m, M - 1) * a.ldx + v * 8), xv);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) ss[m] += xv[e] * xv[e];
+                }
+            }
+            finish_norm(ss);
+        }
+    }
+    stage_load(0);
+    if constexpr (PRENORM) {
+        if (nwin == 1) {
+            float ss[MR];
+#pragma unroll
+            for (int m = 0; m < MR; ++m) {
+                ss[m] = 0.f;
+#pragma unroll
+                for (int i = 0; i < XV; ++i) {
+                    float xv[8];
+                    unpack8(xr[m][i], xv);                   // (beyond K: zeros)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) ss[m] += xv[e] * xv[e];
+                }
+            }
+            finish_norm(ss);
+        }
+    }
+    stage_store(0);
+    __syncthreads();
+    // ---- the stream
+    float acc[MR][R];
+#pragma unroll
+    for (int m = 0; m < MR; ++m)
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[m][r] = 0.f;
+    auto consume = [&](const u32x4 (&w)[2][R], int win, int j) {          // trip j of window win
+        const unsigned char* src = xs + (size_t)(win & 1) * MR * wk * 2;
+#pragma unroll
+        for (int ch = 0; ch < 2; ++ch) {
+            const int k = min((j * 2 + ch) * 1024, wk - 1024) + lane * 16;     // (a trip behind the end is all zeros: any staged x will do)
+            uint32_t xv[MR][8];
+#pragma unroll
+            for (int m = 0; m < MR; ++m) {
+                const u32x4 x0 = *(const u32x4*)(src + ((size_t)m * wk + k) * 2), x1 = *(const u32x4*)(src + ((size_t)m * wk + k) * 2 + 16);
+                xv[m][0] = x0.x; xv[m][1] = x0.y; xv[m][2] = x0.z; xv[m][3] = x0.w;
+                xv[m][4] = x1.x; xv[m][5] = x1.y; xv[m][6] = x1.z; xv[m][7] = x1.w;
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const uint32_t wq[4] = {w[ch][r].x, w[ch][r].y, w[ch][r].z, w[ch][r].w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    uint32_t p0, p1;
+                    e4m3x4_to_bf16(wq[e], p0, p1);
+#pragma unroll
+                    for (int m = 0; m < MR; ++m) {
+                        const uint32_t xa = xv[m][2 * e], xb = xv[m][2 * e + 1];
+                        acc[m][r] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(mm_bf16x2, p0), __builtin_bit_cast(mm_bf16x2, xa), acc[m][r], false);
+                        acc[m][r] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(mm_bf16x2, p1), __builtin_bit_cast(mm_bf16x2, xb), acc[m][r], false);
+                    }
+                }
+            }
+        }
+    };
+    for (int win = 0; win < nwin; ++win) {
+        const int nt = min(WT, ntrip - win * WT);            // trips of this window
+        if (nwin > 1) {
+            stage_load(win + 1);                             // the NEXT window (behind the last: out of range, no access) lands while this one is consumed
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        for (int j0 = 0; j0 < nt; j0 += NB) {
+#pragma unroll
+            for (int jj = 0; jj < NB; ++jj) {
+                consume(wb[jj], win, j0 + jj);
+                // (keeps "consume trip t, then refill its registers": without the pin the sums sink below the loads and the ring is renamed)
+#pragma unroll
+                for (int m = 0; m < MR; ++m) asm volatile("" : "+v"(acc[m][0]), "+v"(acc[m][1]), "+v"(acc[m][2]), "+v"(acc[m][3]) : : "memory");
+                __builtin_amdgcn_sched_barrier(0);
+                issue(wb[jj], win * WT + j0 + jj + NB);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        if (nwin > 1) {                                      // into the OTHER buffer: everyone left it at the barrier before this window
+            stage_store(win + 1);
+            __syncthreads();
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < MR; ++m)
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[m][r] = wave_sum(acc[m][r]);
+    if (!live) return;
+    if constexpr (MODE == 0) {                               // lane (m * R + r) finishes output (m, rows[r])
+        if (lane < MR * R) {
+            const int m = lane / R, r = lane % R, n = rows[0] + r;
+            if (m < M && n < a.N) {
+                float v = 0.f;
+#pragma unroll
+                for (int mm = 0; mm < MR; ++mm)
+#pragma unroll
+                    for (int rr = 0; rr < R; ++rr)
+                        if (mm == m && rr == r) v = acc[mm][rr];
+                plain_store(a, m, n, v * a.scale[n]);
+            }
+        }
+    } else {
+        if (lane >= M) return;                               // lane m finishes the unit's outputs of row m
+        float v4[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            float t = 0.f;
+#pragma unroll
+            for (int mm = 0; mm < MR; ++mm)
+                if (mm == lane) t = acc[mm][r];
+            v4[r] = round_bf(t * a.scale[rows[r]]);           // what the unfused GEMV stores
+        }
+        fused_store<MODE>(a, rows, lane, v4);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ 5 .. 16 rows: MFMA
+// A wave owns four units = 16 weight rows as the A operand of v_mfma_f32_16x16x32_bf16 (lane fr = lane & 15 holds row fr), the x rows are
+// the B operand (row m = fr).  A lane's 16-byte load is row fr, columns k + 16 fq .. + 15 (fq = lane >> 4): widened in registers it is the
+// A fragment of TWO MFMAs, whose B fragments are the 32 bytes of x row m at the same columns in LDS -- which 32 columns an MFMA sums is
+// free as long as A and B agree, so no re-layout is needed.  A step = 64 columns, a trip = four steps (256 contiguous bytes per weight
+// row), NB trips in the ring.  The x rows pass through two LDS windows of 1024 columns (rows 2064 bytes apart: conflict-free fragment
+// reads).  ks = 4 (few weight rows): the four waves of a workgroup share one group of 16 rows, each takes a quarter of every window,
+// the partial tiles meet in LDS in a fixed order; ks depends on the number of units only, so a fused kernel and the sequence it
+// replaces see the same sums.  D: lane (m = fr, unit fq) ends with the four outputs of one unit for one x row.
+constexpr int WKM = 1024;
+constexpr int XROW = WKM * 2 + 16;
+
+template <int MRT, int MODE, bool PRENORM>
+__global__ __launch_bounds__(NT) void gemv_w8_mfma_kernel(W8Args a) {
+    constexpr int NB = 2;
+    constexpr int XV = MRT / 2;                              // 16-byte x vectors per thread and window: MRT rows x 128 vectors over 256 threads
+    extern __shared__ __attribute__((aligned(16))) unsigned char xs[];          // [2][M][XROW]
+    __shared__ f32x4 part[NT / 64][64];
+    __shared__ float red[MRT][NT / 64];
+    __shared__ float rstd_s[MRT];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int fr = lane & 15, fq = lane >> 4;
+    const int ks = a.ks;
+    const int group = blockIdx.x * ((NT / 64) / ks) + wave / ks, kslice = wave % ks;
+    const int K = a.K, M = a.M;
+    const int nwin = (K + WKM - 1) / WKM, nv = K >> 3;
+    const int tpw = 4 / ks;                                  // trips of this wave per window (16 / ks steps)
+    const int ntrip = nwin * tpw;
+    int rows[4];
+    unit_rows<MODE>(a, group * 4 + (fr >> 2), rows);
+    const bool alive = unit_live<MODE>(a, rows) && rows[fr & 3] < a.N;
+    const uint32_t wo = (uint32_t)min(rows[fr & 3], a.N - 1) * (uint32_t)a.ldw;
+    const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)a.W, 0, (uint32_t)((uint64_t)(a.N - 1) * a.ldw + (uint64_t)K), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, (uint32_t)((uint64_t)(M - 1) * a.ldx * 2 + (uint64_t)K * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsN = __builtin_amdgcn_make_buffer_rsrc((void*)(PRENORM ? a.norm_w : a.x), 0, (uint32_t)K * 2u, 0x00020000);
+    const int sm = threadIdx.x >> 7, sv = threadIdx.x & 127;   // staging: vector sv of window row sm + 2 i
+    u32x4 xr[XV], nr;
+    auto stage_load = [&](int w) {
+        const int v = w * (WKM / 8) + sv;
+#pragma unroll
+        for (int i = 0; i < XV; ++i) {
+            const int m = sm + 2 * i;
+            const uint32_t sk = (m < M && v < nv) ? 0u : OOB;
+            xr[i] = __builtin_amdgcn_raw_buffer_load_b128(rsX, ((uint32_t)min(m, M - 1) * (uint32_t)a.ldx * 2u + (uint32_t)v * 16u) | sk, 0, 0);
+        }
+        if constexpr (PRENORM) nr = __builtin_amdgcn_raw_buffer_load_b128(rsN, ((uint32_t)v * 16u) | (v < nv ? 0u : OOB), 0, 0);
+    };
+    auto stage_store = [&](int w) {
+        unsigned char* dst = xs + (size_t)(w & 1) * M * XROW + sv * 16;
+#pragma unroll
+        for (int i = 0; i < XV; ++i) {
+            const int m = sm + 2 * i;
+            if (m < M) {
+                u32x4 out = xr[i];
+                if constexpr (PRENORM) {
+                    float xv[8], nw[8];
+                    unpack8(xr[i], xv);
+                    unpack8(nr, nw);
+                    const float rs = rstd_s[m];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) xv[e] = nw[e] * round_bf(xv[e] * rs);
+                    out = pack8(xv);
+                }
+                *(u32x4*)(dst + (size_t)m * XROW) = out;
+            }
+        }
+    };
+    auto issue = [&](u32x4 (&w)[4], int t) {                 // trip t of this wave: window t / tpw, steps kslice * (16 / ks) + 4 (t % tpw) + i
+        const int k0 = (t / tpw) * WKM + (kslice * (16 / ks) + (t % tpw) * 4) * 64 + fq * 16;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int k = k0 + i * 64;
+            const uint32_t sk = (alive && t < ntrip && k < K) ? 0u : OOB;
+            w[i] = __builtin_amdgcn_raw_buffer_load_b128(rsW, (wo + (uint32_t)k) | sk, 0, 2);
+        }
+    };
+    u32x4 wb[NB][4];
+#pragma unroll
+    for (int j = 0; j < NB; ++j) issue(wb[j], j);
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (PRENORM) {                                 // rmsnorm_fwd_kernel's sums of squares (thread t: vectors t + 256 i in order; block_sum<256>), x from L2
+        float ss[MRT];
+#pragma unroll
+        for (int m = 0; m < MRT; ++m) ss[m] = 0.f;
+        for (int v = threadIdx.x; v < nv; v += NT) {
+#pragma unroll
+            for (int m = 0; m < MRT; ++m) {
+                if (m < M) {
+                    float xv[8];
+                    unpack8(*(const u32x4*)(a.x + (int64_t)m * a.ldx + v * 8), xv);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) ss[m] += xv[e] * xv[e];
+                }
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < MRT; ++m) {
+            const float w = wave_sum(ss[m]);
+            if (lane == 0) red[m][wave] = w;
+        }
+        __syncthreads();
+        if (threadIdx.x < MRT) {
+            float t = 0.f;
+#pragma unroll
+            for (int i = 0; i < NT / 64; ++i) t += red[threadIdx.x][i];
+            rstd_s[threadIdx.x] = rsqrtf(t / (float)K + a.eps);
+        }
+        __syncthreads();
+    }
+    stage_load(0);
+    stage_store(0);
+    __syncthreads();
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    const int xm = min(fr, M - 1);                           // (columns of D beyond M are never read)
+    auto consume = [&](const u32x4 (&w)[4], int t) {
+        const unsigned char* src = xs + (size_t)((t / tpw) & 1) * M * XROW + (size_t)xm * XROW
+                                   + ((kslice * (16 / ks) + (t % tpw) * 4) * 64 + fq * 16) * 2;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const u32x4 x0 = *(const u32x4*)(src + i * 128), x1 = *(const u32x4*)(src + i * 128 + 16);
+            const uint32_t q0 = w[i].x, q1 = w[i].y, q2 = w[i].z, q3 = w[i].w;
+            u32x4 a0, a1;
+            uint32_t lo, hi;
+            e4m3x4_to_bf16(q0, lo, hi); a0.x = lo; a0.y = hi;
+            e4m3x4_to_bf16(q1, lo, hi); a0.z = lo; a0.w = hi;
+            e4m3x4_to_bf16(q2, lo, hi); a1.x = lo; a1.y = hi;
+            e4m3x4_to_bf16(q3, lo, hi); a1.z = lo; a1.w = hi;
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a0), __builtin_bit_cast(bf16x8, x0), acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a1), __builtin_bit_cast(bf16x8, x1), acc1, 0, 0, 0);
+        }
+    };
+    for (int t0 = 0; t0 < ntrip; t0 += NB) {
+#pragma unroll
+        for (int jj = 0; jj < NB; ++jj) {
+            const int t = t0 + jj;                           // (uniform over the workgroup: every wave runs the same trips)
+            if (t < ntrip) {
+                const int win = t / tpw;
+                if (t % tpw == 0 && win + 1 < nwin) {        // the NEXT window lands while this one is consumed
+                    stage_load(win + 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                consume(wb[jj], t);
+                asm volatile("" : "+v"(acc0), "+v"(acc1) : : "memory");
+                __builtin_amdgcn_sched_barrier(0);
+                issue(wb[jj], t + NB);
+                __builtin_amdgcn_sched_barrier(0);
+                if (t % tpw == tpw - 1 && win + 1 < nwin) {  // into the OTHER buffer: everyone left it at the barrier before this window
+                    stage_store(win + 1);
+                    __syncthreads();
+                }
+            }
+        }
+    }
+    f32x4 acc = acc0 + acc1;
+    if (ks > 1) {
+        part[wave][lane] = acc;
+        __syncthreads();
+        if (kslice != 0) return;
+        acc = part[wave][lane];
+        for (int q = 1; q < ks; ++q) acc += part[wave + q][lane];
+    }
+    // lane (m = fr, unit fq of the group): the four outputs of that unit for x row m
+    const int m = fr;
+    int ro[4];
+    unit_rows<MODE>(a, group * 4 + fq, ro);
+    if (m >= M || !unit_live<MODE>(a, ro)) return;
+    if constexpr (MODE == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int n = ro[0] + r;
+            if (n < a.N) plain_store(a, m, n, acc[r] * a.scale[n]);
+        }
+    } else {
+        float v4[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v4[r] = round_bf(acc[r] * a.scale[ro[r]]);
+        fused_store<MODE>(a, ro, m, v4);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ Q, scale -> bf16 (prompt pass, batches over 16)
+__global__ __launch_bounds__(NT) void dequant_w8_kernel(const uint8_t* __restrict__ q, int64_t ldq, const float* __restrict__ scale,
+                                                        uint16_t* __restrict__ out, int64_t ldo, int64_t N, int kv) {
+    const int64_t idx = (int64_t)blockIdx.x * NT + threadIdx.x;
+    if (idx >= N * kv) return;
+    const int64_t n = idx / kv;
+    const int c = (int)(idx % kv);
+    const u32x4 w = *(const u32x4*)(q + n * ldq + (int64_t)c * 16);
+    const float s = scale[n];
+    const uint32_t wq[4] = {w.x, w.y, w.z, w.w};
+    uint32_t o[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const mm_f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)wq[e], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)wq[e], true);
+        o[2 * e] = pack2bf(lo.x * s, lo.y * s);
+        o[2 * e + 1] = pack2bf(hi.x * s, hi.y * s);
+    }
+    uint16_t* dst = out + n * ldo + (int64_t)c * 16;
+    *(u32x4*)dst = u32x4{o[0], o[1], o[2], o[3]};
+    *(u32x4*)(dst + 8) = u32x4{o[4], o[5], o[6], o[7]};
+}
+
+constexpr int LDS_OPT_IN = 80 * 1024;                        // both forms hold at most 66 KiB of x windows next to a few KiB of static LDS
+
+template <int MODE>
+int launch_w8(W8Args& a, int64_t units, bool prenorm, hipStream_t s) {
+#define W8_LAUNCH(KERNEL, GRID, LDS) do { static std::atomic<uint64_t> ok{0};                                                      \
+        if (mm_ensure_dynamic_lds((const void*)KERNEL, LDS_OPT_IN, ok) != MM355_OK) return MM355_ELAUNCH;                            \
+        hipLaunchKernelGGL(KERNEL, dim3(GRID), dim3(NT), LDS, s, a); } while (0)
+    if (a.M <= 4) {
+        const unsigned grid = (unsigned)((units + NT / 64 - 1) / (NT / 64));
+        const int mr = a.M == 1 ? 1 : (a.M == 2 ? 2 : 4);
+        const int wt = mr == 4 ? 2 : 4, ntrip = (a.K + 2047) >> 11;
+        const int lds = (ntrip > wt ? 2 : 1) * mr * (ntrip < wt ? ntrip : wt) * 2048 * 2;        // <= 64 KiB
+#define W8_V(MR) do { if (prenorm) { if constexpr (MODE != 0) W8_LAUNCH((gemv_w8_valu_kernel<MR, MODE, true>), grid, lds); }         \
+                      else W8_LAUNCH((gemv_w8_valu_kernel<MR, MODE, false>), grid, lds); } while (0)
+        if (mr == 1) W8_V(1);
+        else if (mr == 2) W8_V(2);
+        else W8_V(4);
+#undef W8_V
+        return mm_launch_status();
+    }
+    const int64_t groups = (units + 3) / 4;                  // 16 weight rows each
+    a.ks = groups < 1024 ? 4 : 1;
+    const unsigned grid = (unsigned)((groups + (NT / 64) / a.ks - 1) / ((NT / 64) / a.ks));
+    const int lds = 2 * a.M * XROW;
+#define W8_M(MRT) do { if (prenorm) { if constexpr (MODE != 0) W8_LAUNCH((gemv_w8_mfma_kernel<MRT, MODE, true>), grid, lds); }      \
+                       else W8_LAUNCH((gemv_w8_mfma_kernel<MRT, MODE, false>), grid, lds); } while (0)
+    if (a.M <= 8) W8_M(8);
+    else W8_M(16);
+#undef W8_M
+#undef W8_LAUNCH
+    return mm_launch_status();
+}
+
+// x rows, weight bytes and every fused operand in the form the kernels address them (32-bit byte offsets through buffer descriptors)
+int w8_check(const void* x, int64_t ldx, const void* Wq, int64_t ldw, const float* scale, int fmt, int64_t M, int64_t N, int64_t K) {
+    if (!x || !Wq || !scale || M <= 0 || N <= 0 || K <= 0) return MM355_EINVAL;
+    if (fmt != MM355_W8_E4M3) return MM355_EINVAL;
+    if ((K & 15) || (ldx & 7) || (ldw & 15) || ldw < K || !mm_aligned16(x) || !mm_aligned16(Wq) || (((uintptr_t)scale) & 3u)) return MM355_EINVAL;
+    if (N > 0x7fffffff || K > 0x7fffffff) return MM355_EINVAL;
+    if (M > 16) return MM355_EUNSUPPORTED;                   // more rows: mm355_dequant_w8_bf16 + mm355_gemm_bf16
+    if ((uint64_t)(N - 1) * ldw + K >= 0xf0000000ull || (uint64_t)(M - 1) * ldx * 2 + K * 2 >= 0xf0000000ull) return MM355_EUNSUPPORTED;
+    return MM355_OK;
+}
+
+}  // namespace
+
+extern "C" int mm355_gemv_w8(const mm355_bf16* x, int64_t ldx, const uint8_t* Wq, int64_t ldw_bytes, const float* scale, int fmt, void* y,
+                             int64_t ldy, int64_t M, int64_t N, int64_t K, const mm355_bf16* bias, const mm355_bf16* residual, int64_t ldr,
+                             uint32_t flags, void* stream) {
+    (void)hipGetLastError();   // drop any stale, unrelated runtime status before we launch
+    if (!y) return MM355_EINVAL;
+    if ((flags & MM355_GEMM_BIAS) && !bias) return MM355_EINVAL;
+    if ((flags & MM355_GEMM_RESIDUAL) && !residual) return MM355_EINVAL;
+    if ((flags & MM355_GEMM_GELU_ERF) && (flags & MM355_GEMM_GELU_TANH)) return MM355_EINVAL;
+    const int rc = w8_check(x, ldx, Wq, ldw_bytes, scale, fmt, M, N, K);
+    if (rc != MM355_OK) return rc;
+    if (flags & MM355_GEMM_ACCUMULATE) return MM355_EUNSUPPORTED;
+    W8Args a = {};
+    a.x = x; a.ldx = ldx; a.W = Wq; a.ldw = ldw_bytes; a.scale = scale; a.M = (int)M; a.N = (int)N; a.K = (int)K;
+    a.y = y; a.ldy = ldy; a.bias = bias; a.res = residual; a.ldr = ldr; a.flags = flags;
+    return launch_w8<0>(a, (N + 3) / 4, false, (hipStream_t)stream);
+}
+
+extern "C" int mm355_gemv_swiglu_w8(const mm355_bf16* x, int64_t ldx, const uint8_t* Wq, int64_t ldw_bytes, const float* scale, int fmt,
+                                    mm355_bf16* act, int64_t ld_act, int64_t M, int64_t I, int64_t K, const mm355_bf16* norm_w, float eps,
+                                    void* stream) {
+    (void)hipGetLastError();
+    if (!act || I <= 0) return MM355_EINVAL;
+    if (I > 0x3fffffff) return MM355_EINVAL;
+    const int rc = w8_check(x, ldx, Wq, ldw_bytes, scale, fmt, M, 2 * I, K);
+    if (rc != MM355_OK) return rc;
+    if (I & 1) return MM355_EUNSUPPORTED;
+    if ((ld_act & 1) || (((uintptr_t)act) & 3u)) return MM355_EINVAL;
+    if (norm_w && !mm_aligned16(norm_w)) return MM355_EINVAL;
+    if (norm_w && M > 4 && M * (((K + 31) & ~(int64_t)31) + 8) * 2 > 140 * 1024) return MM355_EUNSUPPORTED;   // as the bf16 form documents
+    W8Args a = {};
+    a.x = x; a.ldx = ldx; a.W = Wq; a.ldw = ldw_bytes; a.scale = scale; a.M = (int)M; a.N = (int)(2 * I); a.K = (int)K;
+    a.norm_w = norm_w; a.eps = eps; a.out = act; a.ld_out = ld_act; a.I = (int)I;
+    return launch_w8<1>(a, I / 2, norm_w != nullptr, (hipStream_t)stream);
+}
+
+extern "C" int mm355_gemv_rope_append_w8(const mm355_bf16* x, int64_t ldx, const uint8_t* Wq, int64_t ldw_bytes, const float* scale, int fmt,
+                                         mm355_bf16* qkv, int64_t ld_qkv, int64_t M, int64_t Hq, int64_t Hkv, int64_t d, int64_t K,
+                                         const mm355_bf16* norm_w, float eps, const mm355_bf16* cos_t, const mm355_bf16* sin_t,
+                                         const int32_t* positions, mm355_bf16* k_cache, mm355_bf16* v_cache, int64_t ld_kv,
+                                         int64_t batch_stride_kv, void* stream) {
+    (void)hipGetLastError();
+    if (!qkv || !cos_t || !sin_t || !positions || !k_cache || !v_cache || Hq <= 0 || Hkv <= 0 || d <= 0) return MM355_EINVAL;
+    const int64_t N = (Hq + 2 * Hkv) * d;
+    const int rc = w8_check(x, ldx, Wq, ldw_bytes, scale, fmt, M, N, K);
+    if (rc != MM355_OK) return rc;
+    if (d & 3) return MM355_EUNSUPPORTED;                    // rotation partners in pairs: d / 2 even
+    if ((ld_qkv & 1) || (ld_kv & 3) || (batch_stride_kv & 3) || (((uintptr_t)qkv) & 3u) || (((uintptr_t)k_cache) & 7u) || (((uintptr_t)v_cache) & 7u))
+        return MM355_EINVAL;
+    if (norm_w && !mm_aligned16(norm_w)) return MM355_EINVAL;
+    if (norm_w && M > 4 && M * (((K + 31) & ~(int64_t)31) + 8) * 2 > 140 * 1024) return MM355_EUNSUPPORTED;
+    W8Args a = {};
+    a.x = x; a.ldx = ldx; a.W = Wq; a.ldw = ldw_bytes; a.scale = scale; a.M = (int)M; a.N = (int)N; a.K = (int)K;
+    a.norm_w = norm_w; a.eps = eps; a.out = qkv; a.ld_out = ld_qkv; a.Hq = (int)Hq; a.Hkv = (int)Hkv; a.d = (int)d;
+    a.cos_t = cos_t; a.sin_t = sin_t; a.positions = positions; a.kc = k_cache; a.vc = v_cache; a.ld_kv = ld_kv; a.bs_kv = batch_stride_kv;
+    return launch_w8<2>(a, N / 4, norm_w != nullptr, (hipStream_t)stream);
+}
+
+extern "C" int mm355_dequant_w8_bf16(const uint8_t* Wq, int64_t ldw_bytes, const float* scale, int fmt, mm355_bf16* out, int64_t ld_out,
+                                     int64_t N, int64_t K, void* stream) {
+    (void)hipGetLastError();
+    if (!Wq || !scale || !out || N <= 0 || K <= 0) return MM355_EINVAL;
+    if (fmt != MM355_W8_E4M3) return MM355_EINVAL;
+    if ((K & 15) || (ldw_bytes & 15) || ldw_bytes < K || (ld_out & 7) || ld_out < K || !mm_aligned16(Wq) || !mm_aligned16(out)) return MM355_EINVAL;
+    const int64_t kv = K / 16, total = N * kv;
+    if (K > 0x7fffffff || (total + NT - 1) / NT > 0x7fffffff) return MM355_EINVAL;
+    hipLaunchKernelGGL(dequant_w8_kernel, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, (hipStream_t)stream, Wq, ldw_bytes, scale, out,
+                       ld_out, N, (int)kv);
+    return mm_launch_status();
+}

@@ -799,6 +799,7 @@ def decoder_prefill(x, layers, meta, cache, row=0):
         return x
     for i, layer in enumerate(layers):
         params_ready(layer)
+        w8_materialize(layer)                                 # (a quantised layer: its weights dequantised into the shared scratch, see W8Scratch)
         x, saved = decoder_layer_forward(x, layer, meta)
         qkv = saved[0]
         if B == 1:
@@ -827,6 +828,7 @@ def _prefill_layers_fused(x, layers, meta, cache, row, ident):
     n1 = None
     for i, layer in enumerate(layers):
         params_ready(layer)
+        w8_materialize(layer)
         att, mlp = layer.self_attn, layer.mlp
         wqkv = fused_weight([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight])
         wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
@@ -852,10 +854,106 @@ def _prefill_layers_fused(x, layers, meta, cache, row, ident):
     return x
 
 
+class W8Scratch:
+    """ONE layer's four fused projections as bf16, shared by every quantised layer of a model: the routes that have no w8 kernel (the prompt
+    pass, decode steps of more than 16 rows) dequantise the layer they are about to run into it and take their existing bf16 GEMMs from
+    there.  Correct and not fast: every layer costs four dequant launches and a write + read of its bf16 weights on top of the GEMMs
+    (0.44 GB at LLaMA-3-8B widths); a w8 GEMM is future work."""
+
+    def __init__(self):
+        self.bufs = None
+
+    def views(self, rec):
+        shapes = [tuple(getattr(rec, n)[0].shape) for n in W8Layer.NAMES]
+        if self.bufs is None or [tuple(b.shape) for b in self.bufs] != shapes:
+            self.bufs = [torch.empty(s, device=rec.qkv[0].device, dtype=BF16) for s in shapes]
+        return self.bufs
+
+
+class W8Layer:
+    """The quantised fused weights of one decoder layer (format "fp8_e4m3": ops.quantize_w8): q|k|v, o, gate|up, down, each as
+    (bytes uint8 [N, K], scale f32 [N]) -- the FUSED matrices, as fused_weight concatenates them.  `released`: the layer's bf16 projection
+    parameters no longer hold storage of their own (they alias the model's W8Scratch while a scratch route runs)."""
+    NAMES = ("qkv", "o", "gu", "down")
+
+    def __init__(self, layer, scratch, pow2_scales=False, keep_bf16=False):
+        att, mlp = layer.self_attn, layer.mlp
+        self.params = {"qkv": [att.q_proj.weight, att.k_proj.weight, att.v_proj.weight], "o": [att.o_proj.weight],
+                       "gu": [mlp.gate_proj.weight, mlp.up_proj.weight], "down": [mlp.down_proj.weight]}
+        self.rows = {n: [p.shape[0] for p in ps] for n, ps in self.params.items()}
+        for n in self.NAMES:
+            setattr(self, n, ops.quantize_w8(torch.cat([p.data for p in self.params[n]], 0), pow2_scales))
+        self.scratch = scratch
+        self.released = not keep_bf16
+        for ps in self.params.values():
+            for p in ps:
+                p.w8_quantized = True
+        if self.released:
+            for ps in self.params.values():
+                for p in ps:
+                    p.data = p.data.new_empty((0, p.shape[1]))
+                    p.requires_grad_(False)
+
+    def materialize(self):
+        """This layer's weights as bf16 for a route without w8 kernels (see W8Scratch).  A layer that kept its bf16 parameters runs on them."""
+        if not self.released:
+            return
+        for n, buf in zip(self.NAMES, self.scratch.views(self)):
+            ops.dequant_w8(*getattr(self, n), out=buf)
+            off = 0
+            for p, rows in zip(self.params[n], self.rows[n]):
+                p.data = buf[off:off + rows]
+                off += rows
+
+
+def refuse_w8_params(params, who):
+    """Parameters of a decoder quantised with quantize_decoder_ cannot be trained or sharded: refused by name."""
+    flat = [p for g in params for p in (g["params"] if isinstance(g, dict) else [g])]
+    if any(getattr(p, "w8_quantized", False) for p in flat):
+        raise RuntimeError(f"{who}: the decoder was quantised with quantize_decoder_ (weight-only FP8 is an inference format); "
+                           "ZeRO wrapping and training of quantised weights are not supported")
+
+
+def w8_materialize(layer):
+    rec = getattr(layer, "w8", None)
+    if rec is not None:
+        rec.materialize()
+
+
+def _decode_rows16_w8(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound):
+    """_decode_rows16 on layers that carry a W8Layer record: the same five / seven launches per layer on the mm355_gemv*_w8 kernels."""
+    nq = meta.Hq * meta.d
+    fused = VARIANTS["decode_fused"] and meta.I % 2 == 0 and meta.d % 4 == 0
+    for i, layer in enumerate(layers):
+        rec = layer.w8
+        if fused:
+            fold = x.shape[0] <= VARIANTS["decode_fold_rows"]
+            n1 = x if fold else ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
+            qkv = ops.gemv_rope_append_w8(n1, *rec.qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i],
+                                          norm_w=layer.input_layernorm.weight if fold else None, eps=meta.eps)
+            o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
+            x2 = ops.gemv_w8(o, *rec.o, residual=x)
+            n2 = x2 if fold else ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
+            act = ops.gemv_swiglu_w8(n2, *rec.gu, meta.I, norm_w=layer.post_attention_layernorm.weight if fold else None, eps=meta.eps)
+            x = ops.gemv_w8(act, *rec.down, residual=x2)
+            continue
+        n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
+        qkv = ops.gemv_w8(n1, *rec.qkv)
+        ops.rope_kv_append_(qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
+        o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
+        x2 = ops.gemv_w8(o, *rec.o, residual=x)
+        n2 = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
+        act = ops.swiglu_fwd(ops.gemv_w8(n2, *rec.gu), meta.I)
+        x = ops.gemv_w8(act, *rec.down, residual=x2)
+    return x
+
+
 def _decode_rows16(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound):
     """<= 16 new rows (one per sequence) through every decoder layer against their cache rows k / v [layers, rows, max_len, width]:
     every weight is streamed ONCE for all rows (mm355_gemv* take M <= 16: up to four rows on the vector ALU, 5 .. 16 on MFMA), attention per
     row at its own length."""
+    if getattr(layers[0], "w8", None) is not None:
+        return _decode_rows16_w8(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound)
     nq = meta.Hq * meta.d
     for i, layer in enumerate(layers):
         params_ready(layer)
@@ -902,6 +1000,7 @@ def _decode_rows_gemm(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_
         gu_gemv = VARIANTS["decode_wide_gu_gemv"] and x.shape[0] <= 32 and meta.I % 2 == 0 and ops.gemv_rows32_units(meta.I // 2)
         for i, layer in enumerate(layers):
             params_ready(layer)
+            w8_materialize(layer)                             # (17 rows and more on quantised layers: the scratch route, see W8Scratch)
             att, mlp = layer.self_attn, layer.mlp
             wqkv = fused_weight([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight])
             wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
@@ -922,6 +1021,7 @@ def _decode_rows_gemm(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_
         return x
     for i, layer in enumerate(layers):
         params_ready(layer)
+        w8_materialize(layer)
         att, mlp = layer.self_attn, layer.mlp
         wqkv = fused_weight([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight])
         wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])

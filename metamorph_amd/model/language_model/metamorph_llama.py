@@ -340,6 +340,9 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
             return self._cached_forward(input_ids, inputs_embeds, attention_mask, past_key_values, return_dict)
         if output_attentions:
             raise NotImplementedError("output_attentions: attention probabilities are never materialised by the flash kernel")
+        if self.w8_format is not None:
+            raise NotImplementedError("forward without past_key_values on a decoder quantised with quantize_decoder_: the weight-only FP8 "
+                                      "weights serve the cached generation path only (greedy_decode, generate() / forward with a HipKVCache)")
         return_dict = True if return_dict is None else return_dict
         cfg = self.config
         F.params_ready(None)
@@ -579,6 +582,56 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         output = [torch.tensor(generated, dtype=torch.int32, device=inputs_embeds.device)]
         return (output, emb) if output_image else output
 
+    # ------------------------------------------------------------------ weight-only FP8 decode (reference builder.py:13-25, load_8bit=True)
+    w8_format = None                                         # set by quantize_decoder_
+    w8_lm_head = None                                        # (bytes, scales) of a quantised lm_head
+    w8_released = False
+
+    @torch.no_grad()
+    def quantize_decoder_(self, fmt="fp8_e4m3", lm_head=False, pow2_scales=False, keep_bf16=False):
+        """Quantise the fused projections of every decoder layer (q|k|v, o, gate|up, down; on request the lm_head) to weight-only FP8:
+        e4m3 bytes + one fp32 scale per output row (ops.quantize_w8).  Decode steps of up to 16 sequences then stream half the bytes
+        (mm355_gemv*_w8); the prompt pass and larger batches run the bf16 GEMMs on one layer's weights dequantised into a shared scratch
+        buffer (functional.W8Scratch: correct, not fast).  The bf16 storage of the quantised projections is released unless keep_bf16;
+        embed_tokens, norms, vision tower, projector and vision head stay bf16.  The model ends in eval mode: generation only."""
+        if fmt not in ops.W8_FORMATS:
+            raise ValueError(f"quantize_decoder_: unknown format {fmt!r} (supported: {sorted(ops.W8_FORMATS)})")
+        if self.w8_format is not None:
+            raise RuntimeError(f"quantize_decoder_: the decoder is already quantised ({self.w8_format}); a second call would quantise "
+                               "quantised weights")
+        if lm_head and (getattr(self.config, "tie_word_embeddings", False)
+                        or self.lm_head.weight.data_ptr() == self.model.embed_tokens.weight.data_ptr()):
+            raise ValueError("quantize_decoder_(lm_head=True) with tied embeddings: lm_head shares its storage with embed_tokens, which "
+                             "stays bf16; pass lm_head=False")
+        scratch = F.W8Scratch()
+        for layer in self.model.layers:
+            layer.w8 = F.W8Layer(layer, scratch, pow2_scales=pow2_scales, keep_bf16=keep_bf16)
+        if lm_head:
+            w = self.lm_head.weight
+            self.w8_lm_head = ops.quantize_w8(w.data, pow2_scales)
+            w.w8_quantized = True
+            if not keep_bf16:
+                w.data = w.data.new_empty((0, w.shape[1]))
+                w.requires_grad_(False)
+        self.w8_format = fmt
+        self.w8_released = not keep_bf16
+        self.eval()
+        return self
+
+    def state_dict(self, *args, **kwargs):
+        if self.w8_format is not None and self.w8_released:
+            raise RuntimeError("state_dict of a decoder quantised with quantize_decoder_: the bf16 weights of the quantised projections "
+                               "were released (save before quantising, or pass keep_bf16=True)")
+        return super().state_dict(*args, **kwargs)
+
+    def _lm_head_w8(self, hid):
+        """fp32 logits of the normed rows on the quantised lm_head: up to 16 rows mm355_gemv_w8, more rows the bf16 GEMM on the dequantised
+        weight (a temporary of the lm_head's size: correct, not fast)."""
+        q, scale = self.w8_lm_head
+        if hid.shape[0] <= 16:
+            return ops.gemv_w8(hid, q, scale, out=torch.empty((hid.shape[0], q.shape[0]), device=hid.device, dtype=torch.float32))
+        return ops.gemm(hid, ops.dequant_w8(q, scale), out_f32=True)
+
     # ------------------------------------------------------------------ cached decode (row N1)
     def _decode_meta(self, L):
         cfg = self.config
@@ -598,8 +651,11 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
             if self.apply_softmax:
                 pred_z = ops.softmax_rows(pred_z.contiguous(), 0.07)
             hid = self.model.mm_projector(pred_z)
-        logits = ops.gemv(hid.contiguous(), self.lm_head.weight.data, out=torch.empty((1, self.lm_head.weight.shape[0]), device=x.device,
-                                                                                    dtype=torch.float32))
+        if self.w8_lm_head is not None:
+            logits = self._lm_head_w8(hid.contiguous())
+        else:
+            logits = ops.gemv(hid.contiguous(), self.lm_head.weight.data, out=torch.empty((1, self.lm_head.weight.shape[0]), device=x.device,
+                                                                                        dtype=torch.float32))
         return logits, hid, pred_z
 
     @torch.no_grad()
@@ -696,6 +752,9 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
     def _rows_logits(self, rows, return_hidden=False):
         """final norm + lm_head -> fp32 logits [n, V] (reference :349-359 final norm, :393-399); return_hidden: (logits, normed rows)."""
         hid = self.model.norm(rows)
+        if self.w8_lm_head is not None:
+            logits = self._lm_head_w8(hid.contiguous())
+            return (logits, hid) if return_hidden else logits
         if hid.shape[0] <= 32 and ops.gemv_supported(hid, self.lm_head.weight.data):     # (17 .. 32 rows: wide weights only -- the lm_head is one)
             logits = ops.gemv(hid.contiguous(), self.lm_head.weight.data,
                               out=torch.empty((hid.shape[0], self.lm_head.weight.shape[0]), device=rows.device, dtype=torch.float32))

@@ -271,6 +271,101 @@ def gemv_rope_append(x, wqkv, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache,
     return out
 
 
+# ------------------------------------------------------------------------------------------------ weight-only FP8 (decode)
+
+W8_E4M3 = 1                                                  # MM355_W8_E4M3
+W8_FORMATS = {"fp8_e4m3": W8_E4M3}
+E4M3_MAX = 448.0
+
+
+def quantize_w8(w, pow2_scales=False):
+    """w [N, K] -> (q uint8 [N, K], scale f32 [N]) of format "fp8_e4m3": scale[n] = amax_k |w[n, k]| / 448 (a row of zeros: 1; pow2_scales:
+    rounded UP to a power of two, the dequantised weights are then exact in bf16), q = the OCP e4m3fn byte of RNE(w / scale), saturating at
+    +-448, never a NaN encoding.  Not a hot path: torch ops, on whatever device w lives on."""
+    assert w.dim() == 2
+    wf = w.detach().float()
+    amax = wf.abs().amax(dim=1)
+    scale = torch.where(amax > 0, amax / E4M3_MAX, torch.ones_like(amax))
+    if pow2_scales:
+        m, e = torch.frexp(scale)                            # scale = m * 2^e, m in [0.5, 1)
+        scale = torch.where(m == 0.5, scale, torch.ldexp(torch.ones_like(scale), e))
+    scale = scale.clamp_min(2.0 ** -126)
+    q = (wf / scale[:, None]).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn)
+    return q.view(torch.uint8).contiguous(), scale.contiguous()
+
+
+def _w8_operands(wq, scale, K):
+    assert wq.dtype == torch.uint8 and wq.dim() == 2 and wq.stride(1) == 1 and wq.shape[1] == K, (wq.dtype, wq.shape, K)
+    assert scale.dtype == torch.float32 and scale.is_contiguous() and scale.numel() == wq.shape[0]
+    return wq.data_ptr(), wq.shape[0], wq.stride(0) if wq.shape[0] > 1 else max(wq.stride(0), K)
+
+
+def dequant_w8(wq, scale, out=None):
+    """bf16 [N, K] = RNE(fp32(wq) * scale[:, None]) (mm355_dequant_w8_bf16): the operand of the bf16 GEMMs on the routes that have no w8 kernel."""
+    _chk_dev(wq, scale, out)
+    pw, N, ldw = _w8_operands(wq, scale, wq.shape[1])
+    K = wq.shape[1]
+    out = torch.empty((N, K), device=wq.device, dtype=BF16) if out is None else out
+    assert out.dtype == BF16 and tuple(out.shape) == (N, K) and out.stride(1) == 1
+    _lib.check(_L().mm355_dequant_w8_bf16(pw, ldw, scale.data_ptr(), W8_E4M3, out.data_ptr(), out.stride(0) if N > 1 else max(out.stride(0), K),
+                                          N, K, _stream()), f"mm355_dequant_w8_bf16 N={N} K={K}")
+    return out
+
+
+def gemv_w8(x, wq, scale, out=None, bias=None, residual=None, gelu=None):
+    """out[M,N] = epilogue(scale[n] * x[M,K] . fp32(wq[N,K])^T) for M <= 16 rows: gemv() over e4m3 weight bytes with one fp32 scale per row."""
+    _chk_dev(x, wq, scale, out, bias, residual)
+    px, M, K, ldx = _rows2d(x)
+    assert x.dtype == BF16
+    pw, N, ldw = _w8_operands(wq, scale, K)
+    if out is None:
+        out = torch.empty((M, N), device=x.device, dtype=BF16)
+    po, Mo, No, ldy = _rows2d(out)
+    assert (Mo, No) == (M, N)
+    flags = GEMM_OUT_F32 if out.dtype == torch.float32 else 0
+    pr, ldr = 0, 0
+    if bias is not None:
+        flags |= GEMM_BIAS
+    if gelu is not None:
+        flags |= {"erf": GEMM_GELU_ERF, "tanh": GEMM_GELU_TANH}[gelu]
+    if residual is not None:
+        pr, Mr, Nr, ldr = _rows2d(residual)
+        assert (Mr, Nr) == (M, N)
+        flags |= GEMM_RESIDUAL
+    _lib.check(_L().mm355_gemv_w8(px, ldx, pw, ldw, scale.data_ptr(), W8_E4M3, po, ldy, M, N, K, _p(bias), pr, ldr, flags, _stream()),
+               f"mm355_gemv_w8 M={M} N={N} K={K}")
+    return out
+
+
+def gemv_swiglu_w8(x, wq, scale, I, norm_w=None, eps=0.0, out=None):
+    """gemv_swiglu() over the e4m3 bytes of the fused gate|up weight."""
+    _chk_dev(x, wq, scale, norm_w, out)
+    px, M, K, ldx = _rows2d(x)
+    assert x.dtype == BF16
+    pw, N, ldw = _w8_operands(wq, scale, K)
+    assert N == 2 * I
+    out = torch.empty((M, I), device=x.device, dtype=BF16) if out is None else out
+    _lib.check(_L().mm355_gemv_swiglu_w8(px, ldx, pw, ldw, scale.data_ptr(), W8_E4M3, out.data_ptr(), out.stride(0), M, I, K, _p(norm_w),
+                                         float(eps), _stream()), "mm355_gemv_swiglu_w8")
+    return out
+
+
+def gemv_rope_append_w8(x, wq, scale, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache, norm_w=None, eps=0.0, out=None):
+    """gemv_rope_append() over the e4m3 bytes of the fused q|k|v weight."""
+    _chk_dev(x, wq, scale, norm_w, cos, sin, positions, k_cache, v_cache, out)
+    px, M, K, ldx = _rows2d(x)
+    assert x.dtype == BF16
+    pw, N, ldw = _w8_operands(wq, scale, K)
+    assert N == (Hq + 2 * Hkv) * d and positions.dtype == torch.int32
+    assert k_cache.stride() == v_cache.stride() and k_cache.stride(2) == 1
+    out = torch.empty((M, N), device=x.device, dtype=BF16) if out is None else out
+    _lib.check(_L().mm355_gemv_rope_append_w8(px, ldx, pw, ldw, scale.data_ptr(), W8_E4M3, out.data_ptr(), out.stride(0), M, Hq, Hkv, d, K,
+                                              _p(norm_w), float(eps), cos.data_ptr(), sin.data_ptr(), positions.data_ptr(),
+                                              k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(1), k_cache.stride(0), _stream()),
+               "mm355_gemv_rope_append_w8")
+    return out
+
+
 def rope_kv_append_(qkv, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache):
     """qkv [B, (Hq+2Hkv)*d] new rows: rotate q (in place) and k at positions[b] (int32, device); k, v -> cache row positions[b]."""
     _chk_dev(qkv, cos, sin, positions, k_cache, v_cache)

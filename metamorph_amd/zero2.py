@@ -97,6 +97,8 @@ class Zero2AdamW(torch.optim.Optimizer):
         # `params`: an iterable of tensors, or of torch-style group dicts ({"params": [...], "lr": ..., "weight_decay": ...}) --
         # e.g. the reference's separate `vision_lr` group for the tower (metamorph_trainer.py:201-233)
         params = list(params)
+        from . import functional as F
+        F.refuse_w8_params(params, "Zero2AdamW")
         if params and isinstance(params[0], dict):
             groups = [dict(g, params=[p for p in g["params"] if p.requires_grad]) for g in params]
             groups = [g for g in groups if g["params"]]

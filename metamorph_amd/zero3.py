@@ -65,6 +65,8 @@ class Zero3AdamW(torch.optim.Optimizer):
                  shard_update=None, sumsq=None, clip_coef=None, accumulate=None, param_slots=3, grad_slots=2, min_shard_numel=1 << 20,
                  force_collectives=None, tensor_collectives=None):
         params = list(params)
+        from . import functional as F
+        F.refuse_w8_params(params, "Zero3AdamW")
         if params and isinstance(params[0], dict):
             groups = [dict(g, params=[p for p in g["params"] if p.requires_grad]) for g in params]
             groups = [g for g in groups if g["params"]]
