@@ -354,7 +354,7 @@ int mm355_attn_decode_variant(const mm355_bf16* q, int64_t ld_q, const mm355_bf1
  * load_pretrained_model(..., load_8bit=True); this is a scheme of its own, not LLM.int8).  fmt MM355_W8_E4M3: W[N][K] stored as OCP e4m3fn
  * bytes Wq[N][K] (the gfx950 encoding, not fnuz; row stride ldw_bytes), plus scale[N] fp32; dequantised value fp32(Wq[n][k]) * scale[n].
  *   gemv_w8: y[m][n] = epilogue(scale[n] * sum_k fp32(Wq[n][k]) * fp32(x[m][k])), x bf16, fp32 accumulation, the scale applied once, after
- *         the sum; flags and epilogue as mm355_gemv_bf16.  M <= 16 rows (more: MM355_EUNSUPPORTED -- mm355_dequant_w8_bf16 + the GEMM).  Up to
+ *         the sum; flags and epilogue as mm355_gemv_bf16.  M <= 16 rows (more: MM355_EUNSUPPORTED -- mm355_gemm_w8 below).  Up to
  *         four rows on the vector ALU (v_cvt_pk_f32_fp8 + v_perm_b32 widen a pair of weights to packed bf16 for v_dot2c_f32_bf16), 5 .. 16 on
  *         v_mfma_f32_16x16x32_bf16 with the bytes widened in registers; x rows parked in LDS windows, a register ring of weight loads.
  *         fmt other than MM355_W8_E4M3, K % 16 != 0, ldw_bytes % 16 != 0, a NULL scale or misaligned pointers: MM355_EINVAL before any
@@ -362,8 +362,8 @@ int mm355_attn_decode_variant(const mm355_bf16* q, int64_t ld_q, const mm355_bf1
  *   gemv_swiglu_w8 / gemv_rope_append_w8: the twins of mm355_gemv_swiglu_bf16 / mm355_gemv_rope_append_bf16 (same row limits, same
  *         MM355_EUNSUPPORTED cases: odd I, d % 4 != 0, norm_w with 5 .. 16 rows beyond 140 KiB of rows): the bits of mm355_gemv_w8 +
  *         mm355_swiglu_fwd, of mm355_gemv_w8 + mm355_rope_kv_append, and with norm_w of mm355_rmsnorm_fwd in front.
- *   dequant_w8_bf16: out[n][k] = bf16(fp32(Wq[n][k]) * scale[n]) (RNE), a plain streaming kernel: the prompt pass and batches over 16 rows
- *         run the bf16 GEMMs on one layer's weights dequantised into a scratch buffer.  ld_out % 8 == 0, out 16-byte aligned.
+ *   dequant_w8_bf16: out[n][k] = bf16(fp32(Wq[n][k]) * scale[n]) (RNE), a plain streaming kernel: the routes mm355_gemm_w8* do not take (passes of
+ *         more than 4096 rows, projections that are not split) run the bf16 GEMMs on weights dequantised into a scratch buffer.  ld_out % 8 == 0, out 16-byte aligned.
  * ------------------------------------------------------------------------------------------------ */
 #define MM355_W8_E4M3 1
 int mm355_gemv_w8(const mm355_bf16* x, int64_t ldx, const uint8_t* Wq, int64_t ldw_bytes, const float* scale, int fmt, void* y, int64_t ldy,
@@ -378,6 +378,39 @@ int mm355_gemv_rope_append_w8(const mm355_bf16* x, int64_t ldx, const uint8_t* W
                               int64_t batch_stride_kv, void* stream);
 int mm355_dequant_w8_bf16(const uint8_t* Wq, int64_t ldw_bytes, const float* scale, int fmt, mm355_bf16* out, int64_t ld_out,
                           int64_t N, int64_t K, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The split-K GEMM over the same weight-only FP8 format: the prompt pass and decode steps of MORE than 16 sequences of a quantised decoder
+ * stream the weight as bytes instead of dequantising it into a scratch buffer first (reference: the nn.Linear calls of the 8-bit model,
+ * metamorph/model/builder.py:13-25 with metamorph_llama.py:665-717).  x[M][K] bf16, Wq[N][K] e4m3fn bytes (row stride ldw_bytes), scale[N] fp32.
+ *   gemm_w8:  C[M][N] = scale[n] * sum_k fp32(Wq[n][k]) * fp32(x[m][k]) (+ residual), the twin of mm355_gemm_splitk_bf16: the SAME K slices
+ *         (mm355_gemm_w8_ws_floats == mm355_gemm_splitk_ws_floats), the same 64-wide K tiles and MFMA order, the bytes widened to bf16 in
+ *         registers (exact), so only the weight's storage differs.  The scale multiplies every fp32 partial where the GEMM launch stores it,
+ *         and the reduce launch of the bf16 form adds the slices: C = bf16(sum_s scale[n] * P_s (+ residual)) -- for power-of-two scales the
+ *         bits of mm355_gemm_splitk_bf16 on the dequantised weight, otherwise one fp32 rounding per slice away from scale[n] * sum_s P_s.
+ *         flags: MM355_GEMM_RESIDUAL | MM355_GEMM_OUT_F32.  A shape that is not split (workspace 0: e.g. the lm_head) and every fp32 output
+ *         run the same kernel as ONE slice that stores epilogue(scale[n] * P) straight into C; workspace may then be NULL.
+ *   gemm_w8_norm / gemm_w8_swiglu / gemm_w8_rope_append: the twins of mm355_gemm_splitk_norm_bf16 / _swiglu_bf16 / _rope_append_bf16 (same
+ *         operands, limits and workspaces; mm355_gemm_w8_swiglu_ws_floats == mm355_gemm_splitk_swiglu_ws_floats), the reduce launches shared
+ *         with them; a shape that is not split runs gemm_w8 + mm355_rmsnorm_fwd / mm355_swiglu_fwd / mm355_rope_kv_append inside the library.
+ *   Before any launch: fmt other than MM355_W8_E4M3, K % 64 != 0, ldw_bytes % 16 != 0, ldx % 8 != 0, a NULL scale, misaligned pointers or a
+ *   workspace that is too small: MM355_EINVAL.  M > 4096: MM355_EUNSUPPORTED (larger passes: mm355_dequant_w8_bf16 + the bf16 GEMMs).
+ * ------------------------------------------------------------------------------------------------ */
+int64_t mm355_gemm_w8_ws_floats(int64_t M, int64_t N, int64_t K);
+int mm355_gemm_w8(const mm355_bf16* x, int64_t ldx, const uint8_t* Wq, int64_t ldw_bytes, const float* scale, int fmt, void* C, int64_t ldc,
+                  int64_t M, int64_t N, int64_t K, const mm355_bf16* residual, int64_t ldr, uint32_t flags, float* workspace,
+                  int64_t workspace_floats, void* stream);
+int mm355_gemm_w8_norm(const mm355_bf16* x, int64_t ldx, const uint8_t* Wq, int64_t ldw_bytes, const float* scale, int fmt, mm355_bf16* C,
+                       int64_t M, int64_t N, int64_t K, const mm355_bf16* residual, int64_t ldr, const mm355_bf16* norm_w, float eps,
+                       mm355_bf16* Y, float* workspace, int64_t workspace_floats, void* stream);
+int64_t mm355_gemm_w8_swiglu_ws_floats(int64_t M, int64_t I, int64_t K);
+int mm355_gemm_w8_swiglu(const mm355_bf16* x, int64_t ldx, const uint8_t* Wq, int64_t ldw_bytes, const float* scale, int fmt, mm355_bf16* act,
+                         int64_t ld_act, int64_t M, int64_t I, int64_t K, float* workspace, int64_t workspace_floats, void* stream);
+int mm355_gemm_w8_rope_append(const mm355_bf16* x, int64_t ldx, const uint8_t* Wq, int64_t ldw_bytes, const float* scale, int fmt,
+                              mm355_bf16* qkv, int64_t ld_qkv, int64_t M, int64_t Hq, int64_t Hkv, int64_t d, int64_t K,
+                              const mm355_bf16* cos_t, const mm355_bf16* sin_t, const int32_t* positions, mm355_bf16* k_cache,
+                              mm355_bf16* v_cache, int64_t ld_kv, int64_t batch_stride_kv, float* workspace, int64_t workspace_floats,
+                              void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Elementwise: SwiGLU (HF LlamaMLP; K12), GELU (projector / vision_head), scaling helpers.

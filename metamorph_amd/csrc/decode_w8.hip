@@ -62,14 +62,6 @@ MM_DEV bool unit_live(const W8Args& a, const int (&rows)[4]) {
     else return rows[3] < a.N;
 }
 
-// four e4m3 bytes (k .. k+3) -> the packed bf16 pairs (k, k+1) and (k+2, k+3): exact
-MM_DEV void e4m3x4_to_bf16(uint32_t q, uint32_t& p01, uint32_t& p23) {
-    const mm_f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)q, false);
-    const mm_f32x2 b = __builtin_amdgcn_cvt_pk_f32_fp8((int)q, true);
-    p01 = __builtin_amdgcn_perm(__float_as_uint(a.y), __float_as_uint(a.x), 0x07060302u);
-    p23 = __builtin_amdgcn_perm(__float_as_uint(b.y), __float_as_uint(b.x), 0x07060302u);
-}
-
 // MODE 0: output (m, n) of the scaled sum v -- gemv_kernel's epilogue
 MM_DEV void plain_store(const W8Args& a, int m, int n, float v) {
     const uint32_t flags = a.flags;

@@ -14,53 +14,11 @@
 //   * workgroup -> tile map: bijective XCD remap (block b runs on XCD b % 8) then grouped raster so the
 //     blocks sharing an XCD's L2 walk neighbouring tiles.
 #include "gemm_common.h"
+#include "splitk.h"
 #include <type_traits>
 #include <cstdlib>
 
 namespace {
-
-// Shared epilogue: accumulators -> wave-private LDS slab -> row-contiguous 16-B stores with the fused epilogue.
-template <int TM, int TN, int FM, int FN>
-MM_DEV void gemm_epilogue(f32x4 (&acc)[FM][FN], const GemmArgs& a, unsigned char* smem, int m0, int n0, int wm, int wn, int wave, int lane) {
-    const int fr = lane & 15, fq = lane >> 4;
-    const int M = a.M, N = a.N;
-    constexpr int CPL = TN / 4;                          // columns handled by one lane per row
-    float* stg = (float*)smem + wave * (16 * TN);
-    const uint32_t fl = a.flags;
-    const int row_l = lane >> 2, col_l = (lane & 3) * CPL;
-    uint16_t* Cb = (uint16_t*)a.C;
-    float* Cf = (float*)a.C;
-    const bool vec_ok = ((a.ldc & 7) == 0) && (!(fl & MM355_GEMM_RESIDUAL) || (a.ldr & 7) == 0);
-#pragma unroll
-    for (int i = 0; i < FM; ++i) {
-        // the staging slab is private to this wave and the LDS executes one wave's instructions in order: a wave-level
-        // fence (no s_barrier) is all the write -> read -> next write hand-over needs; the caller has already made sure
-        // (block barrier) that nobody still reads the tile data this slab overlays
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int j = 0; j < FN; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) stg[(fq * 4 + r) * TN + j * 16 + fr] = acc[i][j][r];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        const int grow = m0 + wm * TM + i * 16 + row_l;
-        if (grow < M) {
-            const int64_t rr = (fl & MM355_GEMM_RESIDUAL) ? (a.res_mod > 0 ? (int64_t)(grow % a.res_mod) : (int64_t)grow) : 0;
-#pragma unroll
-            for (int j = 0; j < CPL / 8; ++j) {
-                const int c = n0 + wn * TN + col_l + j * 8;
-                if (c >= N) continue;
-                float v[8];
-                const f32x4 s0 = *(const f32x4*)(stg + row_l * TN + col_l + j * 8);
-                const f32x4 s1 = *(const f32x4*)(stg + row_l * TN + col_l + j * 8 + 4);
-                v[0] = s0.x; v[1] = s0.y; v[2] = s0.z; v[3] = s0.w;
-                v[4] = s1.x; v[5] = s1.y; v[6] = s1.z; v[7] = s1.w;
-                epi_store8(a, fl, vec_ok, grow, rr, c, v);
-            }
-        }
-    }
-}
 
 // Epilogue of the fused gate|up GEMM (mm355_gemm_swiglu_bf16): a wave's 64 tile columns are 32 gate channels followed by the SAME 32
 // up channels (the B tile is staged from two row ranges of the fused weight, see gemm_pp_tile<.., SWI>), so after the staging slab a
@@ -1137,6 +1095,44 @@ int splitk_slices(int64_t M, int64_t N, int64_t K) {
 }
 }  // namespace
 
+// ---- splitk.h: the slice count and the reduce launches, for this file and for gemm_w8.hip
+int mm_splitk_slices(int64_t M, int64_t N, int64_t K) { return splitk_slices(M, N, K); }
+
+int mm_splitk_reduce(const float* part, int slices, int64_t M, int64_t N, const mm355_bf16* residual, int64_t ldr, mm355_bf16* C, int64_t ldc,
+                     hipStream_t stream) {
+    const int64_t vecs = M * (N / 8);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<int64_t>((vecs + 255) / 256, 4096)), dim3(256), 0, stream, part, slices,
+                       (int)M, (int)N, (const uint16_t*)residual, ldr, (uint16_t*)C, ldc);
+    return mm_launch_status();
+}
+
+int mm_splitk_reduce_norm(const float* part, int slices, int64_t M, int64_t N, const mm355_bf16* residual, int64_t ldr, mm355_bf16* C,
+                          const mm355_bf16* norm_w, float eps, mm355_bf16* Y, hipStream_t stream) {
+    const int nv = (int)(N >> 3);
+#define RN(VPT) hipLaunchKernelGGL((splitk_reduce_norm_kernel<VPT>), dim3((unsigned)M), dim3(256), 0, stream, part, slices, (int)M, (int)N, \
+                                   (const uint16_t*)residual, ldr, (uint16_t*)C, N, (const uint16_t*)norm_w, (uint16_t*)Y, N, eps)
+    if (nv <= 256) RN(1); else if (nv <= 512) RN(2); else if (nv <= 1024) RN(4); else RN(8);
+#undef RN
+    return mm_launch_status();
+}
+
+int mm_splitk_reduce_swiglu(const float* part, int slices, int64_t M, int64_t I, mm355_bf16* act, int64_t ld_act, hipStream_t stream) {
+    const int64_t vecs = M * (I / 8);
+    hipLaunchKernelGGL(splitk_reduce_swiglu_kernel, dim3((unsigned)std::min<int64_t>((vecs + 255) / 256, 4096)), dim3(256), 0, stream, part, slices,
+                       (int)M, (int)I, (uint16_t*)act, ld_act);
+    return mm_launch_status();
+}
+
+int mm_splitk_reduce_rope_append(const float* part, int slices, int64_t M, int64_t Hq, int64_t Hkv, int64_t d, mm355_bf16* qkv, int64_t ld_qkv,
+                                 const mm355_bf16* cos_t, const mm355_bf16* sin_t, const int32_t* positions, mm355_bf16* k_cache,
+                                 mm355_bf16* v_cache, int64_t ld_kv, int64_t batch_stride_kv, hipStream_t stream) {
+    const int64_t work = (Hq + Hkv) * (d / 16) + Hkv * d / 8;
+    hipLaunchKernelGGL(splitk_reduce_rope_append_kernel, dim3((unsigned)((work + 255) / 256), (unsigned)M), dim3(256), 0, stream, part, slices,
+                       (int)M, (int)Hq, (int)Hkv, (int)d, (uint16_t*)qkv, ld_qkv, (const uint16_t*)cos_t, (const uint16_t*)sin_t, positions,
+                       (uint16_t*)k_cache, (uint16_t*)v_cache, ld_kv, batch_stride_kv);
+    return mm_launch_status();
+}
+
 extern "C" int64_t mm355_gemm_splitk_ws_floats(int64_t M, int64_t N, int64_t K) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
     const int S = splitk_slices(M, N, K);
@@ -1192,10 +1188,7 @@ extern "C" int mm355_gemm_splitk_bf16(const mm355_bf16* A, int64_t lda, const mm
     int slices = 0;
     const int rc = splitk_partials(A, lda, B, ldb, M, N, K, S, workspace, workspace_floats, (hipStream_t)stream, slices);
     if (rc != MM355_OK) return rc;
-    const int64_t vecs = M * (N / 8);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<int64_t>((vecs + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)workspace, slices, (int)M, (int)N, (const uint16_t*)residual, ldr, (uint16_t*)C, ldc);
-    return mm_launch_status();
+    return mm_splitk_reduce(workspace, slices, M, N, residual, ldr, C, ldc, (hipStream_t)stream);
 }
 
 // ---- split projection + the launch that follows it (see the fused reduce kernels above).  A shape that would not be split runs the plain
@@ -1216,11 +1209,7 @@ extern "C" int mm355_gemm_splitk_norm_bf16(const mm355_bf16* A, int64_t lda, con
     int slices = 0;
     const int rc = splitk_partials(A, lda, B, ldb, M, N, K, S, workspace, workspace_floats, (hipStream_t)stream, slices);
     if (rc != MM355_OK) return rc;
-#define RN(VPT) hipLaunchKernelGGL((splitk_reduce_norm_kernel<VPT>), dim3((unsigned)M), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, slices, \
-                                   (int)M, (int)N, (const uint16_t*)residual, ldr, (uint16_t*)C, N, (const uint16_t*)norm_w, (uint16_t*)Y, N, eps)
-    if (nv <= 256) RN(1); else if (nv <= 512) RN(2); else if (nv <= 1024) RN(4); else RN(8);
-#undef RN
-    return mm_launch_status();
+    return mm_splitk_reduce_norm(workspace, slices, M, N, residual, ldr, C, norm_w, eps, Y, (hipStream_t)stream);
 }
 
 extern "C" int64_t mm355_gemm_splitk_swiglu_ws_floats(int64_t M, int64_t I, int64_t K) {
@@ -1245,10 +1234,7 @@ extern "C" int mm355_gemm_splitk_swiglu_bf16(const mm355_bf16* X, int64_t ldx, c
     int slices = 0;
     const int rc = splitk_partials(X, ldx, Wgu, ldw, M, N, K, S, workspace, workspace_floats, (hipStream_t)stream, slices);
     if (rc != MM355_OK) return rc;
-    const int64_t vecs = M * (I / 8);
-    hipLaunchKernelGGL(splitk_reduce_swiglu_kernel, dim3((unsigned)std::min<int64_t>((vecs + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)workspace, slices, (int)M, (int)I, (uint16_t*)act, ld_act);
-    return mm_launch_status();
+    return mm_splitk_reduce_swiglu(workspace, slices, M, I, act, ld_act, (hipStream_t)stream);
 }
 
 extern "C" int mm355_gemm_splitk_rope_append_bf16(const mm355_bf16* X, int64_t ldx, const mm355_bf16* Wqkv, int64_t ldw, mm355_bf16* qkv, int64_t ld_qkv,
@@ -1269,11 +1255,8 @@ extern "C" int mm355_gemm_splitk_rope_append_bf16(const mm355_bf16* X, int64_t l
     int slices = 0;
     const int rc = splitk_partials(X, ldx, Wqkv, ldw, M, N, K, S, workspace, workspace_floats, (hipStream_t)stream, slices);
     if (rc != MM355_OK) return rc;
-    const int64_t work = (Hq + Hkv) * (d / 16) + Hkv * d / 8;
-    hipLaunchKernelGGL(splitk_reduce_rope_append_kernel, dim3((unsigned)((work + 255) / 256), (unsigned)M), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)workspace, slices, (int)M, (int)Hq, (int)Hkv, (int)d, (uint16_t*)qkv, ld_qkv, (const uint16_t*)cos_t,
-                       (const uint16_t*)sin_t, positions, (uint16_t*)k_cache, (uint16_t*)v_cache, ld_kv, batch_stride_kv);
-    return mm_launch_status();
+    return mm_splitk_reduce_rope_append(workspace, slices, M, Hq, Hkv, d, qkv, ld_qkv, cos_t, sin_t, positions, k_cache, v_cache, ld_kv,
+                                        batch_stride_kv, (hipStream_t)stream);
 }
 
 extern "C" int mm355_gemm_num_variants(void) { return 14; }

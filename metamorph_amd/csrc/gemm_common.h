@@ -1,5 +1,6 @@
 // The GEMM argument block and the fused store of eight adjacent output columns (bias / GELU / residual / accumulate / fp32 or bf16
-// output), shared by every kernel of gemm_bf16.hip so that all of them round exactly the same way.
+// output) with the accumulator epilogue around it, shared by every kernel of gemm_bf16.hip and gemm_w8.hip so that all of them round exactly
+// the same way.
 #pragma once
 #include "mm355_common.h"
 
@@ -99,6 +100,49 @@ MM_DEV void epi_store8(const GemmArgs& a, const uint32_t fl, const bool vec_ok, 
         }
     } else {
         epi_scalar(a.C, a.ldc, a.bias, a.res, a.ldr, fl, N, grow, c, rr, v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
+    }
+}
+
+// Shared epilogue (every gemm_nt_kernel form and the w8 twin in gemm_w8.hip): accumulators -> wave-private LDS slab -> row-contiguous 16-B stores with the fused epilogue.
+template <int TM, int TN, int FM, int FN>
+MM_DEV void gemm_epilogue(f32x4 (&acc)[FM][FN], const GemmArgs& a, unsigned char* smem, int m0, int n0, int wm, int wn, int wave, int lane) {
+    const int fr = lane & 15, fq = lane >> 4;
+    const int M = a.M, N = a.N;
+    constexpr int CPL = TN / 4;                          // columns handled by one lane per row
+    float* stg = (float*)smem + wave * (16 * TN);
+    const uint32_t fl = a.flags;
+    const int row_l = lane >> 2, col_l = (lane & 3) * CPL;
+    uint16_t* Cb = (uint16_t*)a.C;
+    float* Cf = (float*)a.C;
+    const bool vec_ok = ((a.ldc & 7) == 0) && (!(fl & MM355_GEMM_RESIDUAL) || (a.ldr & 7) == 0);
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+        // the staging slab is private to this wave and the LDS executes one wave's instructions in order: a wave-level
+        // fence (no s_barrier) is all the write -> read -> next write hand-over needs; the caller has already made sure
+        // (block barrier) that nobody still reads the tile data this slab overlays
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int j = 0; j < FN; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) stg[(fq * 4 + r) * TN + j * 16 + fr] = acc[i][j][r];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const int grow = m0 + wm * TM + i * 16 + row_l;
+        if (grow < M) {
+            const int64_t rr = (fl & MM355_GEMM_RESIDUAL) ? (a.res_mod > 0 ? (int64_t)(grow % a.res_mod) : (int64_t)grow) : 0;
+#pragma unroll
+            for (int j = 0; j < CPL / 8; ++j) {
+                const int c = n0 + wn * TN + col_l + j * 8;
+                if (c >= N) continue;
+                float v[8];
+                const f32x4 s0 = *(const f32x4*)(stg + row_l * TN + col_l + j * 8);
+                const f32x4 s1 = *(const f32x4*)(stg + row_l * TN + col_l + j * 8 + 4);
+                v[0] = s0.x; v[1] = s0.y; v[2] = s0.z; v[3] = s0.w;
+                v[4] = s1.x; v[5] = s1.y; v[6] = s1.z; v[7] = s1.w;
+                epi_store8(a, fl, vec_ok, grow, rr, c, v);
+            }
+        }
     }
 }
 

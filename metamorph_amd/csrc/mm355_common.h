@@ -43,6 +43,15 @@ MM_DEV u32x4 pack8(const float* f) {
     return v;
 }
 
+// four e4m3 bytes (k .. k+3) -> the packed bf16 pairs (k, k+1) and (k+2, k+3): exact (e4m3 -> fp32 is exact and its upper 16 bits ARE the
+// bf16 value).  Shared by the w8 GEMVs (decode_w8.hip) and the w8 GEMM (gemm_w8.hip).
+MM_DEV void e4m3x4_to_bf16(uint32_t q, uint32_t& p01, uint32_t& p23) {
+    const mm_f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)q, false);
+    const mm_f32x2 b = __builtin_amdgcn_cvt_pk_f32_fp8((int)q, true);
+    p01 = __builtin_amdgcn_perm(__float_as_uint(a.y), __float_as_uint(a.x), 0x07060302u);
+    p23 = __builtin_amdgcn_perm(__float_as_uint(b.y), __float_as_uint(b.x), 0x07060302u);
+}
+
 MM_DEV float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -37,7 +37,10 @@ VARIANTS = {"fuse_swiglu": True, "fuse_rope": True, "fuse_swiglu_bwd": True, "de
             "decode_wide_fused": True, "decode_wide_gu_gemv": True,
             # the prompt pass of ONE sequence (a few hundred rows): the same reduce launches (RoPE + the K / V rows straight into the cache, both
             # RMSNorms), attention reading K / V from the cache rows -- same bits as the prefill_splitk pass, five launches per layer less
-            "prefill_fused": True}
+            "prefill_fused": True,
+            # quantised layers (quantize_decoder_): projections of the prompt pass and of decode steps of more than 16 sequences on the w8
+            # split-K GEMM (mm355_gemm_w8*: the weight bytes streamed once); off: every such projection through the W8Scratch route
+            "w8_gemm": True}
 
 
 def set_variant(name, value):
@@ -799,7 +802,7 @@ def decoder_prefill(x, layers, meta, cache, row=0):
         return x
     for i, layer in enumerate(layers):
         params_ready(layer)
-        w8_materialize(layer)                                 # (a quantised layer: its weights dequantised into the shared scratch, see W8Scratch)
+        w8_materialize(layer)                                 # (a quantised layer: ALL four projections dequantised into the shared scratch, see W8Scratch -- a one-sequence prompt gets here once q|k|v is no longer split, 960 rows at 8B widths)
         x, saved = decoder_layer_forward(x, layer, meta)
         qkv = saved[0]
         if B == 1:
@@ -828,46 +831,59 @@ def _prefill_layers_fused(x, layers, meta, cache, row, ident):
     n1 = None
     for i, layer in enumerate(layers):
         params_ready(layer)
-        w8_materialize(layer)
+        rec = getattr(layer, "w8", None)
+        on8 = w8_route(layer, L, gu_rows=PROMPT_GU_SPLITK_ROWS)   # (a quantised layer: these projections on the w8 GEMM, the rest dequantised)
         att, mlp = layer.self_attn, layer.mlp
-        wqkv = fused_weight([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight])
-        wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
         if n1 is None:
             n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
         kc, vc = cache.k[i, row], cache.v[i, row]                             # [max_len, width]
         rows_k = kc.as_strided((L, kc.shape[0], kc.shape[1]), (0, kc.stride(0), 1))
         rows_v = vc.as_strided((L, vc.shape[0], vc.shape[1]), (0, vc.stride(0), 1))
-        qkv = ops.gemm_splitk_rope_append(n1, wqkv, meta.Hq, meta.Hkv, meta.d, meta.cos, meta.sin, ident, rows_k, rows_v)
+        qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), ops.gemm_w8_rope_append,
+                    ops.gemm_splitk_rope_append, n1, meta.Hq, meta.Hkv, meta.d, meta.cos, meta.sin, ident, rows_k, rows_v)
         o, _ = ops.attn_fwd(qkv[:, :nq], kc[:L], vc[:L], 1, L, meta.Hq, meta.Hkv, meta.d, meta.scale, True, meta.seqlens)
-        x2, n2 = ops.gemm_splitk_norm(o, att.o_proj.weight, layer.post_attention_layernorm.weight, meta.eps, residual=x)
-        if VARIANTS["fuse_swiglu"] and ops.gemm_swiglu_supported(n2, wgu, meta.I):
-            _, act = ops.gemm_swiglu(n2, wgu, meta.I)
-        elif L <= PROMPT_GU_SPLITK_ROWS:
-            act = ops.gemm_splitk_swiglu(n2, wgu, meta.I)
+        x2, n2 = _proj(on8, rec, "o", (att.o_proj.weight,), ops.gemm_w8_norm, ops.gemm_splitk_norm, o,
+                       layer.post_attention_layernorm.weight, meta.eps, residual=x)
+        if "gu" in on8:
+            act = ops.gemm_w8_swiglu(n2, *rec.gu, meta.I)
         else:
-            act = ops.swiglu_fwd(ops.gemm(n2, wgu), meta.I)
+            wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
+            if VARIANTS["fuse_swiglu"] and ops.gemm_swiglu_supported(n2, wgu, meta.I):
+                _, act = ops.gemm_swiglu(n2, wgu, meta.I)
+            elif L <= PROMPT_GU_SPLITK_ROWS:
+                act = ops.gemm_splitk_swiglu(n2, wgu, meta.I)
+            else:
+                act = ops.swiglu_fwd(ops.gemm(n2, wgu), meta.I)
         if i + 1 < len(layers):
             params_ready(layers[i + 1])
-            x, n1 = ops.gemm_splitk_norm(act, mlp.down_proj.weight, layers[i + 1].input_layernorm.weight, meta.eps, residual=x2)
+            x, n1 = _proj(on8, rec, "down", (mlp.down_proj.weight,), ops.gemm_w8_norm, ops.gemm_splitk_norm, act,
+                          layers[i + 1].input_layernorm.weight, meta.eps, residual=x2)
         else:
-            x = ops.gemm_splitk(act, mlp.down_proj.weight, residual=x2)
+            x = _proj(on8, rec, "down", (mlp.down_proj.weight,), ops.gemm_w8, ops.gemm_splitk, act, residual=x2)
     return x
 
 
 class W8Scratch:
-    """ONE layer's four fused projections as bf16, shared by every quantised layer of a model: the routes that have no w8 kernel (the prompt
-    pass, decode steps of more than 16 rows) dequantise the layer they are about to run into it and take their existing bf16 GEMMs from
-    there.  Correct and not fast: every layer costs four dequant launches and a write + read of its bf16 weights on top of the GEMMs
-    (0.44 GB at LLaMA-3-8B widths); a w8 GEMM is future work."""
+    """ONE layer's fused projections as bf16, shared by every quantised layer of a model: a projection whose route has no w8 kernel is
+    dequantised into it (one mm355_dequant_w8_bf16 launch, a write + read of its bf16 weights on top of the GEMM) and takes the existing bf16
+    GEMM from there.  Correct and not fast.  Since mm355_gemm_w8* that is: the batched prompt pass of all sequences at once
+    (decoder_layer_forward), passes of more than 4096 rows, the prompt pass's gate|up above PROMPT_GU_SPLITK_ROWS rows (the ping-pong
+    gemm_swiglu), every projection at a row count where the split-K GEMM does not split it (W8_GEMM_UNSPLIT_MAX_ROWS: at 8B widths a
+    one-sequence prompt's q|k|v beyond 960 rows -- decoder_prefill then runs the WHOLE pass on this route; any projection too narrow
+    to be split), and everything while VARIANTS["w8_gemm"] is off.  A buffer is allocated when
+    its projection first takes this route: `bufs` stays None on a model whose steps all run on the bytes."""
 
     def __init__(self):
         self.bufs = None
 
-    def views(self, rec):
-        shapes = [tuple(getattr(rec, n)[0].shape) for n in W8Layer.NAMES]
-        if self.bufs is None or [tuple(b.shape) for b in self.bufs] != shapes:
-            self.bufs = [torch.empty(s, device=rec.qkv[0].device, dtype=BF16) for s in shapes]
-        return self.bufs
+    def view(self, rec, name):
+        if self.bufs is None:
+            self.bufs = {}
+        shape = tuple(getattr(rec, name)[0].shape)
+        buf = self.bufs.get(name)
+        if buf is None or tuple(buf.shape) != shape:
+            buf = self.bufs[name] = torch.empty(shape, device=rec.qkv[0].device, dtype=BF16)
+        return buf
 
 
 class W8Layer:
@@ -894,11 +910,13 @@ class W8Layer:
                     p.data = p.data.new_empty((0, p.shape[1]))
                     p.requires_grad_(False)
 
-    def materialize(self):
-        """This layer's weights as bf16 for a route without w8 kernels (see W8Scratch).  A layer that kept its bf16 parameters runs on them."""
+    def materialize(self, names=NAMES):
+        """The projections `names` of this layer as bf16 for a route without w8 kernels (see W8Scratch), one matrix at a time: a projection
+        that runs on its bytes is not dequantised.  A layer that kept its bf16 parameters runs on them."""
         if not self.released:
             return
-        for n, buf in zip(self.NAMES, self.scratch.views(self)):
+        for n in names:
+            buf = self.scratch.view(self, n)
             ops.dequant_w8(*getattr(self, n), out=buf)
             off = 0
             for p, rows in zip(self.params[n], self.rows[n]):
@@ -918,6 +936,54 @@ def w8_materialize(layer):
     rec = getattr(layer, "w8", None)
     if rec is not None:
         rec.materialize()
+
+
+# Which projection of a quantised layer takes the w8 GEMM up to how many rows (the rest: W8Scratch), from profiles/decode_w8_wide.json
+# (tools/bench_wide_w8.py).  "split": row counts at which the split-K GEMM cuts the projection into K slices -- the
+# captured step of 17 / 32 / 64 sequences runs 2.3 - 2.6 x faster than on the scratch route and every split launch is ahead of
+# dequantise + bf16 GEMM, so these go to the w8 GEMM up to its limit of 4096 rows.  "unsplit": row counts at which it does not (at 8B widths
+# q|k|v beyond ~960 rows, o and down beyond ~1500, gate|up beyond ~200; any small projection) -- the w8 kernel then runs as one slice of
+# 64 x 128 tiles against the large-tile bf16 kernels on the dequantised weight: that pair is in the
+# tool's per-launch table (w8 against dequantise + bf16 GEMM at 512 / 1024 / 2048 rows), but no MI355X run of it is recorded with this change
+# (measured: not yet), so unsplit projections stay on the scratch route (0 rows).  decoder_prefill leaves the per-projection loop once q|k|v is
+# no longer split: a one-sequence prompt of 8B widths runs q|k|v, o and down on their bytes up to 960 rows (gate|up up to
+# PROMPT_GU_SPLITK_ROWS) and WHOLLY on the scratch route beyond 960 rows.
+W8_GEMM_MAX_ROWS = {"qkv": 4096, "o": 4096, "gu": 4096, "down": 4096}
+W8_GEMM_UNSPLIT_MAX_ROWS = {"qkv": 0, "o": 0, "gu": 0, "down": 0}
+
+
+def w8_on_gemm(layer, rows, gu_rows=None):
+    """The projections of `layer` that run on their e4m3 bytes at `rows` rows (mm355_gemm_w8*), as a set of W8Layer.NAMES.  gu_rows: the
+    caller's own row limit for gate|up on a GEMM of 64 x 128 tiles (the prompt pass: PROMPT_GU_SPLITK_ROWS).  Empty for a layer that is not
+    quantised."""
+    rec = getattr(layer, "w8", None)
+    on8 = set()
+    if rec is not None and VARIANTS["w8_gemm"]:
+        for n in W8Layer.NAMES:
+            N, K = getattr(rec, n)[0].shape
+            cap = (W8_GEMM_MAX_ROWS if ops.gemm_splitk_splits(rows, N, K) else W8_GEMM_UNSPLIT_MAX_ROWS)[n]
+            if n == "gu" and gu_rows is not None:
+                cap = min(cap, gu_rows)
+            if rows <= cap and ops.gemm_w8_supported(rows, K):
+                on8.add(n)
+    return frozenset(on8)
+
+
+def w8_route(layer, rows, gu_rows=None):
+    """w8_on_gemm(), and the other projections of a quantised layer dequantised into the scratch buffer here."""
+    on8 = w8_on_gemm(layer, rows, gu_rows)
+    rec = getattr(layer, "w8", None)
+    if rec is not None:
+        rec.materialize([n for n in W8Layer.NAMES if n not in on8])
+    return on8
+
+
+def _proj(on8, rec, name, weights, w8_op, bf16_op, x, *args, **kw):
+    """One projection of a layer through the w8 op on its e4m3 bytes where w8_route put it there, else through the bf16 op on the (fused)
+    bf16 weight: the two ops of a pair take the same arguments after the weight."""
+    if name in on8:
+        return w8_op(x, *getattr(rec, name), *args, **kw)
+    return bf16_op(x, weights[0] if len(weights) == 1 else fused_weight(weights), *args, **kw)
 
 
 def _decode_rows16_w8(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound):
@@ -992,7 +1058,8 @@ def _decode_rows_gemm(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_
     i.e. the 15 GB read once per chunk).  The GEMV kernels hold one 16-row MFMA operand; beyond it the projections take the split-K GEMM of
     the prompt pass (mm355_gemm_splitk_bf16: 64 x 128 tiles x K slices -- at 32 rows a weight-streaming problem with ~3 workgroups per CU),
     attention per row at its own length; RoPE + cache append, the two RMSNorms and SwiGLU ride in the reduce launches of the split projections
-    (VARIANTS["decode_wide_fused"]; as launches of their own -- thirteen per layer instead of nine -- when off: same bits)."""
+    (VARIANTS["decode_wide_fused"]; as launches of their own -- thirteen per layer instead of nine -- when off: same bits).  A quantised layer
+    takes the same launches on mm355_gemm_w8* (w8_route: per projection; the bytes are streamed once, nothing is dequantised)."""
     nq = meta.Hq * meta.d
     if VARIANTS["decode_wide_fused"] and meta.d % 16 == 0:
         # what follows a split projection rides in its reduce launch (mm355_gemm_splitk_{rope_append,norm,swiglu}_bf16): 9 launches per layer
@@ -1000,39 +1067,45 @@ def _decode_rows_gemm(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_
         gu_gemv = VARIANTS["decode_wide_gu_gemv"] and x.shape[0] <= 32 and meta.I % 2 == 0 and ops.gemv_rows32_units(meta.I // 2)
         for i, layer in enumerate(layers):
             params_ready(layer)
-            w8_materialize(layer)                             # (17 rows and more on quantised layers: the scratch route, see W8Scratch)
+            rec = getattr(layer, "w8", None)
+            on8 = w8_route(layer, x.shape[0])                 # (a quantised layer: these projections on the w8 GEMM, the rest dequantised)
             att, mlp = layer.self_attn, layer.mlp
-            wqkv = fused_weight([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight])
-            wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
             if n1 is None:
                 n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
-            qkv = ops.gemm_splitk_rope_append(n1, wqkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
+            qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), ops.gemm_w8_rope_append,
+                        ops.gemm_splitk_rope_append, n1, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
             o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
-            x2, n2 = ops.gemm_splitk_norm(o, att.o_proj.weight, layer.post_attention_layernorm.weight, meta.eps, residual=x)
-            if gu_gemv:
-                act = ops.gemv_swiglu(n2, wgu, meta.I)        # up to 32 rows: the weight stream of the 16-row kernel, a second x row group on its fragments
+            x2, n2 = _proj(on8, rec, "o", (att.o_proj.weight,), ops.gemm_w8_norm, ops.gemm_splitk_norm, o,
+                           layer.post_attention_layernorm.weight, meta.eps, residual=x)
+            if "gu" in on8:
+                act = ops.gemm_w8_swiglu(n2, *rec.gu, meta.I)  # (17 - 32 rows too: the w8 GEMV has no second row group)
             else:
-                act = ops.gemm_splitk_swiglu(n2, wgu, meta.I)
+                wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
+                if gu_gemv:
+                    act = ops.gemv_swiglu(n2, wgu, meta.I)    # up to 32 rows: the weight stream of the 16-row kernel, a second x row group on its fragments
+                else:
+                    act = ops.gemm_splitk_swiglu(n2, wgu, meta.I)
             if i + 1 < len(layers):
                 params_ready(layers[i + 1])                   # (its input norm weight is read by this layer's last launch)
-                x, n1 = ops.gemm_splitk_norm(act, mlp.down_proj.weight, layers[i + 1].input_layernorm.weight, meta.eps, residual=x2)
+                x, n1 = _proj(on8, rec, "down", (mlp.down_proj.weight,), ops.gemm_w8_norm, ops.gemm_splitk_norm, act,
+                              layers[i + 1].input_layernorm.weight, meta.eps, residual=x2)
             else:
-                x = ops.gemm_splitk(act, mlp.down_proj.weight, residual=x2)
+                x = _proj(on8, rec, "down", (mlp.down_proj.weight,), ops.gemm_w8, ops.gemm_splitk, act, residual=x2)
         return x
     for i, layer in enumerate(layers):
         params_ready(layer)
-        w8_materialize(layer)
+        rec = getattr(layer, "w8", None)
+        on8 = w8_route(layer, x.shape[0])
         att, mlp = layer.self_attn, layer.mlp
-        wqkv = fused_weight([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight])
-        wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
         n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
-        qkv = ops.gemm_splitk(n1, wqkv)
+        qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), ops.gemm_w8, ops.gemm_splitk, n1)
         ops.rope_kv_append_(qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
         o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
-        x2 = ops.gemm_splitk(o, att.o_proj.weight, residual=x)
+        x2 = _proj(on8, rec, "o", (att.o_proj.weight,), ops.gemm_w8, ops.gemm_splitk, o, residual=x)
         n2 = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
-        act = ops.swiglu_fwd(ops.gemm_splitk(n2, wgu), meta.I)
-        x = ops.gemm_splitk(act, mlp.down_proj.weight, residual=x2)
+        gu = _proj(on8, rec, "gu", (mlp.gate_proj.weight, mlp.up_proj.weight), ops.gemm_w8, ops.gemm_splitk, n2)
+        act = ops.swiglu_fwd(gu, meta.I)
+        x = _proj(on8, rec, "down", (mlp.down_proj.weight,), ops.gemm_w8, ops.gemm_splitk, act, residual=x2)
     return x
 
 

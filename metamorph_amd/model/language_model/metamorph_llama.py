@@ -591,8 +591,13 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
     def quantize_decoder_(self, fmt="fp8_e4m3", lm_head=False, pow2_scales=False, keep_bf16=False):
         """Quantise the fused projections of every decoder layer (q|k|v, o, gate|up, down; on request the lm_head) to weight-only FP8:
         e4m3 bytes + one fp32 scale per output row (ops.quantize_w8).  Decode steps of up to 16 sequences then stream half the bytes
-        (mm355_gemv*_w8); the prompt pass and larger batches run the bf16 GEMMs on one layer's weights dequantised into a shared scratch
-        buffer (functional.W8Scratch: correct, not fast).  The bf16 storage of the quantised projections is released unless keep_bf16;
+        (mm355_gemv*_w8); larger batches and the prompt pass of one sequence stream the same bytes through the w8 split-K GEMM
+        (mm355_gemm_w8*, functional.w8_route) for every projection that the split-K GEMM splits at that row count -- at 8B widths a
+        prompt of up to 960 rows (its gate|up up to functional.PROMPT_GU_SPLITK_ROWS), a decode step of up to 192 sequences.  What is left dequantises one projection at a time into a
+        shared scratch buffer and runs the bf16 GEMMs (functional.W8Scratch: correct, not fast): projections at row counts where they are not
+        split (a one-sequence prompt of more than 960 rows at 8B widths runs wholly there), the prompt pass's gate|up above
+        functional.PROMPT_GU_SPLITK_ROWS rows, the batched prompt pass of all sequences at once, passes of more than 4096 rows.  The bf16
+        storage of the quantised projections is released unless keep_bf16;
         embed_tokens, norms, vision tower, projector and vision head stay bf16.  The model ends in eval mode: generation only."""
         if fmt not in ops.W8_FORMATS:
             raise ValueError(f"quantize_decoder_: unknown format {fmt!r} (supported: {sorted(ops.W8_FORMATS)})")
@@ -625,11 +630,14 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         return super().state_dict(*args, **kwargs)
 
     def _lm_head_w8(self, hid):
-        """fp32 logits of the normed rows on the quantised lm_head: up to 16 rows mm355_gemv_w8, more rows the bf16 GEMM on the dequantised
-        weight (a temporary of the lm_head's size: correct, not fast)."""
+        """fp32 logits of the normed rows on the quantised lm_head: up to 16 rows mm355_gemv_w8, more rows mm355_gemm_w8 (one slice, fp32
+        output); beyond its limits (more than 4096 rows, a hidden size that is no multiple of 64) the bf16 GEMM on the dequantised weight, a
+        temporary of the lm_head's size."""
         q, scale = self.w8_lm_head
         if hid.shape[0] <= 16:
             return ops.gemv_w8(hid, q, scale, out=torch.empty((hid.shape[0], q.shape[0]), device=hid.device, dtype=torch.float32))
+        if F.VARIANTS["w8_gemm"] and ops.gemm_w8_supported(hid.shape[0], hid.shape[1]):
+            return ops.gemm_w8(hid, q, scale, out_f32=True)
         return ops.gemm(hid, ops.dequant_w8(q, scale), out_f32=True)
 
     # ------------------------------------------------------------------ cached decode (row N1)

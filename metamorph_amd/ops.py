@@ -301,7 +301,7 @@ def _w8_operands(wq, scale, K):
 
 
 def dequant_w8(wq, scale, out=None):
-    """bf16 [N, K] = RNE(fp32(wq) * scale[:, None]) (mm355_dequant_w8_bf16): the operand of the bf16 GEMMs on the routes that have no w8 kernel."""
+    """bf16 [N, K] = RNE(fp32(wq) * scale[:, None]) (mm355_dequant_w8_bf16): the operand of the bf16 GEMMs on the routes gemm_w8* do not take."""
     _chk_dev(wq, scale, out)
     pw, N, ldw = _w8_operands(wq, scale, wq.shape[1])
     K = wq.shape[1]
@@ -363,6 +363,84 @@ def gemv_rope_append_w8(x, wq, scale, Hq, Hkv, d, cos, sin, positions, k_cache, 
                                               _p(norm_w), float(eps), cos.data_ptr(), sin.data_ptr(), positions.data_ptr(),
                                               k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(1), k_cache.stride(0), _stream()),
                "mm355_gemv_rope_append_w8")
+    return out
+
+
+def gemm_w8_supported(M, K):
+    """mm355_gemm_w8* take this problem (whole 64-wide K tiles, at most 4096 rows)."""
+    return K % 64 == 0 and 0 < M <= 4096
+
+
+def gemm_w8(x, wq, scale, residual=None, out=None, out_f32=False):
+    """out[M, N] = scale[n] * x[M, K] . fp32(wq[N, K])^T (+ residual): gemm_splitk() over e4m3 weight bytes (mm355_gemm_w8) -- the same K
+    slices and summation order, the bytes widened in registers.  out_f32 (or an fp32 `out`): fp32 output in one slice (the lm_head)."""
+    _chk_dev(x, wq, scale, residual, out)
+    px, M, K, ldx = _rows2d(x)
+    assert x.dtype == BF16
+    pw, N, ldw = _w8_operands(wq, scale, K)
+    if out is None:
+        out = torch.empty((M, N), device=x.device, dtype=torch.float32 if out_f32 else BF16)
+    po, Mo, No, ldc = _rows2d(out)
+    assert (Mo, No) == (M, N) and out.dtype in (BF16, torch.float32)
+    flags = GEMM_OUT_F32 if out.dtype == torch.float32 else 0
+    pr, ldr = 0, 0
+    if residual is not None:
+        pr, Mr, Nr, ldr = _rows2d(residual)
+        assert (Mr, Nr) == (M, N) and residual.dtype == BF16
+        flags |= GEMM_RESIDUAL
+    n_ws = 0 if flags & GEMM_OUT_F32 else int(_L().mm355_gemm_w8_ws_floats(M, N, K))
+    ws = _splitk_ws(n_ws, x.device)
+    _lib.check(_L().mm355_gemm_w8(px, ldx, pw, ldw, scale.data_ptr(), W8_E4M3, po, ldc, M, N, K, pr, ldr, flags, ws.data_ptr(), n_ws, _stream()),
+               f"mm355_gemm_w8 M={M} N={N} K={K}")
+    return out
+
+
+def gemm_w8_norm(x, wq, scale, norm_w, eps, residual=None):
+    """gemm_splitk_norm() over e4m3 weight bytes (mm355_gemm_w8_norm): (c, y)."""
+    _chk_dev(x, wq, scale, norm_w, residual)
+    px, M, K, ldx = _rows2d(x)
+    pw, N, ldw = _w8_operands(wq, scale, K)
+    assert x.dtype == BF16 and norm_w.numel() == N
+    c = torch.empty((M, N), device=x.device, dtype=BF16)
+    y = torch.empty((M, N), device=x.device, dtype=BF16)
+    pr, ldr = 0, 0
+    if residual is not None:
+        pr, Mr, Nr, ldr = _rows2d(residual)
+        assert (Mr, Nr) == (M, N)
+    n_ws = int(_L().mm355_gemm_w8_ws_floats(M, N, K))
+    ws = _splitk_ws(n_ws, x.device)
+    _lib.check(_L().mm355_gemm_w8_norm(px, ldx, pw, ldw, scale.data_ptr(), W8_E4M3, c.data_ptr(), M, N, K, pr, ldr, norm_w.data_ptr(), float(eps),
+                                       y.data_ptr(), ws.data_ptr(), n_ws, _stream()), f"mm355_gemm_w8_norm M={M} N={N} K={K}")
+    return c, y
+
+
+def gemm_w8_swiglu(x, wq, scale, I):
+    """gemm_splitk_swiglu() over the e4m3 bytes of the fused gate|up weight (mm355_gemm_w8_swiglu)."""
+    _chk_dev(x, wq, scale)
+    px, M, K, ldx = _rows2d(x)
+    pw, N, ldw = _w8_operands(wq, scale, K)
+    assert N == 2 * I and x.dtype == BF16
+    act = torch.empty((M, I), device=x.device, dtype=BF16)
+    n_ws = int(_L().mm355_gemm_w8_swiglu_ws_floats(M, I, K))
+    ws = _splitk_ws(n_ws, x.device)
+    _lib.check(_L().mm355_gemm_w8_swiglu(px, ldx, pw, ldw, scale.data_ptr(), W8_E4M3, act.data_ptr(), act.stride(0), M, I, K, ws.data_ptr(), n_ws,
+                                         _stream()), f"mm355_gemm_w8_swiglu M={M} I={I} K={K}")
+    return act
+
+
+def gemm_w8_rope_append(x, wq, scale, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache):
+    """gemm_splitk_rope_append() over the e4m3 bytes of the fused q|k|v weight (mm355_gemm_w8_rope_append)."""
+    _chk_dev(x, wq, scale, cos, sin, positions, k_cache, v_cache)
+    px, M, K, ldx = _rows2d(x)
+    pw, N, ldw = _w8_operands(wq, scale, K)
+    assert x.dtype == BF16 and N == (Hq + 2 * Hkv) * d and positions.dtype == torch.int32
+    assert k_cache.stride() == v_cache.stride() and k_cache.stride(2) == 1
+    out = torch.empty((M, N), device=x.device, dtype=BF16)
+    n_ws = int(_L().mm355_gemm_w8_ws_floats(M, N, K))
+    ws = _splitk_ws(n_ws, x.device)
+    _lib.check(_L().mm355_gemm_w8_rope_append(px, ldx, pw, ldw, scale.data_ptr(), W8_E4M3, out.data_ptr(), out.stride(0), M, Hq, Hkv, d, K,
+                                              cos.data_ptr(), sin.data_ptr(), positions.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                                              k_cache.stride(1), k_cache.stride(0), ws.data_ptr(), n_ws, _stream()), "mm355_gemm_w8_rope_append")
     return out
 
 
