@@ -413,6 +413,42 @@ int mm355_gemm_w8_rope_append(const mm355_bf16* x, int64_t ldx, const uint8_t* W
                               void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Cached decode over an FP8 KV cache (csrc/decode_kv8.hip).  fmt MM355_KV8_E4M3: one cached head-row -- the d post-RoPE bf16 values of one
+ * KV head of one token -- is d OCP e4m3fn bytes plus ONE fp32 scale: scale = the smallest power of two with amax / scale <= 448 (a row of
+ * zeros: 1), q[c] = RNE_e4m3(x[c] / scale) (exact shift, nothing saturates, subnormals rounded, -0 kept; non-finite inputs are outside the
+ * contract).  fp32(q[c]) * scale is exact and a bf16 value, so every reader equals the bf16 kernels on the dequantised rows bit for bit.
+ * Bytes: [.., rows, Hkv * d] with row stride ld_*_bytes; scales: [.., rows, Hkv] fp32 with row stride ld_scale (floats); the batch strides
+ * separate the sequences.
+ *   kv_quant_f8: n_rows already-rotated bf16 rows src[r][Hkv * d] (row stride ld_src elements: e.g. the k columns of a fused q|k|v
+ *         activation) -> cache row row0 + r % rows_per_seq of sequence r / rows_per_seq.  One head-row per 16-lane group.
+ *   rope_kv_append_f8: the twin of mm355_rope_kv_append (device positions, graph-replayable): q rotated in place with the same bits, the
+ *         rotated k rounded to bf16 as that kernel stores it and then quantised, v quantised; bytes and scales into cache row positions[b].
+ *   attn_decode_f8(_variant): the twin of mm355_attn_decode(_variant), variants 0 and 2: s_j = k_scale[j] * sum_c fp32(K8[j][c]) *
+ *         (fp32(q[c]) * scale), o[c] = sum_j (p_j * v_scale[j]) * fp32(V8[j][c]) / l -- each scale once per key, the sums in the order of
+ *         the bf16 kernel (8 consecutive columns per lane, now one 8-byte load), the same workspace (mm355_attn_decode_ws_floats), the same
+ *         max_kv_len launch parameter and counter reset.  Equal to mm355_attn_decode on the dequantised cache, barring fp32 underflow.
+ *   Before any launch: fmt other than MM355_KV8_E4M3, a NULL scale pointer, pointers or strides that are not 8-byte (src / qkv: 16-byte)
+ *   aligned: MM355_EINVAL; d % 8 != 0 or d > 128: MM355_EUNSUPPORTED (rope_kv_append_f8 needs d % 16 == 0 as its twin does).
+ * ------------------------------------------------------------------------------------------------ */
+#define MM355_KV8_E4M3 1
+int mm355_kv_quant_f8(const mm355_bf16* src, int64_t ld_src, int64_t n_rows, int64_t rows_per_seq, int64_t Hkv, int64_t d,
+                      uint8_t* dst_bytes, int64_t ld_dst_bytes, float* dst_scale, int64_t ld_scale, int64_t batch_stride_bytes,
+                      int64_t batch_stride_scale, int64_t row0, int fmt, void* stream);
+int mm355_rope_kv_append_f8(mm355_bf16* qkv, int64_t ld, int64_t B, int64_t Hq, int64_t Hkv, int64_t d, const mm355_bf16* cos_t,
+                            const mm355_bf16* sin_t, const int32_t* positions, uint8_t* k_cache, uint8_t* v_cache, int64_t ld_kv_bytes,
+                            int64_t batch_stride_kv_bytes, float* k_scale, float* v_scale, int64_t ld_scale, int64_t batch_stride_scale,
+                            int fmt, void* stream);
+int mm355_attn_decode_f8(const mm355_bf16* q, int64_t ld_q, const uint8_t* k_cache, const uint8_t* v_cache, int64_t ld_kv_bytes,
+                         int64_t batch_stride_kv_bytes, const float* k_scale, const float* v_scale, int64_t ld_scale,
+                         int64_t batch_stride_scale, int fmt, const int32_t* kv_lens, int64_t max_kv_len, mm355_bf16* o, int64_t ld_o,
+                         int64_t B, int64_t Hq, int64_t Hkv, int64_t d, float scale, float* workspace, void* stream);
+int mm355_attn_decode_f8_variant(const mm355_bf16* q, int64_t ld_q, const uint8_t* k_cache, const uint8_t* v_cache, int64_t ld_kv_bytes,
+                                 int64_t batch_stride_kv_bytes, const float* k_scale, const float* v_scale, int64_t ld_scale,
+                                 int64_t batch_stride_scale, int fmt, const int32_t* kv_lens, int64_t max_kv_len, mm355_bf16* o,
+                                 int64_t ld_o, int64_t B, int64_t Hq, int64_t Hkv, int64_t d, float scale, float* workspace, int variant,
+                                 void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Elementwise: SwiGLU (HF LlamaMLP; K12), GELU (projector / vision_head), scaling helpers.
  * gu = [M][2I] with gate in columns [0,I) and up in [I,2I).
  * ------------------------------------------------------------------------------------------------ */

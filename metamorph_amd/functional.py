@@ -747,10 +747,23 @@ class KVCache:
     batch = 1).  Every row of the batch has its own length; the write positions live on the device as well (pos_dev / len_dev, int32
     [batch]) so that a decode step -- ONE pass over the weights for all rows -- is replayable as a hipGraph."""
 
-    def __init__(self, n_layers, max_len, width, device, Hq=None, d=None, batch=1):
+    def __init__(self, n_layers, max_len, width, device, Hq=None, d=None, batch=1, fmt="bf16"):
+        if fmt not in ops.KV_FORMATS:
+            raise ValueError(f"unknown KV cache format {fmt!r}; known: {', '.join(ops.KV_FORMATS)}")
         self.batch = batch
-        self.k = torch.empty((n_layers, batch, max_len, width), device=device, dtype=BF16)
-        self.v = torch.empty((n_layers, batch, max_len, width), device=device, dtype=BF16)
+        self.fmt = fmt
+        self.k_scale = self.v_scale = None
+        if fmt == "fp8_e4m3":
+            # one e4m3 byte per value plus one fp32 scale per head-row (ops.quantize_kv8): (d + 4) / 2d of the bf16 bytes
+            if d is None or width % d:
+                raise ValueError("an fp8_e4m3 KV cache needs the head size d (its scales are per head-row)")
+            self.k = torch.empty((n_layers, batch, max_len, width), device=device, dtype=torch.uint8)
+            self.v = torch.empty((n_layers, batch, max_len, width), device=device, dtype=torch.uint8)
+            self.k_scale = torch.empty((n_layers, batch, max_len, width // d), device=device, dtype=torch.float32)
+            self.v_scale = torch.empty((n_layers, batch, max_len, width // d), device=device, dtype=torch.float32)
+        else:
+            self.k = torch.empty((n_layers, batch, max_len, width), device=device, dtype=BF16)
+            self.v = torch.empty((n_layers, batch, max_len, width), device=device, dtype=BF16)
         self.max_len = max_len
         self.lengths = [0] * batch                                               # host mirror of pos_dev
         self.pos_dev = torch.zeros(batch, device=device, dtype=torch.int32)      # row the next token of sequence b is written to
@@ -759,6 +772,15 @@ class KVCache:
         if Hq is not None:                                                       # (sized for the whole batch: beyond 16 rows one attention launch serves all of them)
             self.ws = torch.zeros(int(ops._L().mm355_attn_decode_ws_floats(batch, Hq, d, max_len)), device=device,
                                   dtype=torch.float32)                           # arrival counters start at 0
+
+    @property
+    def kv8(self):
+        """(k_scale, v_scale) of an fp8_e4m3 cache, None for a bf16 one"""
+        return None if self.k_scale is None else (self.k_scale, self.v_scale)
+
+    def nbytes(self):
+        """bytes of the cached rows (and their scales)"""
+        return sum(t.numel() * t.element_size() for t in (self.k, self.v, self.k_scale, self.v_scale) if t is not None)
 
     @property
     def length(self):
@@ -805,7 +827,14 @@ def decoder_prefill(x, layers, meta, cache, row=0):
         w8_materialize(layer)                                 # (a quantised layer: ALL four projections dequantised into the shared scratch, see W8Scratch -- a one-sequence prompt gets here once q|k|v is no longer split, 960 rows at 8B widths)
         x, saved = decoder_layer_forward(x, layer, meta)
         qkv = saved[0]
-        if B == 1:
+        if cache.kv8 is not None:                            # fp8_e4m3 cache: the rows are quantised as they enter it (one launch each for k and v)
+            kr = cache.k[i, row:row + 1] if B == 1 else cache.k[i]
+            vr = cache.v[i, row:row + 1] if B == 1 else cache.v[i]
+            ksr = cache.k_scale[i, row:row + 1] if B == 1 else cache.k_scale[i]
+            vsr = cache.v_scale[i, row:row + 1] if B == 1 else cache.v_scale[i]
+            ops.kv_quant_f8(qkv[:, nq:nq + nk], meta.Hkv, meta.d, kr, ksr, rows_per_seq=L)
+            ops.kv_quant_f8(qkv[:, nq + nk:], meta.Hkv, meta.d, vr, vsr, rows_per_seq=L)
+        elif B == 1:
             # the k / v column blocks of the fused activation -> cache rows: a strided row copy with 16-byte vectors (mm355_rows_gather with the
             # identity map: ~3 us; ATen's strided bf16 copy took 28 us per call, 1.3 of the 10.8 ms of a 512-row prompt pass)
             ops.rows_gather(qkv[:, nq:nq + nk], ident, out=cache.k[i, row, :L])
@@ -829,6 +858,11 @@ def _prefill_layers_fused(x, layers, meta, cache, row, ident):
     L = x.shape[0]
     nq = meta.Hq * meta.d
     n1 = None
+    stage = None
+    if cache.kv8 is not None:
+        # fp8_e4m3 cache: the reduce launch writes the rotated k and the v rows into ONE pair of bf16 staging buffers shared by all layers,
+        # attention runs on them (the bits of the bf16-cache pass), then they are quantised into the cache rows
+        stage = torch.empty((2, L, meta.Hkv * meta.d), device=x.device, dtype=BF16)
     for i, layer in enumerate(layers):
         params_ready(layer)
         rec = getattr(layer, "w8", None)
@@ -836,12 +870,15 @@ def _prefill_layers_fused(x, layers, meta, cache, row, ident):
         att, mlp = layer.self_attn, layer.mlp
         if n1 is None:
             n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
-        kc, vc = cache.k[i, row], cache.v[i, row]                             # [max_len, width]
+        kc, vc = (stage[0], stage[1]) if stage is not None else (cache.k[i, row], cache.v[i, row])   # [max_len, width]
         rows_k = kc.as_strided((L, kc.shape[0], kc.shape[1]), (0, kc.stride(0), 1))
         rows_v = vc.as_strided((L, vc.shape[0], vc.shape[1]), (0, vc.stride(0), 1))
         qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), ops.gemm_w8_rope_append,
                     ops.gemm_splitk_rope_append, n1, meta.Hq, meta.Hkv, meta.d, meta.cos, meta.sin, ident, rows_k, rows_v)
         o, _ = ops.attn_fwd(qkv[:, :nq], kc[:L], vc[:L], 1, L, meta.Hq, meta.Hkv, meta.d, meta.scale, True, meta.seqlens)
+        if stage is not None:
+            ops.kv_quant_f8(stage[0], meta.Hkv, meta.d, cache.k[i, row:row + 1], cache.k_scale[i, row:row + 1])
+            ops.kv_quant_f8(stage[1], meta.Hkv, meta.d, cache.v[i, row:row + 1], cache.v_scale[i, row:row + 1])
         x2, n2 = _proj(on8, rec, "o", (att.o_proj.weight,), ops.gemm_w8_norm, ops.gemm_splitk_norm, o,
                        layer.post_attention_layernorm.weight, meta.eps, residual=x)
         if "gu" in on8:
@@ -986,7 +1023,15 @@ def _proj(on8, rec, name, weights, w8_op, bf16_op, x, *args, **kw):
     return bf16_op(x, weights[0] if len(weights) == 1 else fused_weight(weights), *args, **kw)
 
 
-def _decode_rows16_w8(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound):
+def _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound):
+    """The new q|k|v rows against layer i of an fp8_e4m3 cache (k / v: the bytes, kv8: the scales): RoPE + quantising append, then attention
+    over the bytes -- the row just appended included.  Two launches; the projection in front is the plain one."""
+    ops.rope_kv_append_f8_(qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i], kv8[0][i], kv8[1][i])
+    return ops.attn_decode_f8(qkv[:, :meta.Hq * meta.d], k[i], v[i], kv8[0][i], kv8[1][i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d,
+                              meta.scale, workspace=ws)
+
+
+def _decode_rows16_w8(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound, kv8=None):
     """_decode_rows16 on layers that carry a W8Layer record: the same five / seven launches per layer on the mm355_gemv*_w8 kernels."""
     nq = meta.Hq * meta.d
     fused = VARIANTS["decode_fused"] and meta.I % 2 == 0 and meta.d % 4 == 0
@@ -994,10 +1039,14 @@ def _decode_rows16_w8(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_
         rec = layer.w8
         if fused:
             fold = x.shape[0] <= VARIANTS["decode_fold_rows"]
-            n1 = x if fold else ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
-            qkv = ops.gemv_rope_append_w8(n1, *rec.qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i],
-                                          norm_w=layer.input_layernorm.weight if fold else None, eps=meta.eps)
-            o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
+            if kv8 is not None:                              # fp8_e4m3 cache: norm, plain projection, quantising append, attention over the bytes
+                qkv = ops.gemv_w8(ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps), *rec.qkv)
+                o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound)
+            else:
+                n1 = x if fold else ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
+                qkv = ops.gemv_rope_append_w8(n1, *rec.qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i],
+                                              norm_w=layer.input_layernorm.weight if fold else None, eps=meta.eps)
+                o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
             x2 = ops.gemv_w8(o, *rec.o, residual=x)
             n2 = x2 if fold else ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
             act = ops.gemv_swiglu_w8(n2, *rec.gu, meta.I, norm_w=layer.post_attention_layernorm.weight if fold else None, eps=meta.eps)
@@ -1005,8 +1054,11 @@ def _decode_rows16_w8(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_
             continue
         n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
         qkv = ops.gemv_w8(n1, *rec.qkv)
-        ops.rope_kv_append_(qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
-        o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
+        if kv8 is not None:
+            o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound)
+        else:
+            ops.rope_kv_append_(qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
+            o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
         x2 = ops.gemv_w8(o, *rec.o, residual=x)
         n2 = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
         act = ops.swiglu_fwd(ops.gemv_w8(n2, *rec.gu), meta.I)
@@ -1014,12 +1066,12 @@ def _decode_rows16_w8(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_
     return x
 
 
-def _decode_rows16(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound):
+def _decode_rows16(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound, kv8=None):
     """<= 16 new rows (one per sequence) through every decoder layer against their cache rows k / v [layers, rows, max_len, width]:
     every weight is streamed ONCE for all rows (mm355_gemv* take M <= 16: up to four rows on the vector ALU, 5 .. 16 on MFMA), attention per
     row at its own length."""
     if getattr(layers[0], "w8", None) is not None:
-        return _decode_rows16_w8(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound)
+        return _decode_rows16_w8(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound, kv8)
     nq = meta.Hq * meta.d
     for i, layer in enumerate(layers):
         params_ready(layer)
@@ -1032,10 +1084,16 @@ def _decode_rows16(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bou
             # Five rows and more (the MFMA GEMVs): the norm runs as its own launch -- folded in, every workgroup would normalise ALL rows again
             # (measured, cached step of 32 layers: four rows 3.50 -> 3.38 ms with the norms folded, eight rows slower) -- seven launches, same bits.
             fold = x.shape[0] <= VARIANTS["decode_fold_rows"]
-            n1 = x if fold else ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
-            qkv = ops.gemv_rope_append(n1, wqkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i],
-                                       norm_w=layer.input_layernorm.weight if fold else None, eps=meta.eps)
-            o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
+            if kv8 is not None:
+                # fp8_e4m3 cache: the norm and the plain projection as launches of their own (no fused *_rope_append_f8 form), then the
+                # quantising append and attention over the bytes: seven launches per layer up to the fold limit, eight beyond
+                qkv = ops.gemv(ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps), wqkv)
+                o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound)
+            else:
+                n1 = x if fold else ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
+                qkv = ops.gemv_rope_append(n1, wqkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i],
+                                           norm_w=layer.input_layernorm.weight if fold else None, eps=meta.eps)
+                o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
             x2 = ops.gemv(o, att.o_proj.weight, residual=x)
             n2 = x2 if fold else ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
             act = ops.gemv_swiglu(n2, wgu, meta.I, norm_w=layer.post_attention_layernorm.weight if fold else None, eps=meta.eps)
@@ -1043,8 +1101,11 @@ def _decode_rows16(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bou
             continue
         n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
         qkv = ops.gemv(n1, wqkv)
-        ops.rope_kv_append_(qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
-        o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
+        if kv8 is not None:
+            o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound)
+        else:
+            ops.rope_kv_append_(qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
+            o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
         x2 = ops.gemv(o, att.o_proj.weight, residual=x)
         n2 = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
         gu = ops.gemv(n2, wgu)
@@ -1053,7 +1114,7 @@ def _decode_rows16(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bou
     return x
 
 
-def _decode_rows_gemm(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound):
+def _decode_rows_gemm(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound, kv8=None):
     """17 new rows and more (one per sequence) through every decoder layer in ONE pass over the weights (round 6; rounds 5: chunks of 16 rows,
     i.e. the 15 GB read once per chunk).  The GEMV kernels hold one 16-row MFMA operand; beyond it the projections take the split-K GEMM of
     the prompt pass (mm355_gemm_splitk_bf16: 64 x 128 tiles x K slices -- at 32 rows a weight-streaming problem with ~3 workgroups per CU),
@@ -1072,9 +1133,13 @@ def _decode_rows_gemm(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_
             att, mlp = layer.self_attn, layer.mlp
             if n1 is None:
                 n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
-            qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), ops.gemm_w8_rope_append,
-                        ops.gemm_splitk_rope_append, n1, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
-            o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
+            if kv8 is not None:                              # fp8_e4m3 cache: the plain split projection, then the quantising append (ten launches per layer)
+                qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), ops.gemm_w8, ops.gemm_splitk, n1)
+                o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound)
+            else:
+                qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), ops.gemm_w8_rope_append,
+                            ops.gemm_splitk_rope_append, n1, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
+                o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
             x2, n2 = _proj(on8, rec, "o", (att.o_proj.weight,), ops.gemm_w8_norm, ops.gemm_splitk_norm, o,
                            layer.post_attention_layernorm.weight, meta.eps, residual=x)
             if "gu" in on8:
@@ -1099,8 +1164,11 @@ def _decode_rows_gemm(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_
         att, mlp = layer.self_attn, layer.mlp
         n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
         qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), ops.gemm_w8, ops.gemm_splitk, n1)
-        ops.rope_kv_append_(qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
-        o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
+        if kv8 is not None:
+            o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound)
+        else:
+            ops.rope_kv_append_(qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
+            o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
         x2 = _proj(on8, rec, "o", (att.o_proj.weight,), ops.gemm_w8, ops.gemm_splitk, o, residual=x)
         n2 = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
         gu = _proj(on8, rec, "gu", (mlp.gate_proj.weight, mlp.up_proj.weight), ops.gemm_w8, ops.gemm_splitk, n2)
@@ -1136,9 +1204,9 @@ def decoder_decode_row(x, layers, meta, cache, cos, sin, kv_bound=None):
         # the bound is a launch parameter (number of key groups): a sequence longer than it would silently attend to its first `bound` keys
         raise ValueError(f"decode bound {bound} is below the longest sequence + 1 ({cache.length + 1}); lengths change only through set_lengths")
     if B <= 16:
-        y = _decode_rows16(x, layers, meta, cos, sin, cache.k, cache.v, cache.pos_dev, cache.len_dev, cache.ws, bound)
+        y = _decode_rows16(x, layers, meta, cos, sin, cache.k, cache.v, cache.pos_dev, cache.len_dev, cache.ws, bound, cache.kv8)
     else:
-        y = _decode_rows_gemm(x, layers, meta, cos, sin, cache.k, cache.v, cache.pos_dev, cache.len_dev, cache.ws, bound)
+        y = _decode_rows_gemm(x, layers, meta, cos, sin, cache.k, cache.v, cache.pos_dev, cache.len_dev, cache.ws, bound, cache.kv8)
     cache.pos_dev.add_(1)
     cache.len_dev.add_(1)
     cache.lengths = [n + 1 for n in cache.lengths]

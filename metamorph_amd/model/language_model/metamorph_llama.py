@@ -105,9 +105,10 @@ class HipKVCache(DynamicCache):
     reference's `forward` does: the batch goes to one HF forward per step).  HF only asks a cache for its length and, under beam search,
     to re-order its batch rows (`reorder_cache`); the tensors never leave the device or change layout."""
 
-    def __init__(self, capacity=None, **kw):
+    def __init__(self, capacity=None, kv_format=None, **kw):
         super().__init__(**kw)
         self.capacity = capacity          # rows to allocate at the first (prompt) pass; None: prompt + 1024 + 2
+        self.kv_format = kv_format        # "bf16" / "fp8_e4m3" (functional.KVCache); None: config.mm355_kv_cache_format
         self.kv = None                    # functional.KVCache of the whole batch
         self.pads = []                    # left-padding rows of every sequence in the batch HF sees (never cached: kv.lengths count real rows)
         self.stepper = None               # functional.DecodeStepGraph
@@ -138,6 +139,9 @@ class HipKVCache(DynamicCache):
         sel = torch.as_tensor(idx, dtype=torch.long, device=kv.k.device)
         kv.k[:, :, :n].copy_(kv.k[:, :, :n].index_select(1, sel))
         kv.v[:, :, :n].copy_(kv.v[:, :, :n].index_select(1, sel))
+        if getattr(kv, "k_scale", None) is not None:          # an fp8_e4m3 cache: the scales travel with their bytes
+            kv.k_scale[:, :, :n].copy_(kv.k_scale[:, :, :n].index_select(1, sel))
+            kv.v_scale[:, :, :n].copy_(kv.v_scale[:, :, :n].index_select(1, sel))
         kv.set_lengths([kv.lengths[j] for j in idx])
         self.pads = [self.pads[j] for j in idx]
 
@@ -667,6 +671,14 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         return logits, hid, pred_z
 
     @torch.no_grad()
+    def _kv_cache_format(self, fmt=None):
+        """The KV cache format of cached generation: `fmt` if given, else config.mm355_kv_cache_format ("bf16", the default, or
+        "fp8_e4m3": e4m3 bytes plus one fp32 scale per head-row, functional.KVCache)."""
+        fmt = getattr(self.config, "mm355_kv_cache_format", "bf16") if fmt is None else fmt
+        if fmt not in ops.KV_FORMATS:
+            raise ValueError(f"unknown KV cache format {fmt!r}; known: {', '.join(ops.KV_FORMATS)}")
+        return fmt
+
     def _greedy_decode_cached(self, inputs_embeds, start_image_token_id, end_image_token_id, eos_token_id, max_new_tokens,
                               output_image):
         if inputs_embeds.shape[0] != 1:
@@ -681,7 +693,7 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         max_len = L0 + max_new_tokens + 2
         cos, sin = self.model.rope_tables(max_len, dev)
         meta.cos, meta.sin = cos, sin
-        cache = F.KVCache(len(self.model.layers), max_len, meta.Hkv * meta.d, dev, Hq=meta.Hq, d=meta.d)
+        cache = F.KVCache(len(self.model.layers), max_len, meta.Hkv * meta.d, dev, Hq=meta.Hq, d=meta.d, fmt=self._kv_cache_format())
         x = F.decoder_prefill(inputs_embeds.reshape(L0, h).contiguous(), self.model.layers, meta, cache)[-1:].contiguous()
         stepper = F.DecodeStepGraph(self.model.layers, meta, cache, cos, sin, h, dev)
         in_image_mode = False
@@ -735,7 +747,8 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         cos, sin = self.model.rope_tables(cap, dev)
         _, meta = self._decode_meta(L0)
         meta.cos, meta.sin = cos, sin
-        cache.kv = F.KVCache(len(self.model.layers), cap, meta.Hkv * meta.d, dev, Hq=meta.Hq, d=meta.d, batch=B)
+        cache.kv = F.KVCache(len(self.model.layers), cap, meta.Hkv * meta.d, dev, Hq=meta.Hq, d=meta.d, batch=B,
+                             fmt=self._kv_cache_format(cache.kv_format))
         cache.meta = meta
         if B > 1 and all(n == L0 for n in lens):
             _, mb = self._decode_meta(L0)

@@ -471,6 +471,88 @@ def attn_decode(q, k_cache, v_cache, kv_lens, max_kv_len, Hq, Hkv, d, scale, out
     return out
 
 
+# ------------------------------------------------------------------------------------------------ FP8 KV cache (decode)
+
+KV8_E4M3 = 1                                                 # MM355_KV8_E4M3
+KV_FORMATS = ("bf16", "fp8_e4m3")
+
+
+def quantize_kv8(rows, Hkv, d):
+    """rows [..., Hkv*d] bf16 -> (q uint8 [..., Hkv*d], scale f32 [..., Hkv]) of KV format "fp8_e4m3": per head-row (the d values of one KV
+    head of one token) scale = the smallest power of two with amax / scale <= 448 (zeros: 1), q = the OCP e4m3fn byte of RNE(x / scale) -- an
+    exact shift, nothing saturates.  The contract mm355_kv_quant_f8 / mm355_rope_kv_append_f8 are tested against.  Not a hot path: torch ops,
+    on whatever device rows lives on."""
+    assert rows.dtype == BF16 and rows.shape[-1] == Hkv * d
+    x = rows.detach().float().reshape(*rows.shape[:-1], Hkv, d)
+    amax = x.abs().amax(dim=-1)
+    m, e = torch.frexp(amax)                                 # amax = m * 2^e, m in [0.5, 1); 448 = 0.875 * 2^9
+    sh = torch.where(amax > 0, e - 9 + (m > 0.875).to(e.dtype), torch.zeros_like(e))
+    q = torch.ldexp(x, -sh[..., None]).to(torch.float8_e4m3fn)
+    scale = torch.ldexp(torch.ones_like(amax), sh)
+    return q.view(torch.uint8).reshape(rows.shape).contiguous(), scale.contiguous()
+
+
+def dequant_kv8(q, scale, Hkv, d):
+    """bf16 [..., Hkv*d] = fp32(q) * scale per head-row: exact, and exactly a bf16 value (torch ops: tests and tools)."""
+    assert q.dtype == torch.uint8 and q.shape[-1] == Hkv * d and scale.shape[-1] == Hkv
+    x = q.contiguous().view(torch.float8_e4m3fn).float().reshape(*q.shape[:-1], Hkv, d) * scale.float()[..., None]
+    return x.reshape(q.shape).to(BF16)
+
+
+def _kv8_cache(c8, sc, Hkv, d):
+    """(ld bytes, batch stride bytes, ld scale, batch stride scale) of a cache [B, Lmax, Hkv*d] uint8 with scales [B, Lmax, Hkv] f32"""
+    assert c8.dtype == torch.uint8 and c8.dim() == 3 and c8.shape[2] == Hkv * d and c8.stride(2) == 1, (c8.dtype, c8.shape, c8.stride())
+    assert sc.dtype == torch.float32 and sc.dim() == 3 and tuple(sc.shape) == (c8.shape[0], c8.shape[1], Hkv) and sc.stride(2) == 1
+    return c8.stride(1), c8.stride(0), sc.stride(1), sc.stride(0)
+
+
+def kv_quant_f8(src, Hkv, d, dst, dst_scale, row0=0, rows_per_seq=None):
+    """src [R, Hkv*d] bf16 (already rotated; may be a column block of a wider tensor) -> cache rows: source row r goes to row
+    row0 + r % rows_per_seq of sequence r // rows_per_seq of dst [B, Lmax, Hkv*d] uint8 / dst_scale [B, Lmax, Hkv] f32
+    (mm355_kv_quant_f8; rows_per_seq None: all rows belong to sequence 0)."""
+    _chk_dev(src, dst, dst_scale)
+    ps, R, W, lds = _rows2d(src)
+    assert src.dtype == BF16 and W == Hkv * d
+    ldb, bsb, ldsc, bssc = _kv8_cache(dst, dst_scale, Hkv, d)
+    rps = R if rows_per_seq is None else int(rows_per_seq)
+    assert R % rps == 0 and R // rps <= dst.shape[0] and row0 + rps <= dst.shape[1], (R, rps, row0, dst.shape)
+    _lib.check(_L().mm355_kv_quant_f8(ps, lds, R, rps, Hkv, d, dst.data_ptr(), ldb, dst_scale.data_ptr(), ldsc, bsb, bssc, int(row0), KV8_E4M3,
+                                      _stream()), f"mm355_kv_quant_f8 R={R} Hkv={Hkv} d={d}")
+
+
+def rope_kv_append_f8_(qkv, Hq, Hkv, d, cos, sin, positions, k8, v8, k_scale, v_scale):
+    """rope_kv_append_() into an e4m3 cache: q rotated in place (the same bits), the rotated k row (rounded to bf16 as the bf16 cache would
+    hold it) and the v row quantised into row positions[b] of k8 / v8 [B, Lmax, Hkv*d] uint8 and k_scale / v_scale [B, Lmax, Hkv] f32."""
+    _chk_dev(qkv, cos, sin, positions, k8, v8, k_scale, v_scale)
+    assert positions.dtype == torch.int32 and k8.stride() == v8.stride() and k_scale.stride() == v_scale.stride()
+    ldb, bsb, ldsc, bssc = _kv8_cache(k8, k_scale, Hkv, d)
+    _kv8_cache(v8, v_scale, Hkv, d)
+    B = qkv.shape[0]
+    _lib.check(_L().mm355_rope_kv_append_f8(qkv.data_ptr(), qkv.stride(0), B, Hq, Hkv, d, cos.data_ptr(), sin.data_ptr(), positions.data_ptr(),
+                                            k8.data_ptr(), v8.data_ptr(), ldb, bsb, k_scale.data_ptr(), v_scale.data_ptr(), ldsc, bssc,
+                                            KV8_E4M3, _stream()), "mm355_rope_kv_append_f8")
+    return qkv
+
+
+def attn_decode_f8(q, k8, v8, k_scale, v_scale, kv_lens, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None, variant=0):
+    """attn_decode() over an e4m3 cache: k8 / v8 [B, Lmax, Hkv*d] uint8, k_scale / v_scale [B, Lmax, Hkv] f32 (variants 0 and 2)."""
+    _chk_dev(q, k8, v8, k_scale, v_scale, kv_lens)
+    B = q.shape[0]
+    assert k8.shape == v8.shape and k8.stride() == v8.stride() and k_scale.stride() == v_scale.stride()
+    ldb, bsb, ldsc, bssc = _kv8_cache(k8, k_scale, Hkv, d)
+    _kv8_cache(v8, v_scale, Hkv, d)
+    assert kv_lens.dtype == torch.int32 and max_kv_len <= k8.shape[1]
+    out = torch.empty((B, Hq * d), device=q.device, dtype=BF16) if out is None else out
+    ws = workspace
+    if ws is None:
+        ws = torch.zeros(int(_L().mm355_attn_decode_ws_floats(B, Hq, d, max_kv_len)), device=q.device, dtype=torch.float32)   # arrival counters start at 0
+    _lib.check(_L().mm355_attn_decode_f8_variant(q.data_ptr(), q.stride(0), k8.data_ptr(), v8.data_ptr(), ldb, bsb, k_scale.data_ptr(),
+                                                 v_scale.data_ptr(), ldsc, bssc, KV8_E4M3, kv_lens.data_ptr(), max_kv_len, out.data_ptr(),
+                                                 out.stride(0), B, Hq, Hkv, d, scale, ws.data_ptr(), int(variant), _stream()),
+               "mm355_attn_decode_f8")
+    return out
+
+
 def transpose(x, out=None, ld_out=None):
     """out[c, r] = x[r, c]"""
     _chk_dev(x, out)
