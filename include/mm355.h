@@ -449,6 +449,36 @@ int mm355_attn_decode_f8_variant(const mm355_bf16* q, int64_t ld_q, const uint8_
                                  void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Extending a filled KV cache by n rows per sequence in one pass (csrc/attn_extend.hip): the shape between the prompt pass (mm355_attn_fwd: one
+ * length for queries and keys) and the decode step (mm355_attn_decode: one query row per sequence) -- a follow-up turn of a conversation, a
+ * prompt run in chunks, several candidate tokens scored against one cache (reference: the cached generate() of metamorph_llama.py:502-597).
+ *   attn_extend: q [B*n][Hq*d] (ld_q), ALREADY rotated, row (b, i) at b * n + i; caches [B][rows][Hkv*d] as mm355_attn_decode takes them (row
+ *         stride ld_kv, sequence stride batch_stride_kv); past[B] int32 on the device; o [B*n][Hq*d] (ld_o).  The cache already holds the
+ *         chunk's own rows at past[b] .. past[b] + n - 1 (the append comes first); row (b, i) attends the keys j <= past[b] + i: o = softmax(
+ *         scale * q K^T) V with the softmax in fp32 and the scale applied on the fp32 side.  max_kv_len is a host bound, past[b] + n <=
+ *         max_kv_len <= rows: it sizes the launch and the workspace (mm355_attn_extend_ws_floats floats, 16-byte aligned; 0: workspace may be
+ *         NULL) and no row >= max_kv_len is read whatever past[] says; cache rows >= past[b] + n are never read.  Right for n == 1 and
+ *         past[b] == 0.  v_mfma_f32_16x16x32_bf16, K / V tiles through LDS, the query rows of a GQA group packed into one row tile so that a
+ *         tile of the cache is read once per KV head; few workgroups (small n, long prefix): the key tiles are dealt to several workgroups
+ *         and a second launch merges their partials.  The split is a function of (B, n, Hq, Hkv, max_kv_len) alone.
+ *   attn_extend_f8: the same over an e4m3 cache (bytes and scales as mm355_attn_decode_f8 takes them): the bytes times the power-of-two scale
+ *         are widened to bf16 on the way into LDS (exact, see above), the rest is the same code: equal to mm355_attn_extend on the dequantised
+ *         cache bit for bit.
+ *   Before any launch: fmt other than MM355_KV8_E4M3, a NULL pointer or scale, n > max_kv_len, Hq % Hkv != 0, q / o not 16-byte aligned or
+ *   ld_q / ld_o % 8 != 0, cache pointers or strides not 16-byte (e4m3: 8-byte) aligned, a row stride shorter than a row, a workspace that is
+ *   missing or too small: MM355_EINVAL; d % 8 != 0, d > 128 or a GQA group other than 1, 2, 4, 8: MM355_EUNSUPPORTED.
+ * ------------------------------------------------------------------------------------------------ */
+int64_t mm355_attn_extend_ws_floats(int64_t B, int64_t n, int64_t Hq, int64_t Hkv, int64_t d, int64_t max_kv_len);
+int mm355_attn_extend(const mm355_bf16* q, int64_t ld_q, const mm355_bf16* k_cache, const mm355_bf16* v_cache, int64_t ld_kv,
+                      int64_t batch_stride_kv, const int32_t* past, int64_t n, int64_t max_kv_len, mm355_bf16* o, int64_t ld_o,
+                      int64_t B, int64_t Hq, int64_t Hkv, int64_t d, float scale, float* workspace, int64_t workspace_floats, void* stream);
+int mm355_attn_extend_f8(const mm355_bf16* q, int64_t ld_q, const uint8_t* k_cache, const uint8_t* v_cache, int64_t ld_kv_bytes,
+                         int64_t batch_stride_kv_bytes, const float* k_scale, const float* v_scale, int64_t ld_scale,
+                         int64_t batch_stride_scale, int fmt, const int32_t* past, int64_t n, int64_t max_kv_len, mm355_bf16* o,
+                         int64_t ld_o, int64_t B, int64_t Hq, int64_t Hkv, int64_t d, float scale, float* workspace,
+                         int64_t workspace_floats, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Elementwise: SwiGLU (HF LlamaMLP; K12), GELU (projector / vision_head), scaling helpers.
  * gu = [M][2I] with gate in columns [0,I) and up in [I,2I).
  * ------------------------------------------------------------------------------------------------ */

@@ -1,0 +1,361 @@
+// Attention of n NEW rows against a filled KV cache (gfx950): row (b, i) sits at position past[b] + i and attends the cache rows
+// [0, past[b] + i]; the chunk's own rows are already in the cache (the append comes first).  The shape between the prompt pass
+// (mm355_attn_fwd: one length for queries and keys) and the decode step (mm355_attn_decode: one query row per sequence).
+//
+// The kernel is attn2.hip's fwd_kernel ("swapped" formulation: S^T = K Q^T, O^T += V^T P^T, natural [64][d] K / V tiles in LDS with the
+// 16-B chunk swizzle, P never leaves registers, online softmax in the log2 domain with deferred rescale) with three changes:
+//   * query rows are PACKED per KV head: packed row r = i * G + g is query row i of head hk * G + g (G = the GQA group), so a workgroup
+//     (sequence, KV head, 64 packed rows = 16 per wave) reads every K / V tile once for the whole group, and n = 1 with G = 4 is 4 rows of
+//     one fragment instead of 4 workgroups;
+//   * the key limit is per row and comes from the device: key j is visible to row r iff j <= past[b] + r / G;
+//   * when (sequences x KV heads x row tiles) is a handful of workgroups, the 64-key tiles are dealt to `nsplit` workgroups in contiguous
+//     runs; each writes its unnormalised fp32 O, running reference maximum and sum, and extend_merge_kernel (a second launch) folds them.
+//     The split depends on the launch arguments only (never on past[]), so the bf16 and the e4m3 form of one call split alike.
+// The e4m3 form differs in the tile mover alone: 8 bytes per 8 columns plus the head-row's scale, widened to bf16 (exact: mm355.h, the
+// KV8 contract) where the tile is written into LDS.  Everything after that is the same code on the same bits.
+// Cache rows >= past[b] + n are never read: ragged tiles clamp their row index to the last visible row of the workgroup.
+#include "attn2.h"
+#include <algorithm>
+
+namespace {
+using namespace attn2;
+
+struct XArgs {
+    const uint16_t* q; int64_t ld_q;
+    const unsigned char* k; const unsigned char* v; int64_t ld_kv, bs_kv;      // BYTES per cache row / per sequence
+    const float* ks; const float* vs; int64_t ld_sc, bs_sc;                    // e4m3 form: scales [B][rows][Hkv]
+    const int32_t* past; uint16_t* o; int64_t ld_o; float* ws;
+    int n, Hkv, d, G, R, nqt, nsplit, tps, max_kv; int64_t rpad;
+    float scale;
+};
+
+struct Plan { int G, R, nqt, nsplit, tps; int64_t rpad; };
+
+// nsplit: 1 while the row tiles alone give every other CU a workgroup; else enough runs of >= 4 key tiles to reach about one per CU
+Plan make_plan(int64_t B, int64_t n, int64_t Hq, int64_t Hkv, int64_t max_kv_len) {
+    Plan p;
+    p.G = (int)(Hq / Hkv);
+    p.R = (int)(n * p.G);
+    p.nqt = (p.R + 63) / 64;
+    p.rpad = (int64_t)p.nqt * 64;
+    const int64_t nwg = B * Hkv * p.nqt;
+    const int ktiles = (int)((max_kv_len + 63) / 64);
+    int ns = 1;
+    if (nwg < 128) ns = (int)std::min<int64_t>(std::max(1, ktiles / 4), (256 + nwg - 1) / nwg);
+    ns = std::min(ns, 64);
+    p.tps = (ktiles + ns - 1) / ns;
+    p.nsplit = (ktiles + p.tps - 1) / p.tps;
+    return p;
+}
+
+template <int NV, bool F8> struct Stage;
+template <int NV> struct Stage<NV, false> { u32x4 r[NV]; };
+template <int NV> struct Stage<NV, true> { u32x2 r[NV]; float s[NV]; };
+
+// rows [row0, row0 + 64) of one KV head -> registers; rows past `end` repeat row end - 1 (masked by the caller), columns >= d are zero
+template <int DP, int NV, bool F8>
+MM_DEV void load_tile(Stage<NV, F8>& st, const unsigned char* base, const float* sbase, int64_t ld, int64_t ld_sc, int row0, int end, int d, int tid) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int v = tid + i * NT, row = v / (DP / 8), c = v % (DP / 8);
+        const bool on = v < Geo<DP>::V64 && c * 8 < d;
+        const int rr = min(row0 + row, end - 1);
+        if constexpr (F8) {
+            st.r[i] = on ? *(const u32x2*)(base + (int64_t)rr * ld + c * 8) : u32x2{0u, 0u};
+            st.s[i] = on ? sbase[(int64_t)rr * ld_sc] : 0.f;
+        } else {
+            st.r[i] = on ? *(const u32x4*)(base + (int64_t)rr * ld + c * 16) : u32x4{0u, 0u, 0u, 0u};
+        }
+    }
+}
+template <int DP, int NV, bool F8>
+MM_DEV void store_tile(const Stage<NV, F8>& st, unsigned char* s, int tid) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int v = tid + i * NT, row = v / (DP / 8), c = v % (DP / 8);
+        if (v >= Geo<DP>::V64) continue;
+        u32x4 w;
+        if constexpr (F8) {                                  // e4m3 -> fp32 is exact, times a power of two is exact and a bf16 value
+            const mm_f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)st.r[i].x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)st.r[i].x, true);
+            const mm_f32x2 e = __builtin_amdgcn_cvt_pk_f32_fp8((int)st.r[i].y, false), f = __builtin_amdgcn_cvt_pk_f32_fp8((int)st.r[i].y, true);
+            const float sc = st.s[i];
+            w.x = pack2bf(a.x * sc, a.y * sc); w.y = pack2bf(b.x * sc, b.y * sc);
+            w.z = pack2bf(e.x * sc, e.y * sc); w.w = pack2bf(f.x * sc, f.y * sc);
+        } else {
+            w = st.r[i];
+        }
+        *(u32x4*)(s + offN<Geo<DP>::DS>(row, c)) = w;
+    }
+}
+
+template <int DP, bool F8>
+__global__ __launch_bounds__(NT) void extend_kernel(XArgs a) {
+    using G_ = Geo<DP>;
+    constexpr int DS = G_::DS, KS = G_::KS, NF = G_::NF;
+    constexpr int NV = (G_::V64 + NT - 1) / NT;
+    constexpr int EPI = 4 * 16 * DP * 2;                    // bf16 output staging
+    constexpr int SMEM = 2 * G_::T64 > EPI ? 2 * G_::T64 : EPI;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM];
+    unsigned char* sK = smem;
+    unsigned char* sV = smem + G_::T64;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int fr = lane & 15, fq = lane >> 4;
+    const int qt = blockIdx.x / a.nsplit, split = blockIdx.x % a.nsplit;
+    const int hk = blockIdx.y, b = blockIdx.z;
+    const int d = a.d, G = a.G, R = a.R, n = a.n;
+    const int past = a.past[b];
+    const int q0 = qt * 64, qw0 = q0 + wave * 16;
+    // last key (exclusive) any row of this workgroup sees; the host bound keeps a wrong past[] inside the cache
+    const int kv_end = min(past + min(R - 1, q0 + 63) / G + 1, a.max_kv);
+    const int ntiles = (kv_end + 63) >> 6;
+    const int t0 = split * a.tps, t1 = min(ntiles, t0 + a.tps);
+
+    const int pr = min(qw0 + fr, R - 1);                     // this lane's packed row (clamped: rows >= R are not stored)
+    const int qi = pr / G, qg = pr - qi * G;
+    const int klim = past + qi;                              // last visible key of the row
+    const int wave_lo = past + min(qw0, R - 1) / G, wave_hi = past + min(qw0 + 15, R - 1) / G;
+    const bool wave_on = qw0 < R;
+
+    bf16x8 qf[KS];                                           // B operand: Q[row = fr][d chunk]
+    {
+        const uint16_t* qp = a.q + ((int64_t)b * n + qi) * a.ld_q + (int64_t)(hk * G + qg) * d;
+#pragma unroll
+        for (int kk = 0; kk < KS; ++kk) {
+            const int c = kk * 32 + fq * 8;
+            qf[kk] = (c < d) ? *(const bf16x8*)(qp + c) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        }
+    }
+    f32x4 ot[NF];                                            // O^T[d = j*16 + fq*4 + r][row = fr]
+    float m_run = -INFINITY, l_run = 0.f;
+#pragma unroll
+    for (int j = 0; j < NF; ++j) ot[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    constexpr int EB = F8 ? 1 : 2;
+    const unsigned char* kbase = a.k + (int64_t)b * a.bs_kv + (int64_t)hk * d * EB;
+    const unsigned char* vbase = a.v + (int64_t)b * a.bs_kv + (int64_t)hk * d * EB;
+    const float* ksb = F8 ? a.ks + (int64_t)b * a.bs_sc + hk : nullptr;
+    const float* vsb = F8 ? a.vs + (int64_t)b * a.bs_sc + hk : nullptr;
+    const float sl2 = a.scale * 1.4426950408889634f;         // scores in log2 domain: exp2(s*sl2 - m), the scale on the fp32 side
+
+    if (t0 < t1) {
+        Stage<NV, F8> rk, rv;
+        load_tile<DP, NV, F8>(rk, kbase, ksb, a.ld_kv, a.ld_sc, t0 * 64, kv_end, d, tid);
+        load_tile<DP, NV, F8>(rv, vbase, vsb, a.ld_kv, a.ld_sc, t0 * 64, kv_end, d, tid);
+        store_tile<DP, NV, F8>(rk, sK, tid);
+        store_tile<DP, NV, F8>(rv, sV, tid);
+        __syncthreads();
+        constexpr float RESCALE_THR = 6.0f;                  // log2 units: keep the old running max while it grows < 2^6
+        for (int t = t0; t < t1; ++t) {
+            const int kv0 = t * 64;
+            const bool more = t + 1 < t1;
+            if (more) {
+                load_tile<DP, NV, F8>(rk, kbase, ksb, a.ld_kv, a.ld_sc, kv0 + 64, kv_end, d, tid);
+                load_tile<DP, NV, F8>(rv, vbase, vsb, a.ld_kv, a.ld_sc, kv0 + 64, kv_end, d, tid);
+            }
+            if (wave_on && kv0 <= wave_hi) {                 // a wave whose rows all precede this tile has nothing to do here
+                f32x4 st[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) st[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int kk = 0; kk < KS; ++kk) {
+                        const bf16x8 kf = *(const bf16x8*)(sK + offN<DS>(j * 16 + fr, kk * 4 + fq));
+                        st[j] = mfma16(kf, qf[kk], st[j]);
+                    }
+                if (kv0 + 63 > wave_lo) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            if (kv0 + j * 16 + fq * 4 + r > klim) st[j][r] = -INFINITY;
+                }
+                float mx = -INFINITY;                         // max of the RAW scores (scale > 0 commutes with max)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) mx = fmaxf(mx, st[j][r]);
+                mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+                mx *= sl2;
+                // deferred rescale: move the running max (and touch the O accumulators) only when some row's max grew by more than 2^THR
+                const bool grow = mx > m_run + RESCALE_THR || m_run == -INFINITY;
+                if (__any(grow && mx > -INFINITY)) {
+                    const float mn = fmaxf(m_run, mx);
+                    const float alpha = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m_run - mn);
+                    l_run *= alpha;
+#pragma unroll
+                    for (int j = 0; j < NF; ++j) ot[j] *= alpha;
+                    m_run = mn;
+                }
+                const float mref = m_run;
+                float rs = 0.f;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float p = (mref == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(fmaf(st[j][r], sl2, -mref));
+                        st[j][r] = p;
+                        rs += p;
+                    }
+                rs += __shfl_xor(rs, 16, 64);
+                rs += __shfl_xor(rs, 32, 64);
+                l_run += rs;
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk) {
+                    const bf16x8 pb = pack_acc(st[2 * kk], st[2 * kk + 1]);
+#pragma unroll
+                    for (int j = 0; j < NF; ++j) {
+                        const bf16x8 va = read_nat_perm<DS>(sV, kk * 32, j, fr, fq);      // V^T[d][keys perm]
+                        ot[j] = mfma16(va, pb, ot[j]);
+                    }
+                }
+            }
+            __syncthreads();                                 // every wave is done reading this tile
+            if (more) {
+                store_tile<DP, NV, F8>(rk, sK, tid);
+                store_tile<DP, NV, F8>(rv, sV, tid);
+                __syncthreads();
+            }
+        }
+    }
+
+    if (a.nsplit > 1) {                                      // partial: unnormalised O, reference maximum (log2 domain) and sum
+        if (qw0 + fr < R) {
+            const int64_t row = (((int64_t)b * a.Hkv + hk) * a.nsplit + split) * a.rpad + qw0 + fr;
+            float* po = a.ws + row * DP;
+#pragma unroll
+            for (int j = 0; j < NF; ++j) *(f32x4*)(po + j * 16 + fq * 4) = ot[j];
+            if (fq == 0) {
+                float* ml = a.ws + (int64_t)gridDim.z * a.Hkv * a.nsplit * a.rpad * DP + row * 2;
+                ml[0] = m_run; ml[1] = l_run;
+            }
+        }
+        return;
+    }
+    // epilogue: O = O^T / l -> bf16 [row][d] in LDS -> row-contiguous 16-B stores
+    unsigned char* so = smem + wave * (16 * DP * 2);
+    const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;
+#pragma unroll
+    for (int j = 0; j < NF; ++j) {
+        u32x2 w;
+        w.x = pack2bf(ot[j][0] * inv, ot[j][1] * inv);
+        w.y = pack2bf(ot[j][2] * inv, ot[j][3] * inv);
+        *(u32x2*)(so + fr * (DP * 2) + (j * 16 + fq * 4) * 2) = w;
+    }
+    __syncthreads();
+    for (int v = lane; v < 16 * (d >> 3); v += 64) {
+        const int r = v / (d >> 3), c = (v % (d >> 3)) * 8;
+        const int p = qw0 + r;
+        if (p < R) {
+            const int i = p / G, g = p - i * G;
+            *(u32x4*)(a.o + ((int64_t)b * n + i) * a.ld_o + (int64_t)(hk * G + g) * d + c) = *(const u32x4*)(so + r * (DP * 2) + c * 2);
+        }
+    }
+}
+
+// o[row][4 columns] = sum_s 2^(m_s - M) O_s / sum_s 2^(m_s - M) l_s over the key runs of one packed row; a run that saw no key has m = -inf
+template <int DP>
+__global__ __launch_bounds__(NT) void extend_merge_kernel(XArgs a) {
+    const int hk = blockIdx.y, b = blockIdx.z;
+    const int idx = blockIdx.x * NT + threadIdx.x;
+    const int p = idx / (DP / 4), c = (idx % (DP / 4)) * 4;
+    if (p >= a.R || c >= a.d) return;
+    const int64_t row0 = ((int64_t)b * a.Hkv + hk) * a.nsplit * a.rpad + p;
+    const float* ml = a.ws + (int64_t)gridDim.z * a.Hkv * a.nsplit * a.rpad * DP;
+    float M = -INFINITY;
+    for (int s = 0; s < a.nsplit; ++s) M = fmaxf(M, ml[(row0 + s * a.rpad) * 2]);
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    float l = 0.f;
+    for (int s = 0; s < a.nsplit; ++s) {
+        const int64_t row = row0 + s * a.rpad;
+        const float m = ml[row * 2];
+        if (m == -INFINITY) continue;
+        const float w = __builtin_amdgcn_exp2f(m - M);
+        l += w * ml[row * 2 + 1];
+        acc += w * *(const f32x4*)(a.ws + row * DP + c);
+    }
+    const float inv = l > 0.f ? 1.0f / l : 0.f;
+    const int i = p / a.G, g = p - i * a.G;
+    u32x2 w;
+    w.x = pack2bf(acc[0] * inv, acc[1] * inv);
+    w.y = pack2bf(acc[2] * inv, acc[3] * inv);
+    *(u32x2*)(a.o + ((int64_t)b * a.n + i) * a.ld_o + (int64_t)(hk * a.G + g) * a.d + c) = w;
+}
+
+template <int DP, bool F8>
+int launch(const XArgs& a, int64_t B, hipStream_t s) {
+    hipLaunchKernelGGL((extend_kernel<DP, F8>), dim3((unsigned)(a.nqt * a.nsplit), (unsigned)a.Hkv, (unsigned)B), dim3(NT), 0, s, a);
+    if (a.nsplit > 1) {
+        if (mm_launch_status() != MM355_OK) return MM355_ELAUNCH;
+        const unsigned gx = (unsigned)(((int64_t)a.R * (DP / 4) + NT - 1) / NT);
+        hipLaunchKernelGGL((extend_merge_kernel<DP>), dim3(gx, (unsigned)a.Hkv, (unsigned)B), dim3(NT), 0, s, a);
+    }
+    return mm_launch_status();
+}
+
+int pick_dp(int64_t d) { return d <= 64 ? 64 : (d <= 96 ? 96 : 128); }
+
+// eb = bytes per cached element (2: bf16, 1: e4m3); ld_kv / bs_kv arrive in BYTES
+int extend_impl(const mm355_bf16* q, int64_t ld_q, const void* k, const void* v, int64_t ld_kv, int64_t bs_kv, int eb, const float* ks,
+                const float* vs, int64_t ld_sc, int64_t bs_sc, const int32_t* past, int64_t n, int64_t max_kv_len, mm355_bf16* o, int64_t ld_o,
+                int64_t B, int64_t Hq, int64_t Hkv, int64_t d, float scale, float* ws, int64_t ws_floats, void* stream) {
+    if (!q || !k || !v || !past || !o || B <= 0 || n <= 0 || Hq <= 0 || Hkv <= 0 || (Hq % Hkv) || d <= 0 || max_kv_len <= 0 || n > max_kv_len ||
+        max_kv_len > 0x7fffffc0ll || n * (Hq / Hkv) > 0x7fffffc0ll || B > 65535 || Hkv > 65535)
+        return MM355_EINVAL;
+    if ((d & 7) || d > 128) return MM355_EUNSUPPORTED;
+    const uintptr_t amask = eb == 2 ? 15u : 7u;              // one 16-byte (bf16) or 8-byte (e4m3) load per 8 columns
+    if (!mm_aligned16(q) || !mm_aligned16(o) || (ld_q & 7) || (ld_o & 7) || ld_q < Hq * d || ld_o < Hq * d || (((uintptr_t)k | (uintptr_t)v) & amask) ||
+        (ld_kv & (int64_t)amask) || (bs_kv & (int64_t)amask) || ld_kv < Hkv * d * eb)
+        return MM355_EINVAL;
+    if (eb == 1 && (((((uintptr_t)ks) | ((uintptr_t)vs)) & 3u) || ld_sc < Hkv)) return MM355_EINVAL;
+    const int64_t G = Hq / Hkv;
+    if (G != 1 && G != 2 && G != 4 && G != 8) return MM355_EUNSUPPORTED;      // GQA group sizes 1, 2, 4, 8
+    const Plan p = make_plan(B, n, Hq, Hkv, max_kv_len);
+    const int dp = pick_dp(d);
+    if (p.nsplit > 1 && (!ws || (((uintptr_t)ws) & 15u) || ws_floats < B * Hkv * p.nsplit * p.rpad * (dp + 2))) return MM355_EINVAL;
+    XArgs a{q, ld_q, (const unsigned char*)k, (const unsigned char*)v, ld_kv, bs_kv, ks, vs, ld_sc, bs_sc, past, o, ld_o, ws,
+            (int)n, (int)Hkv, (int)d, p.G, p.R, p.nqt, p.nsplit, p.tps, (int)max_kv_len, p.rpad, scale};
+    hipStream_t s = (hipStream_t)stream;
+    if (eb == 2) {
+        switch (dp) {
+            case 64: return launch<64, false>(a, B, s);
+            case 96: return launch<96, false>(a, B, s);
+            default: return launch<128, false>(a, B, s);
+        }
+    }
+    switch (dp) {
+        case 64: return launch<64, true>(a, B, s);
+        case 96: return launch<96, true>(a, B, s);
+        default: return launch<128, true>(a, B, s);
+    }
+}
+
+}  // namespace
+
+extern "C" int64_t mm355_attn_extend_ws_floats(int64_t B, int64_t n, int64_t Hq, int64_t Hkv, int64_t d, int64_t max_kv_len) {
+    if (B <= 0 || n <= 0 || Hq <= 0 || Hkv <= 0 || (Hq % Hkv) || d <= 0 || d > 128 || max_kv_len <= 0) return 0;
+    const Plan p = make_plan(B, n, Hq, Hkv, max_kv_len);
+    return p.nsplit > 1 ? B * Hkv * p.nsplit * p.rpad * (pick_dp(d) + 2) : 0;
+}
+
+extern "C" int mm355_attn_extend(const mm355_bf16* q, int64_t ld_q, const mm355_bf16* k_cache, const mm355_bf16* v_cache, int64_t ld_kv,
+                                 int64_t batch_stride_kv, const int32_t* past, int64_t n, int64_t max_kv_len, mm355_bf16* o, int64_t ld_o,
+                                 int64_t B, int64_t Hq, int64_t Hkv, int64_t d, float scale, float* workspace, int64_t workspace_floats,
+                                 void* stream) {
+    (void)hipGetLastError();
+    return extend_impl(q, ld_q, k_cache, v_cache, ld_kv * 2, batch_stride_kv * 2, 2, nullptr, nullptr, 0, 0, past, n, max_kv_len, o, ld_o, B, Hq, Hkv,
+                       d, scale, workspace, workspace_floats, stream);
+}
+
+extern "C" int mm355_attn_extend_f8(const mm355_bf16* q, int64_t ld_q, const uint8_t* k_cache, const uint8_t* v_cache, int64_t ld_kv_bytes,
+                                    int64_t batch_stride_kv_bytes, const float* k_scale, const float* v_scale, int64_t ld_scale,
+                                    int64_t batch_stride_scale, int fmt, const int32_t* past, int64_t n, int64_t max_kv_len, mm355_bf16* o,
+                                    int64_t ld_o, int64_t B, int64_t Hq, int64_t Hkv, int64_t d, float scale, float* workspace,
+                                    int64_t workspace_floats, void* stream) {
+    (void)hipGetLastError();
+    if (fmt != MM355_KV8_E4M3 || !k_scale || !v_scale) return MM355_EINVAL;
+    return extend_impl(q, ld_q, k_cache, v_cache, ld_kv_bytes, batch_stride_kv_bytes, 1, k_scale, v_scale, ld_scale, batch_stride_scale, past, n,
+                       max_kv_len, o, ld_o, B, Hq, Hkv, d, scale, workspace, workspace_floats, stream);
+}

@@ -40,7 +40,11 @@ VARIANTS = {"fuse_swiglu": True, "fuse_rope": True, "fuse_swiglu_bwd": True, "de
             "prefill_fused": True,
             # quantised layers (quantize_decoder_): projections of the prompt pass and of decode steps of more than 16 sequences on the w8
             # split-K GEMM (mm355_gemm_w8*: the weight bytes streamed once); off: every such projection through the W8Scratch route
-            "w8_gemm": True}
+            "w8_gemm": True,
+            # n > 1 new rows on a filled cache (a follow-up turn, a prompt run in chunks): ONE pass over the weights with mm355_attn_extend
+            # (decoder_extend); off, or fewer than extend_min_rows rows: one captured decode step per row (two rows: the pass's floor of one
+            # split-K stream over the weights is 0.81 - 1.46 x two GEMV steps, profiles/extend_pass.md)
+            "extend_pass": True, "extend_min_rows": 3}
 
 
 def set_variant(name, value):
@@ -898,6 +902,132 @@ def _prefill_layers_fused(x, layers, meta, cache, row, ident):
         else:
             x = _proj(on8, rec, "down", (mlp.down_proj.weight,), ops.gemm_w8, ops.gemm_splitk, act, residual=x2)
     return x
+
+
+def _attend_extend(q, cache, i, row, past_dev, n, bound, meta):
+    """attention of the n new rows of sequence `row` over layer i of the cache, which already holds them"""
+    if cache.kv8 is not None:
+        return ops.attn_extend_f8(q, cache.k[i, row:row + 1], cache.v[i, row:row + 1], cache.k_scale[i, row:row + 1],
+                                  cache.v_scale[i, row:row + 1], past_dev, n, bound, meta.Hq, meta.Hkv, meta.d, meta.scale)
+    return ops.attn_extend(q, cache.k[i, row:row + 1], cache.v[i, row:row + 1], past_dev, n, bound, meta.Hq, meta.Hkv, meta.d, meta.scale)
+
+
+def _append_rows(qkv, cache, i, row, past, ident, meta):
+    """the rotated k and the v columns of the new rows -> cache rows past .. past + n - 1 of layer i (an fp8_e4m3 cache: quantised on the way)"""
+    nq, nk = meta.Hq * meta.d, meta.Hkv * meta.d
+    n = qkv.shape[0]
+    if cache.kv8 is not None:
+        ops.kv_quant_f8(qkv[:, nq:nq + nk], meta.Hkv, meta.d, cache.k[i, row:row + 1], cache.k_scale[i, row:row + 1], row0=past)
+        ops.kv_quant_f8(qkv[:, nq + nk:], meta.Hkv, meta.d, cache.v[i, row:row + 1], cache.v_scale[i, row:row + 1], row0=past)
+    else:
+        ops.rows_gather(qkv[:, nq:nq + nk], ident, out=cache.k[i, row, past:past + n])
+        ops.rows_gather(qkv[:, nq + nk:], ident, out=cache.v[i, row, past:past + n])
+
+
+def decoder_extend(x, layers, meta, cache, row=0):
+    """n new rows of sequence `row` on its FILLED cache in one pass over the weights: x [n, h] -> hidden rows [n, h] (pre final norm); the rows
+    sit at positions past .. past + n - 1 (past = cache.lengths[row] >= 1) and afterwards cache.lengths[row] == past + n.  A follow-up turn
+    of a conversation, a slice of a prompt run in chunks, candidate tokens scored against a cache (then KVCache.set_length back).
+    _prefill_layers_fused with three differences: the positions are past + arange(n), attention is mm355_attn_extend over the cache rows
+    (the append comes first), and an fp8_e4m3 cache is read back quantised -- the new rows are rotated in the q|k|v activation, quantised
+    into the cache at row past and attended from there: the semantics of n decode steps (every row sees the quantised form of all rows, its
+    own included), not of the first prompt pass.  The projections take the prompt pass's routes (w8_route, W8Scratch, the split-K limits);
+    where _prefill_layers_fused does not apply (more than 4096 rows, q|k|v not split, d % 16 != 0) the plain decoder_layer_forward route
+    with mm355_rope_qk_pos and a row copy into the cache."""
+    n, h = x.shape
+    past = int(cache.lengths[row])
+    if past < 1:
+        raise ValueError(f"decoder_extend needs a filled cache, sequence {row} holds no rows: the first rows of a sequence go through decoder_prefill")
+    if past + n > cache.max_len:
+        raise ValueError(f"KV cache capacity of {cache.max_len} rows is too small for {past} cached + {n} new rows")
+    if torch.is_grad_enabled():
+        raise RuntimeError("decoder_extend is an inference pass (torch.no_grad())")
+    nq = meta.Hq * meta.d
+    bound = past + n
+    ident = torch.arange(n, device=x.device, dtype=torch.int32)
+    pos = ident + past
+    past_dev = pos[:1]
+    splitk = VARIANTS["prefill_splitk"] and n <= 4096
+    wq_shape = ((meta.Hq + 2 * meta.Hkv) * meta.d, h)
+    if splitk and VARIANTS["prefill_fused"] and meta.d % 16 == 0 and ops.gemm_splitk_splits(n, *wq_shape):
+        n1 = None
+        for i, layer in enumerate(layers):
+            params_ready(layer)
+            rec = getattr(layer, "w8", None)
+            on8 = w8_route(layer, n, gu_rows=PROMPT_GU_SPLITK_ROWS)
+            att, mlp = layer.self_attn, layer.mlp
+            if n1 is None:
+                n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
+            wq = (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight)
+            if cache.kv8 is not None:                         # plain split projection, rotation in place, quantising append (no fused f8 form)
+                qkv = _proj(on8, rec, "qkv", wq, ops.gemm_w8, ops.gemm_splitk, n1)
+                ops.rope_qk_(qkv, 1, n, meta.Hq, meta.Hkv, meta.d, meta.cos, meta.sin, pos_offset=past_dev)
+                _append_rows(qkv, cache, i, row, past, ident, meta)
+            else:
+                kc, vc = cache.k[i, row], cache.v[i, row]
+                rows_k = kc.as_strided((n, kc.shape[0], kc.shape[1]), (0, kc.stride(0), 1))
+                rows_v = vc.as_strided((n, vc.shape[0], vc.shape[1]), (0, vc.stride(0), 1))
+                qkv = _proj(on8, rec, "qkv", wq, ops.gemm_w8_rope_append, ops.gemm_splitk_rope_append, n1, meta.Hq, meta.Hkv, meta.d,
+                            meta.cos, meta.sin, pos, rows_k, rows_v)
+            o = _attend_extend(qkv[:, :nq], cache, i, row, past_dev, n, bound, meta)
+            x2, n2 = _proj(on8, rec, "o", (att.o_proj.weight,), ops.gemm_w8_norm, ops.gemm_splitk_norm, o,
+                           layer.post_attention_layernorm.weight, meta.eps, residual=x)
+            if "gu" in on8:
+                act = ops.gemm_w8_swiglu(n2, *rec.gu, meta.I)
+            else:
+                wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
+                if VARIANTS["fuse_swiglu"] and ops.gemm_swiglu_supported(n2, wgu, meta.I):
+                    _, act = ops.gemm_swiglu(n2, wgu, meta.I)
+                elif n <= PROMPT_GU_SPLITK_ROWS:
+                    act = ops.gemm_splitk_swiglu(n2, wgu, meta.I)
+                else:
+                    act = ops.swiglu_fwd(ops.gemm(n2, wgu), meta.I)
+            if i + 1 < len(layers):
+                params_ready(layers[i + 1])
+                x, n1 = _proj(on8, rec, "down", (mlp.down_proj.weight,), ops.gemm_w8_norm, ops.gemm_splitk_norm, act,
+                              layers[i + 1].input_layernorm.weight, meta.eps, residual=x2)
+            else:
+                x = _proj(on8, rec, "down", (mlp.down_proj.weight,), ops.gemm_w8, ops.gemm_splitk, act, residual=x2)
+    else:
+        mm = ops.gemm_splitk if splitk else ops.gemm
+        for i, layer in enumerate(layers):
+            params_ready(layer)
+            w8_materialize(layer)                             # (a quantised layer: the scratch route, as decoder_prefill's plain pass)
+            att, mlp = layer.self_attn, layer.mlp
+            wqkv = fused_weight([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight])
+            wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
+            qkv = mm(ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps), wqkv)
+            ops.rope_qk_(qkv, 1, n, meta.Hq, meta.Hkv, meta.d, meta.cos, meta.sin, pos_offset=past_dev)
+            _append_rows(qkv, cache, i, row, past, ident, meta)
+            o = _attend_extend(qkv[:, :nq], cache, i, row, past_dev, n, bound, meta)
+            x2 = mm(o, att.o_proj.weight, residual=x)
+            n2 = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
+            if VARIANTS["fuse_swiglu"] and ops.gemm_swiglu_supported(n2, wgu, meta.I):
+                _, act = ops.gemm_swiglu(n2, wgu, meta.I)
+            else:
+                gu = ops.gemm_splitk(n2, wgu) if (splitk and n <= PROMPT_GU_SPLITK_ROWS) else ops.gemm(n2, wgu)
+                act = ops.swiglu_fwd(gu, meta.I)
+            x = mm(act, mlp.down_proj.weight, residual=x2)
+    cache.set_length(past + n, row)
+    return x
+
+
+def decoder_prefill_chunked(x, layers, meta, cache, chunk, row=0):
+    """decoder_prefill of one sequence in slices of `chunk` rows: the first through decoder_prefill, every further one (the last may be short)
+    through decoder_extend against the rows cached so far.  Bounds the live activations by the slice, and keeps a quantised decoder on the w8
+    split-K GEMM where the whole prompt would leave it (W8Scratch).  An fp8_e4m3 cache: the slices after the first read the cache quantised."""
+    L = x.shape[0]
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError(f"prefill chunk of {chunk} rows: need at least 1")
+    if L <= chunk:
+        return decoder_prefill(x, layers, meta, cache, row)
+    assert meta.B == 1
+    head = LayerMeta(1, chunk, meta.Hq, meta.Hkv, meta.d, meta.I, meta.eps, meta.cos, meta.sin, None)
+    outs = [decoder_prefill(x[:chunk].contiguous(), layers, head, cache, row)]
+    for r0 in range(chunk, L, chunk):
+        outs.append(decoder_extend(x[r0:min(L, r0 + chunk)].contiguous(), layers, meta, cache, row))
+    return torch.cat(outs, 0)
 
 
 class W8Scratch:

@@ -105,9 +105,14 @@ class HipKVCache(DynamicCache):
     reference's `forward` does: the batch goes to one HF forward per step).  HF only asks a cache for its length and, under beam search,
     to re-order its batch rows (`reorder_cache`); the tensors never leave the device or change layout."""
 
-    def __init__(self, capacity=None, kv_format=None, **kw):
+    def __init__(self, capacity=None, kv_format=None, prefill_chunk=None, **kw):
         super().__init__(**kw)
+        if prefill_chunk is not None and int(prefill_chunk) < 1:
+            raise ValueError(f"HipKVCache(prefill_chunk={prefill_chunk}): a prompt is run in slices of at least 1 row (None: in one pass)")
         self.capacity = capacity          # rows to allocate at the first (prompt) pass; None: prompt + 1024 + 2
+        # a prompt of more rows runs its first prefill_chunk rows as the prompt pass and every further slice as an extend pass against the
+        # rows cached so far (functional.decoder_extend); None: config.mm355_prefill_chunk_rows, whose default None is one pass
+        self.prefill_chunk = None if prefill_chunk is None else int(prefill_chunk)
         self.kv_format = kv_format        # "bf16" / "fp8_e4m3" (functional.KVCache); None: config.mm355_kv_cache_format
         self.kv = None                    # functional.KVCache of the whole batch
         self.pads = []                    # left-padding rows of every sequence in the batch HF sees (never cached: kv.lengths count real rows)
@@ -679,6 +684,16 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
             raise ValueError(f"unknown KV cache format {fmt!r}; known: {', '.join(ops.KV_FORMATS)}")
         return fmt
 
+    def _prefill_chunk_rows(self, cache=None):
+        """Rows per slice of a chunked prompt pass: the cache's own `prefill_chunk` if it has one, else config.mm355_prefill_chunk_rows
+        (None, the default: the prompt in one pass)."""
+        n = getattr(cache, "prefill_chunk", None)
+        if n is None:
+            n = getattr(self.config, "mm355_prefill_chunk_rows", None)
+            if n is not None and int(n) < 1:
+                raise ValueError(f"config.mm355_prefill_chunk_rows = {n}: a prompt is run in slices of at least 1 row (None: in one pass)")
+        return None if n is None else int(n)
+
     def _greedy_decode_cached(self, inputs_embeds, start_image_token_id, end_image_token_id, eos_token_id, max_new_tokens,
                               output_image):
         if inputs_embeds.shape[0] != 1:
@@ -694,7 +709,11 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         cos, sin = self.model.rope_tables(max_len, dev)
         meta.cos, meta.sin = cos, sin
         cache = F.KVCache(len(self.model.layers), max_len, meta.Hkv * meta.d, dev, Hq=meta.Hq, d=meta.d, fmt=self._kv_cache_format())
-        x = F.decoder_prefill(inputs_embeds.reshape(L0, h).contiguous(), self.model.layers, meta, cache)[-1:].contiguous()
+        chunk = self._prefill_chunk_rows()
+        if chunk is None:
+            x = F.decoder_prefill(inputs_embeds.reshape(L0, h).contiguous(), self.model.layers, meta, cache)[-1:].contiguous()
+        else:
+            x = F.decoder_prefill_chunked(inputs_embeds.reshape(L0, h).contiguous(), self.model.layers, meta, cache, chunk)[-1:].contiguous()
         stepper = F.DecodeStepGraph(self.model.layers, meta, cache, cos, sin, h, dev)
         in_image_mode = False
         generated, image_embeds = [], []
@@ -765,10 +784,28 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         return out
 
     def _decode_batch(self, x, cache):
-        """New rows x [B, n, h] (usually n = 1) appended against the batch's cache, every position in ONE pass for all B sequences ->
-        their hidden rows [B, n, h] (pre final norm)."""
+        """New rows x [B, n, h] (the hook of n = 1: one row per sequence and step) appended against the batch's cache, every position in ONE
+        pass for all B sequences -> their hidden rows [B, n, h] (pre final norm)."""
         outs = [cache.stepper.step(x[:, t].contiguous()).clone() for t in range(x.shape[1])]
         return outs[0].unsqueeze(1) if len(outs) == 1 else torch.stack(outs, 1)
+
+    def _extend_batch(self, x, cache, rows=None):
+        """n > 1 new rows per sequence x [B, n, h] on the FILLED cache -> their hidden rows [B, n, h] (pre final norm): one extend pass per
+        sequence (functional.decoder_extend: the weights streamed once for its n rows), one sequence after the other as ragged prompts run.
+        rows: the sequences of the cache the B row blocks belong to (default: all of them, in order).  functional.set_variant("extend_pass",
+        False), or fewer than VARIANTS["extend_min_rows"] rows: the captured decode step once per row (all sequences at once)."""
+        B, n, h = x.shape
+        kv = cache.kv
+        rows = list(range(kv.batch)) if rows is None else [int(b) for b in rows]
+        if len(rows) != B:
+            raise ValueError(f"{B} row blocks for {len(rows)} sequences")
+        need = max(kv.lengths[b] for b in rows) + n
+        if need > kv.max_len:
+            raise ValueError(f"HipKVCache capacity {kv.max_len} is smaller than the {need} rows this call extends a sequence to "
+                             "(size it with HipKVCache(capacity=...); a cache is not grown)")
+        if (not F.VARIANTS["extend_pass"] or n < F.VARIANTS["extend_min_rows"]) and rows == list(range(kv.batch)):
+            return MetaMorphLlamaForCausalLM._decode_batch(self, x, cache)
+        return torch.stack([F.decoder_extend(x[j].contiguous(), self.model.layers, cache.meta, kv, row=b) for j, b in enumerate(rows)], 0)
 
     def _rows_logits(self, rows, return_hidden=False):
         """final norm + lm_head -> fp32 logits [n, V] (reference :349-359 final norm, :393-399); return_hidden: (logits, normed rows)."""
@@ -790,8 +827,15 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
             inputs_embeds = self.model.embed_tokens(input_ids)
         if inputs_embeds.dtype != BF16:
             raise TypeError(f"inputs_embeds must be bf16, got {inputs_embeds.dtype}")
-        B, n, h = inputs_embeds.shape
         cache = past_key_values
+        if isinstance(cache, HipKVCache) and cache.kv is not None and attention_mask is not None and inputs_embeds.shape[1] > 1:
+            # continuing a conversation: generate(inputs=<whole conversation>, past_key_values=<cache holding a prefix of it>).  The mask
+            # covers cached + new positions whatever the installed transformers did with the inputs_embeds of a filled cache, so the rows
+            # beyond (mask length - cached length) from the end are the cached prefix: only the rest goes through the decoder
+            new = int(attention_mask.shape[1]) - cache.get_seq_length()
+            if 0 < new < inputs_embeds.shape[1]:
+                inputs_embeds = inputs_embeds[:, -new:]
+        B, n, h = inputs_embeds.shape
         if cache is None:
             cache = HipKVCache()
         if not isinstance(cache, HipKVCache):
@@ -817,13 +861,31 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
                                                   "between the prompt and the generated tokens in the reference as well")
                     pads[b] = n - nb
             cache.pads = pads
-            outs = self._prefill_batch([inputs_embeds[b, pads[b]:].reshape(n - pads[b], h) for b in range(B)], cache)
+            seqs = [inputs_embeds[b, pads[b]:].reshape(n - pads[b], h) for b in range(B)]
+            chunk = self._prefill_chunk_rows(cache)
+            if chunk is None or max(x.shape[0] for x in seqs) <= chunk:
+                outs = self._prefill_batch(seqs, cache)
+            else:
+                if cache.capacity is None:                    # (the prompt hook sizes the cache from the rows it is given)
+                    cache.capacity = max(x.shape[0] for x in seqs) + 1024 + 2
+                outs = [[o] for o in self._prefill_batch([x[:chunk] for x in seqs], cache)]
+                for r0 in range(chunk, max(x.shape[0] for x in seqs), chunk):
+                    live = [b for b in range(B) if seqs[b].shape[0] > r0]
+                    if len({min(seqs[b].shape[0], r0 + chunk) for b in live}) == 1:      # one slice length: one call for all of them
+                        ys = self._extend_batch(torch.stack([seqs[b][r0:r0 + chunk] for b in live], 0), cache,
+                                                **({} if len(live) == B else {"rows": live}))
+                        for j, b in enumerate(live):
+                            outs[b].append(ys[j])
+                    else:
+                        for b in live:
+                            outs[b].append(self._extend_batch(seqs[b][None, r0:r0 + chunk], cache, rows=[b])[0])
+                outs = [torch.cat([t.to(o[0].dtype) for t in o], 0) for o in outs]
             # padding positions: rows nobody reads (HF takes logits[:, -1])
             rows = torch.cat([r if not pads[b] else torch.cat([r.new_zeros((pads[b], h)), r], 0) for b, r in enumerate(outs)], 0)
         else:
             if len(cache.pads) != B:
                 raise ValueError(f"cache holds {len(cache.pads)} sequences, the step brings {B}")
-            rows = self._decode_batch(inputs_embeds, cache).reshape(B * n, h)
+            rows = (self._decode_batch if n == 1 else self._extend_batch)(inputs_embeds, cache).reshape(B * n, h)
         logits, hidden = self._rows_logits(rows.contiguous(), return_hidden=True)
         logits, hidden = logits.view(B, n, -1), hidden.view(B, n, h)
         if return_dict is False:

@@ -553,6 +553,50 @@ def attn_decode_f8(q, k8, v8, k_scale, v_scale, kv_lens, max_kv_len, Hq, Hkv, d,
     return out
 
 
+# ------------------------------------------------------------------------------------------------ extending a filled cache by n rows
+
+def _extend_args(q, past, n, max_kv_len, rows, Hq, Hkv, d, out, workspace):
+    B = past.shape[0]
+    pq, R, W, ldq = _rows2d(q)
+    assert q.dtype == BF16 and R == B * n and W == Hq * d, (q.shape, B, n, Hq, d)
+    assert past.dtype == torch.int32 and n <= max_kv_len <= rows, (n, max_kv_len, rows)
+    out = torch.empty((B * n, Hq * d), device=q.device, dtype=BF16) if out is None else out
+    po, Ro, Wo, ldo = _rows2d(out)
+    assert out.dtype == BF16 and (Ro, Wo) == (R, W)
+    n_ws = int(_L().mm355_attn_extend_ws_floats(B, n, Hq, Hkv, d, max_kv_len))
+    ws = workspace
+    if n_ws and (ws is None or ws.numel() < n_ws):
+        ws = torch.empty(n_ws, device=q.device, dtype=torch.float32)
+    return B, pq, ldq, out, po, ldo, ws, (0 if ws is None else ws.numel())
+
+
+def attn_extend(q, k, v, past, n, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None):
+    """n new rows per sequence against a filled cache (mm355_attn_extend): q [B*n, Hq*d] bf16, already rotated, row (b, i) at b*n + i (may be
+    a column block of a wider tensor); k / v [B, rows, Hkv*d] bf16 already holding the chunk's own rows at past[b] .. past[b]+n-1; past int32
+    [B] on the device; max_kv_len a host bound with past[b] + n <= max_kv_len <= rows.  Row (b, i) attends the keys j <= past[b] + i."""
+    _chk_dev(q, k, v, past, out)
+    assert k.dim() == 3 and k.dtype == BF16 and k.shape == v.shape and k.stride(2) == 1 and v.stride() == k.stride() and k.shape[2] == Hkv * d
+    assert k.shape[0] >= past.shape[0]
+    B, pq, ldq, out, po, ldo, ws, n_ws = _extend_args(q, past, n, max_kv_len, k.shape[1], Hq, Hkv, d, out, workspace)
+    _lib.check(_L().mm355_attn_extend(pq, ldq, k.data_ptr(), v.data_ptr(), k.stride(1), k.stride(0), past.data_ptr(), n, max_kv_len, po, ldo,
+                                      B, Hq, Hkv, d, scale, _p(ws), n_ws, _stream()), f"mm355_attn_extend B={B} n={n} Hq={Hq} Hkv={Hkv} d={d}")
+    return out
+
+
+def attn_extend_f8(q, k8, v8, k_scale, v_scale, past, n, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None):
+    """attn_extend() over an e4m3 cache: k8 / v8 [B, rows, Hkv*d] uint8, k_scale / v_scale [B, rows, Hkv] f32 (mm355_attn_extend_f8): equal to
+    attn_extend() on dequant_kv8() of the cache bit for bit."""
+    _chk_dev(q, k8, v8, k_scale, v_scale, past, out)
+    assert k8.shape == v8.shape and k8.stride() == v8.stride() and k_scale.stride() == v_scale.stride() and k8.shape[0] >= past.shape[0]
+    ldb, bsb, ldsc, bssc = _kv8_cache(k8, k_scale, Hkv, d)
+    _kv8_cache(v8, v_scale, Hkv, d)
+    B, pq, ldq, out, po, ldo, ws, n_ws = _extend_args(q, past, n, max_kv_len, k8.shape[1], Hq, Hkv, d, out, workspace)
+    _lib.check(_L().mm355_attn_extend_f8(pq, ldq, k8.data_ptr(), v8.data_ptr(), ldb, bsb, k_scale.data_ptr(), v_scale.data_ptr(), ldsc, bssc,
+                                         KV8_E4M3, past.data_ptr(), n, max_kv_len, po, ldo, B, Hq, Hkv, d, scale, _p(ws), n_ws, _stream()),
+               f"mm355_attn_extend_f8 B={B} n={n} Hq={Hq} Hkv={Hkv} d={d}")
+    return out
+
+
 def transpose(x, out=None, ld_out=None):
     """out[c, r] = x[r, c]"""
     _chk_dev(x, out)
