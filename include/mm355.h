@@ -380,6 +380,39 @@ int mm355_dequant_w8_bf16(const uint8_t* Wq, int64_t ldw_bytes, const float* sca
                           int64_t N, int64_t K, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The decode GEMVs over weight-only MXFP4 (the reference's other quantised mode: metamorph/model/builder.py:13-25, load_4bit=True; OCP MX,
+ * not bitsandbytes' NF4).  fmt MM355_W4_MXFP4, K % 32 == 0: W[N][K] stored as e2m1 nibbles Wq[N][K/2] (row stride ldw_bytes; byte j of a
+ * row holds k = 2j in bits 3:0 and k = 2j+1 in bits 7:4, the torch.float4_e2m1fn_x2 order; a nibble = sign (bit 3) + a code for |v| in
+ * {0, 0.5, 1, 1.5, 2, 3, 4, 6}) plus one e8m0 scale byte per 32 consecutive k, S[N][K/32] (row stride lds_bytes): dequantised value
+ * Wd[n][k] = e2m1(nibble) * 2^(S[n][k/32] - 127), exactly a bf16 value for S in 2 .. 252 (what ops.quantize_w4 emits; never 0xFF).
+ * 4.25 bits per weight.  Coarser than FP8 (relative RMS weight error 0.114 against 0.026 on Gaussian weights): opt-in.
+ *   gemv_w4: y[m][n] = epilogue(sum_k fp32(Wd[n][k]) * fp32(x[m][k])), x bf16, fp32 accumulation, the group scale inside the widening
+ *         conversion (v_cvt_scalef32_pk_bf16_fp4: a byte and its scale -> a packed bf16 pair), nothing multiplied after the sum; flags
+ *         and epilogue as mm355_gemv_bf16.  M <= 16 rows (more: MM355_EUNSUPPORTED -- mm355_dequant_w4_bf16 + the bf16 GEMMs).  Up to four
+ *         rows on v_dot2c_f32_bf16, 5 .. 16 on v_mfma_f32_16x16x32_bf16; a 16-byte load is one scale group.  fmt other than
+ *         MM355_W4_MXFP4, K % 32 != 0, ldw_bytes % 16 != 0, lds_bytes < K / 32, a NULL S or misaligned pointers: MM355_EINVAL before any
+ *         launch.  32-bit byte offsets: N * ldw_bytes < 3.75 GiB, else MM355_EUNSUPPORTED.
+ *   gemv_swiglu_w4 / gemv_rope_append_w4: the twins of mm355_gemv_swiglu_w8 / mm355_gemv_rope_append_w8 (S, lds_bytes in place of scale;
+ *         same row limits and MM355_EUNSUPPORTED cases): the bits of mm355_gemv_w4 + mm355_swiglu_fwd, of mm355_gemv_w4 +
+ *         mm355_rope_kv_append, and with norm_w of mm355_rmsnorm_fwd in front.
+ *   dequant_w4_bf16: out[n][k] = bf16(Wd[n][k]), exact (no rounding), a plain streaming kernel for every route without a w4 kernel (more
+ *         than 16 rows, prompt passes).  ld_out % 8 == 0, out 16-byte aligned.
+ * ------------------------------------------------------------------------------------------------ */
+#define MM355_W4_MXFP4 2
+int mm355_gemv_w4(const mm355_bf16* x, int64_t ldx, const uint8_t* Wq, int64_t ldw_bytes, const uint8_t* S, int64_t lds_bytes, int fmt,
+                  void* y, int64_t ldy, int64_t M, int64_t N, int64_t K, const mm355_bf16* bias, const mm355_bf16* residual, int64_t ldr,
+                  uint32_t flags, void* stream);
+int mm355_gemv_swiglu_w4(const mm355_bf16* x, int64_t ldx, const uint8_t* Wq, int64_t ldw_bytes, const uint8_t* S, int64_t lds_bytes, int fmt,
+                         mm355_bf16* act, int64_t ld_act, int64_t M, int64_t I, int64_t K, const mm355_bf16* norm_w, float eps, void* stream);
+int mm355_gemv_rope_append_w4(const mm355_bf16* x, int64_t ldx, const uint8_t* Wq, int64_t ldw_bytes, const uint8_t* S, int64_t lds_bytes,
+                              int fmt, mm355_bf16* qkv, int64_t ld_qkv, int64_t M, int64_t Hq, int64_t Hkv, int64_t d, int64_t K,
+                              const mm355_bf16* norm_w, float eps, const mm355_bf16* cos_t, const mm355_bf16* sin_t,
+                              const int32_t* positions, mm355_bf16* k_cache, mm355_bf16* v_cache, int64_t ld_kv,
+                              int64_t batch_stride_kv, void* stream);
+int mm355_dequant_w4_bf16(const uint8_t* Wq, int64_t ldw_bytes, const uint8_t* S, int64_t lds_bytes, int fmt, mm355_bf16* out, int64_t ld_out,
+                          int64_t N, int64_t K, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * The split-K GEMM over the same weight-only FP8 format: the prompt pass and decode steps of MORE than 16 sequences of a quantised decoder
  * stream the weight as bytes instead of dequantising it into a scratch buffer first (reference: the nn.Linear calls of the 8-bit model,
  * metamorph/model/builder.py:13-25 with metamorph_llama.py:665-717).  x[M][K] bf16, Wq[N][K] e4m3fn bytes (row stride ldw_bytes), scale[N] fp32.

@@ -1046,7 +1046,7 @@ class W8Scratch:
     def view(self, rec, name):
         if self.bufs is None:
             self.bufs = {}
-        shape = tuple(getattr(rec, name)[0].shape)
+        shape = rec.shape(name)
         buf = self.bufs.get(name)
         if buf is None or tuple(buf.shape) != shape:
             buf = self.bufs[name] = torch.empty(shape, device=rec.qkv[0].device, dtype=BF16)
@@ -1058,6 +1058,13 @@ class W8Layer:
     (bytes uint8 [N, K], scale f32 [N]) -- the FUSED matrices, as fused_weight concatenates them.  `released`: the layer's bf16 projection
     parameters no longer hold storage of their own (they alias the model's W8Scratch while a scratch route runs)."""
     NAMES = ("qkv", "o", "gu", "down")
+    ON_GEMM = True                                           # the format has a split-K GEMM on its bytes (mm355_gemm_w8*)
+    gemv, gemv_swiglu, gemv_rope_append, dequant = (staticmethod(f) for f in (ops.gemv_w8, ops.gemv_swiglu_w8, ops.gemv_rope_append_w8,
+                                                                                ops.dequant_w8))
+
+    @staticmethod
+    def quantize(w, pow2_scales):
+        return ops.quantize_w8(w, pow2_scales)
 
     def __init__(self, layer, scratch, pow2_scales=False, keep_bf16=False):
         att, mlp = layer.self_attn, layer.mlp
@@ -1065,7 +1072,7 @@ class W8Layer:
                        "gu": [mlp.gate_proj.weight, mlp.up_proj.weight], "down": [mlp.down_proj.weight]}
         self.rows = {n: [p.shape[0] for p in ps] for n, ps in self.params.items()}
         for n in self.NAMES:
-            setattr(self, n, ops.quantize_w8(torch.cat([p.data for p in self.params[n]], 0), pow2_scales))
+            setattr(self, n, self.quantize(torch.cat([p.data for p in self.params[n]], 0), pow2_scales))
         self.scratch = scratch
         self.released = not keep_bf16
         for ps in self.params.values():
@@ -1077,6 +1084,10 @@ class W8Layer:
                     p.data = p.data.new_empty((0, p.shape[1]))
                     p.requires_grad_(False)
 
+    def shape(self, name):
+        """(N, K) of the fused weight `name`."""
+        return (sum(self.rows[name]), self.params[name][0].shape[1])
+
     def materialize(self, names=NAMES):
         """The projections `names` of this layer as bf16 for a route without w8 kernels (see W8Scratch), one matrix at a time: a projection
         that runs on its bytes is not dequantised.  A layer that kept its bf16 parameters runs on them."""
@@ -1084,18 +1095,31 @@ class W8Layer:
             return
         for n in names:
             buf = self.scratch.view(self, n)
-            ops.dequant_w8(*getattr(self, n), out=buf)
+            self.dequant(*getattr(self, n), out=buf)
             off = 0
             for p, rows in zip(self.params[n], self.rows[n]):
                 p.data = buf[off:off + rows]
                 off += rows
 
 
+class W4Layer(W8Layer):
+    """W8Layer in format "mxfp4" (ops.quantize_w4): each fused matrix as (nibbles uint8 [N, K/2], e8m0 group scales uint8 [N, K/32]).
+    Decode steps of up to 16 rows run on the mm355_gemv*_w4 kernels; there is no w4 split-K GEMM, so every other route dequantises
+    into the W8Scratch (mm355_dequant_w4_bf16, exact) and runs the bf16 GEMMs."""
+    ON_GEMM = False
+    gemv, gemv_swiglu, gemv_rope_append, dequant = (staticmethod(f) for f in (ops.gemv_w4, ops.gemv_swiglu_w4, ops.gemv_rope_append_w4,
+                                                                                ops.dequant_w4))
+
+    @staticmethod
+    def quantize(w, pow2_scales):                            # (the group scales are powers of two by format: pow2_scales has no effect)
+        return ops.quantize_w4(w)
+
+
 def refuse_w8_params(params, who):
     """Parameters of a decoder quantised with quantize_decoder_ cannot be trained or sharded: refused by name."""
     flat = [p for g in params for p in (g["params"] if isinstance(g, dict) else [g])]
     if any(getattr(p, "w8_quantized", False) for p in flat):
-        raise RuntimeError(f"{who}: the decoder was quantised with quantize_decoder_ (weight-only FP8 is an inference format); "
+        raise RuntimeError(f"{who}: the decoder was quantised with quantize_decoder_ (weight-only FP8 / MXFP4 are inference formats); "
                            "ZeRO wrapping and training of quantised weights are not supported")
 
 
@@ -1125,9 +1149,9 @@ def w8_on_gemm(layer, rows, gu_rows=None):
     quantised."""
     rec = getattr(layer, "w8", None)
     on8 = set()
-    if rec is not None and VARIANTS["w8_gemm"]:
+    if rec is not None and rec.ON_GEMM and VARIANTS["w8_gemm"]:
         for n in W8Layer.NAMES:
-            N, K = getattr(rec, n)[0].shape
+            N, K = rec.shape(n)
             cap = (W8_GEMM_MAX_ROWS if ops.gemm_splitk_splits(rows, N, K) else W8_GEMM_UNSPLIT_MAX_ROWS)[n]
             if n == "gu" and gu_rows is not None:
                 cap = min(cap, gu_rows)
@@ -1162,7 +1186,8 @@ def _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, k
 
 
 def _decode_rows16_w8(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound, kv8=None):
-    """_decode_rows16 on layers that carry a W8Layer record: the same five / seven launches per layer on the mm355_gemv*_w8 kernels."""
+    """_decode_rows16 on layers that carry a W8Layer record: the same five / seven launches per layer on the record's own kernels
+    (W8Layer: mm355_gemv*_w8, W4Layer: mm355_gemv*_w4)."""
     nq = meta.Hq * meta.d
     fused = VARIANTS["decode_fused"] and meta.I % 2 == 0 and meta.d % 4 == 0
     for i, layer in enumerate(layers):
@@ -1170,29 +1195,29 @@ def _decode_rows16_w8(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_
         if fused:
             fold = x.shape[0] <= VARIANTS["decode_fold_rows"]
             if kv8 is not None:                              # fp8_e4m3 cache: norm, plain projection, quantising append, attention over the bytes
-                qkv = ops.gemv_w8(ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps), *rec.qkv)
+                qkv = rec.gemv(ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps), *rec.qkv)
                 o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound)
             else:
                 n1 = x if fold else ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
-                qkv = ops.gemv_rope_append_w8(n1, *rec.qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i],
+                qkv = rec.gemv_rope_append(n1, *rec.qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i],
                                               norm_w=layer.input_layernorm.weight if fold else None, eps=meta.eps)
                 o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
-            x2 = ops.gemv_w8(o, *rec.o, residual=x)
+            x2 = rec.gemv(o, *rec.o, residual=x)
             n2 = x2 if fold else ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
-            act = ops.gemv_swiglu_w8(n2, *rec.gu, meta.I, norm_w=layer.post_attention_layernorm.weight if fold else None, eps=meta.eps)
-            x = ops.gemv_w8(act, *rec.down, residual=x2)
+            act = rec.gemv_swiglu(n2, *rec.gu, meta.I, norm_w=layer.post_attention_layernorm.weight if fold else None, eps=meta.eps)
+            x = rec.gemv(act, *rec.down, residual=x2)
             continue
         n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
-        qkv = ops.gemv_w8(n1, *rec.qkv)
+        qkv = rec.gemv(n1, *rec.qkv)
         if kv8 is not None:
             o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound)
         else:
             ops.rope_kv_append_(qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
             o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
-        x2 = ops.gemv_w8(o, *rec.o, residual=x)
+        x2 = rec.gemv(o, *rec.o, residual=x)
         n2 = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
-        act = ops.swiglu_fwd(ops.gemv_w8(n2, *rec.gu), meta.I)
-        x = ops.gemv_w8(act, *rec.down, residual=x2)
+        act = ops.swiglu_fwd(rec.gemv(n2, *rec.gu), meta.I)
+        x = rec.gemv(act, *rec.down, residual=x2)
     return x
 
 

@@ -350,8 +350,8 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         if output_attentions:
             raise NotImplementedError("output_attentions: attention probabilities are never materialised by the flash kernel")
         if self.w8_format is not None:
-            raise NotImplementedError("forward without past_key_values on a decoder quantised with quantize_decoder_: the weight-only FP8 "
-                                      "weights serve the cached generation path only (greedy_decode, generate() / forward with a HipKVCache)")
+            raise NotImplementedError("forward without past_key_values on a decoder quantised with quantize_decoder_: the weight-only "
+                                      "quantised weights serve the cached generation path only (greedy_decode, generate() / forward with a HipKVCache)")
         return_dict = True if return_dict is None else return_dict
         cfg = self.config
         F.params_ready(None)
@@ -607,9 +607,15 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         split (a one-sequence prompt of more than 960 rows at 8B widths runs wholly there), the prompt pass's gate|up above
         functional.PROMPT_GU_SPLITK_ROWS rows, the batched prompt pass of all sequences at once, passes of more than 4096 rows.  The bf16
         storage of the quantised projections is released unless keep_bf16;
-        embed_tokens, norms, vision tower, projector and vision head stay bf16.  The model ends in eval mode: generation only."""
-        if fmt not in ops.W8_FORMATS:
-            raise ValueError(f"quantize_decoder_: unknown format {fmt!r} (supported: {sorted(ops.W8_FORMATS)})")
+        embed_tokens, norms, vision tower, projector and vision head stay bf16.  The model ends in eval mode: generation only.
+        fmt="mxfp4" (the counterpart of the reference's load_4bit=True): OCP MXFP4, e2m1 nibbles + one e8m0 scale per 32 consecutive k
+        (ops.quantize_w4), 4.25 bits per weight and coarser than FP8 (relative RMS weight error 0.114 against 0.026 on Gaussian weights;
+        on a trained checkpoint: not measured) -- opt-in.  Decode steps of up to 16 sequences run on mm355_gemv*_w4; there is no w4
+        split-K GEMM yet, so every other route (more sequences, prompt passes, decoder_extend) takes the scratch route.  Hidden and
+        intermediate size must be multiples of 32; lm_head=True is refused (the head is the accuracy-critical matrix and beyond 16 rows
+        it would need a temporary of its bf16 size); pow2_scales has no effect (the group scales are powers of two by format)."""
+        if fmt not in ops.QUANT_FORMATS:
+            raise ValueError(f"quantize_decoder_: unknown format {fmt!r} (supported: {sorted(ops.QUANT_FORMATS)})")
         if self.w8_format is not None:
             raise RuntimeError(f"quantize_decoder_: the decoder is already quantised ({self.w8_format}); a second call would quantise "
                                "quantised weights")
@@ -617,9 +623,16 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
                         or self.lm_head.weight.data_ptr() == self.model.embed_tokens.weight.data_ptr()):
             raise ValueError("quantize_decoder_(lm_head=True) with tied embeddings: lm_head shares its storage with embed_tokens, which "
                              "stays bf16; pass lm_head=False")
+        w4 = fmt in ops.W4_FORMATS
+        if w4 and lm_head:
+            raise ValueError('quantize_decoder_(fmt="mxfp4", lm_head=True): a 4-bit lm_head is not supported (the head is the '
+                             "accuracy-critical matrix); pass lm_head=False")
+        if w4 and (self.config.hidden_size % 32 or self.config.intermediate_size % 32):
+            raise ValueError(f'quantize_decoder_(fmt="mxfp4"): hidden size {self.config.hidden_size} and intermediate size '
+                             f"{self.config.intermediate_size} must be multiples of 32 (one scale per 32 consecutive k)")
         scratch = F.W8Scratch()
         for layer in self.model.layers:
-            layer.w8 = F.W8Layer(layer, scratch, pow2_scales=pow2_scales, keep_bf16=keep_bf16)
+            layer.w8 = (F.W4Layer if w4 else F.W8Layer)(layer, scratch, pow2_scales=pow2_scales, keep_bf16=keep_bf16)
         if lm_head:
             w = self.lm_head.weight
             self.w8_lm_head = ops.quantize_w8(w.data, pow2_scales)

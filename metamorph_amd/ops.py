@@ -366,6 +366,118 @@ def gemv_rope_append_w8(x, wq, scale, Hq, Hkv, d, cos, sin, positions, k_cache, 
     return out
 
 
+# ------------------------------------------------------------------------------------------------ weight-only MXFP4 (decode)
+
+W4_MXFP4 = 2                                                 # MM355_W4_MXFP4
+W4_FORMATS = {"mxfp4": W4_MXFP4}
+QUANT_FORMATS = {**W8_FORMATS, **W4_FORMATS}                 # what quantize_decoder_ accepts
+E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)         # |value| of the codes 0 .. 7; bit 3 of a nibble is the sign
+
+
+def quantize_w4(w):
+    """w [N, K], K % 32 == 0 -> (q uint8 [N, K/2], s uint8 [N, K/32]) of format "mxfp4" (OCP MX): per group of 32 consecutive k the e8m0
+    scale 2^e, e = clamp(floor(log2(amax)) - 2, -125, 125) stored as s = e + 127 (a group of zeros: e = 0), and per element the e2m1 code
+    of RNE(w / 2^e) (ties to the even code, saturating at +-6) with the sign of w in bit 3; byte j of a row holds k = 2j in bits 3:0 and
+    k = 2j+1 in bits 7:4.  Every dequantised value is exactly a bf16 value.  Not a hot path: torch ops, on whatever device w lives on."""
+    assert w.dim() == 2 and w.shape[1] % 32 == 0, tuple(w.shape)
+    N, K = w.shape
+    wf = w.detach().float().view(N, K // 32, 32)
+    amax = wf.abs().amax(dim=2)
+    _, ex = torch.frexp(amax)                                # amax = m * 2^ex, m in [0.5, 1): floor(log2(amax)) = ex - 1
+    e = torch.where(amax > 0, (ex - 3).clamp(-125, 125), torch.zeros_like(ex))
+    v = torch.ldexp(wf.abs(), -e[:, :, None])                # exact: a power-of-two factor
+    # RNE onto the grid: steps of 0.5 below 2, of 1 below 4, of 2 above; torch.round is half-to-even, which is the even CODE on every piece
+    r = torch.where(v < 2, torch.round(v * 2) / 2, torch.where(v < 4, torch.round(v), torch.round(v / 2) * 2)).clamp_max(6.0)
+    code = torch.bucketize(r, torch.tensor(E2M1_GRID, device=w.device, dtype=torch.float32)).to(torch.uint8)
+    code = code | (torch.signbit(wf).to(torch.uint8) << 3)
+    code = code.view(N, K // 2, 2)
+    q = code[:, :, 0] | (code[:, :, 1] << 4)
+    return q.contiguous(), (e + 127).to(torch.uint8).contiguous()
+
+
+def dequant_w4_reference(q, s):
+    """fp32 [N, K] of (q, s) in format "mxfp4", in torch ops (the definition; every value is exactly a bf16 value): what
+    mm355_dequant_w4_bf16 writes and what the w4 GEMVs multiply."""
+    N, K2 = q.shape
+    grid = torch.tensor(E2M1_GRID + tuple(-g for g in E2M1_GRID), device=q.device, dtype=torch.float32)
+    nib = torch.stack((q & 15, q >> 4), 2).view(N, K2 * 2).long()
+    return torch.ldexp(grid[nib].view(N, K2 // 16, 32), (s.int() - 127)[:, :, None]).view(N, K2 * 2)
+
+
+def _w4_operands(wq, s, K):
+    assert K % 32 == 0, K
+    assert wq.dtype == torch.uint8 and wq.dim() == 2 and wq.stride(1) == 1 and wq.shape[1] == K // 2, (wq.dtype, wq.shape, K)
+    assert s.dtype == torch.uint8 and s.dim() == 2 and s.stride(1) == 1 and tuple(s.shape) == (wq.shape[0], K // 32), (s.dtype, s.shape, K)
+    N = wq.shape[0]
+    return wq.data_ptr(), N, (wq.stride(0) if N > 1 else max(wq.stride(0), K // 2)), s.data_ptr(), (s.stride(0) if N > 1 else max(s.stride(0), K // 32))
+
+
+def dequant_w4(wq, s, out=None):
+    """bf16 [N, K] of (wq, s) in format "mxfp4", exact (mm355_dequant_w4_bf16): the operand of the bf16 GEMMs on every route without a w4 kernel."""
+    _chk_dev(wq, s, out)
+    K = wq.shape[1] * 2
+    pw, N, ldw, ps, lds = _w4_operands(wq, s, K)
+    out = torch.empty((N, K), device=wq.device, dtype=BF16) if out is None else out
+    assert out.dtype == BF16 and tuple(out.shape) == (N, K) and out.stride(1) == 1
+    _lib.check(_L().mm355_dequant_w4_bf16(pw, ldw, ps, lds, W4_MXFP4, out.data_ptr(), out.stride(0) if N > 1 else max(out.stride(0), K),
+                                          N, K, _stream()), f"mm355_dequant_w4_bf16 N={N} K={K}")
+    return out
+
+
+def gemv_w4(x, wq, s, out=None, bias=None, residual=None, gelu=None):
+    """out[M,N] = epilogue(x[M,K] . Wd[N,K]^T) for M <= 16 rows: gemv() over MXFP4 weights (e2m1 nibbles wq [N, K/2], e8m0 group scales s [N, K/32])."""
+    _chk_dev(x, wq, s, out, bias, residual)
+    px, M, K, ldx = _rows2d(x)
+    assert x.dtype == BF16
+    pw, N, ldw, ps, lds = _w4_operands(wq, s, K)
+    if out is None:
+        out = torch.empty((M, N), device=x.device, dtype=BF16)
+    po, Mo, No, ldy = _rows2d(out)
+    assert (Mo, No) == (M, N)
+    flags = GEMM_OUT_F32 if out.dtype == torch.float32 else 0
+    pr, ldr = 0, 0
+    if bias is not None:
+        flags |= GEMM_BIAS
+    if gelu is not None:
+        flags |= {"erf": GEMM_GELU_ERF, "tanh": GEMM_GELU_TANH}[gelu]
+    if residual is not None:
+        pr, Mr, Nr, ldr = _rows2d(residual)
+        assert (Mr, Nr) == (M, N)
+        flags |= GEMM_RESIDUAL
+    _lib.check(_L().mm355_gemv_w4(px, ldx, pw, ldw, ps, lds, W4_MXFP4, po, ldy, M, N, K, _p(bias), pr, ldr, flags, _stream()),
+               f"mm355_gemv_w4 M={M} N={N} K={K}")
+    return out
+
+
+def gemv_swiglu_w4(x, wq, s, I, norm_w=None, eps=0.0, out=None):
+    """gemv_swiglu() over the MXFP4 form of the fused gate|up weight."""
+    _chk_dev(x, wq, s, norm_w, out)
+    px, M, K, ldx = _rows2d(x)
+    assert x.dtype == BF16
+    pw, N, ldw, ps, lds = _w4_operands(wq, s, K)
+    assert N == 2 * I
+    out = torch.empty((M, I), device=x.device, dtype=BF16) if out is None else out
+    _lib.check(_L().mm355_gemv_swiglu_w4(px, ldx, pw, ldw, ps, lds, W4_MXFP4, out.data_ptr(), out.stride(0), M, I, K, _p(norm_w),
+                                         float(eps), _stream()), "mm355_gemv_swiglu_w4")
+    return out
+
+
+def gemv_rope_append_w4(x, wq, s, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache, norm_w=None, eps=0.0, out=None):
+    """gemv_rope_append() over the MXFP4 form of the fused q|k|v weight."""
+    _chk_dev(x, wq, s, norm_w, cos, sin, positions, k_cache, v_cache, out)
+    px, M, K, ldx = _rows2d(x)
+    assert x.dtype == BF16
+    pw, N, ldw, ps, lds = _w4_operands(wq, s, K)
+    assert N == (Hq + 2 * Hkv) * d and positions.dtype == torch.int32
+    assert k_cache.stride() == v_cache.stride() and k_cache.stride(2) == 1
+    out = torch.empty((M, N), device=x.device, dtype=BF16) if out is None else out
+    _lib.check(_L().mm355_gemv_rope_append_w4(px, ldx, pw, ldw, ps, lds, W4_MXFP4, out.data_ptr(), out.stride(0), M, Hq, Hkv, d, K,
+                                              _p(norm_w), float(eps), cos.data_ptr(), sin.data_ptr(), positions.data_ptr(),
+                                              k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(1), k_cache.stride(0), _stream()),
+               "mm355_gemv_rope_append_w4")
+    return out
+
+
 def gemm_w8_supported(M, K):
     """mm355_gemm_w8* take this problem (whole 64-wide K tiles, at most 4096 rows)."""
     return K % 64 == 0 and 0 < M <= 4096
