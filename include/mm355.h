@@ -86,6 +86,8 @@ int mm355_gemm_splitk_bf16(const mm355_bf16* A, int64_t lda, const mm355_bf16* B
  *                 (o projection -> post-attention norm; down projection -> the next layer's input norm).  workspace: mm355_gemm_splitk_ws_floats.
  *   _swiglu:      act[M][I] = SiLU(g) * u, [g | u] = X . Wgu[2 I][K]^T                                    == gemm_splitk -> swiglu_fwd
  *                 workspace: mm355_gemm_splitk_swiglu_ws_floats(M, I, K) floats (never 0: the unsplit sequence parks its bf16 g | u rows there).
+ *                 I % 4 == 0 where the problem is split (I % 8 != 0 or act rows without 16-byte alignment: the reduce launch writes one
+ *                 output per thread, same arithmetic); the unsplit sequence keeps mm355_swiglu_fwd's I % 8 == 0.
  *   _rope_append: one new q|k|v row per sequence: q rotated at positions[m] (device) -> qkv[m][0 .. Hq d), rotated k and v -> cache row
  *                 positions[m]; the k | v columns of qkv are not written                                   == gemm_splitk -> rope_kv_append
  *                 workspace: mm355_gemm_splitk_ws_floats(M, (Hq + 2 Hkv) d, K).  M <= 65535, d % 16 == 0. */
@@ -388,15 +390,15 @@ int mm355_dequant_w8_bf16(const uint8_t* Wq, int64_t ldw_bytes, const float* sca
  * 4.25 bits per weight.  Coarser than FP8 (relative RMS weight error 0.114 against 0.026 on Gaussian weights): opt-in.
  *   gemv_w4: y[m][n] = epilogue(sum_k fp32(Wd[n][k]) * fp32(x[m][k])), x bf16, fp32 accumulation, the group scale inside the widening
  *         conversion (v_cvt_scalef32_pk_bf16_fp4: a byte and its scale -> a packed bf16 pair), nothing multiplied after the sum; flags
- *         and epilogue as mm355_gemv_bf16.  M <= 16 rows (more: MM355_EUNSUPPORTED -- mm355_dequant_w4_bf16 + the bf16 GEMMs).  Up to four
+ *         and epilogue as mm355_gemv_bf16.  M <= 16 rows (more: MM355_EUNSUPPORTED -- mm355_gemm_w4 below).  Up to four
  *         rows on v_dot2c_f32_bf16, 5 .. 16 on v_mfma_f32_16x16x32_bf16; a 16-byte load is one scale group.  fmt other than
  *         MM355_W4_MXFP4, K % 32 != 0, ldw_bytes % 16 != 0, lds_bytes < K / 32, a NULL S or misaligned pointers: MM355_EINVAL before any
  *         launch.  32-bit byte offsets: N * ldw_bytes < 3.75 GiB, else MM355_EUNSUPPORTED.
  *   gemv_swiglu_w4 / gemv_rope_append_w4: the twins of mm355_gemv_swiglu_w8 / mm355_gemv_rope_append_w8 (S, lds_bytes in place of scale;
  *         same row limits and MM355_EUNSUPPORTED cases): the bits of mm355_gemv_w4 + mm355_swiglu_fwd, of mm355_gemv_w4 +
  *         mm355_rope_kv_append, and with norm_w of mm355_rmsnorm_fwd in front.
- *   dequant_w4_bf16: out[n][k] = bf16(Wd[n][k]), exact (no rounding), a plain streaming kernel for every route without a w4 kernel (more
- *         than 16 rows, prompt passes).  ld_out % 8 == 0, out 16-byte aligned.
+ *   dequant_w4_bf16: out[n][k] = bf16(Wd[n][k]), exact (no rounding), a plain streaming kernel: the routes mm355_gemm_w4* do not take
+ *         (passes of more than 4096 rows, shapes the split-K GEMM does not split).  ld_out % 8 == 0, out 16-byte aligned.
  * ------------------------------------------------------------------------------------------------ */
 #define MM355_W4_MXFP4 2
 int mm355_gemv_w4(const mm355_bf16* x, int64_t ldx, const uint8_t* Wq, int64_t ldw_bytes, const uint8_t* S, int64_t lds_bytes, int fmt,
@@ -441,6 +443,41 @@ int mm355_gemm_w8_swiglu(const mm355_bf16* x, int64_t ldx, const uint8_t* Wq, in
                          int64_t ld_act, int64_t M, int64_t I, int64_t K, float* workspace, int64_t workspace_floats, void* stream);
 int mm355_gemm_w8_rope_append(const mm355_bf16* x, int64_t ldx, const uint8_t* Wq, int64_t ldw_bytes, const float* scale, int fmt,
                               mm355_bf16* qkv, int64_t ld_qkv, int64_t M, int64_t Hq, int64_t Hkv, int64_t d, int64_t K,
+                              const mm355_bf16* cos_t, const mm355_bf16* sin_t, const int32_t* positions, mm355_bf16* k_cache,
+                              mm355_bf16* v_cache, int64_t ld_kv, int64_t batch_stride_kv, float* workspace, int64_t workspace_floats,
+                              void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The split-K GEMM over the weight-only MXFP4 format (csrc/gemm_w4.hip): the prompt pass and decode steps of MORE than 16 sequences of a 4-bit
+ * decoder stream the weight as nibbles instead of dequantising it into a scratch buffer first.  Operands as mm355_gemv_w4: x[M][K] bf16,
+ * Wq[N][K/2] e2m1 nibbles (row stride ldw_bytes), S[N][K/32] e8m0 scale bytes (row stride lds_bytes), fmt MM355_W4_MXFP4.
+ *   gemm_w4:  C[M][N] = sum_k fp32(Wd[n][k]) * fp32(x[m][k]) (+ residual), the twin of mm355_gemm_splitk_bf16 and mm355_gemm_w8: the SAME K
+ *         slices (mm355_gemm_w4_ws_floats == mm355_gemm_splitk_ws_floats), the same 64-wide K tiles and MFMA order, the nibbles widened to
+ *         bf16 in registers with the group scale inside the conversion (v_cvt_scalef32_pk_bf16_fp4, exact).  Nothing is multiplied after the
+ *         sum and the partials of a split problem are plain, so for ANY scales the result is bit for bit that of mm355_gemm_splitk_bf16 on
+ *         the output of mm355_dequant_w4_bf16.  flags: MM355_GEMM_RESIDUAL | MM355_GEMM_OUT_F32.  A shape that is not split (workspace 0)
+ *         and every fp32 output run the same kernel as ONE slice that stores straight into C; workspace may then be NULL.
+ *   gemm_w4_norm / gemm_w4_swiglu / gemm_w4_rope_append: the twins of mm355_gemm_w8_norm / _swiglu / _rope_append (S, lds_bytes in place of
+ *         scale; same operands, limits and workspaces; mm355_gemm_w4_swiglu_ws_floats == mm355_gemm_splitk_swiglu_ws_floats), the reduce
+ *         launches shared with the bf16 forms; a shape that is not split runs gemm_w4 + mm355_rmsnorm_fwd / mm355_swiglu_fwd /
+ *         mm355_rope_kv_append inside the library.
+ *   Before any launch: fmt other than MM355_W4_MXFP4, K % 64 != 0, ldw_bytes % 16 != 0, ldw_bytes < K / 2, lds_bytes < K / 32, ldx % 8 != 0,
+ *   a NULL S, misaligned pointers or a workspace that is too small: MM355_EINVAL.  M > 4096: MM355_EUNSUPPORTED (larger passes:
+ *   mm355_dequant_w4_bf16 + the bf16 GEMMs).  The kernel addresses Wq and S with 64-bit offsets: no limit on N * ldw_bytes.
+ * ------------------------------------------------------------------------------------------------ */
+int64_t mm355_gemm_w4_ws_floats(int64_t M, int64_t N, int64_t K);
+int mm355_gemm_w4(const mm355_bf16* x, int64_t ldx, const uint8_t* Wq, int64_t ldw_bytes, const uint8_t* S, int64_t lds_bytes, int fmt, void* C,
+                  int64_t ldc, int64_t M, int64_t N, int64_t K, const mm355_bf16* residual, int64_t ldr, uint32_t flags, float* workspace,
+                  int64_t workspace_floats, void* stream);
+int mm355_gemm_w4_norm(const mm355_bf16* x, int64_t ldx, const uint8_t* Wq, int64_t ldw_bytes, const uint8_t* S, int64_t lds_bytes, int fmt,
+                       mm355_bf16* C, int64_t M, int64_t N, int64_t K, const mm355_bf16* residual, int64_t ldr, const mm355_bf16* norm_w,
+                       float eps, mm355_bf16* Y, float* workspace, int64_t workspace_floats, void* stream);
+int64_t mm355_gemm_w4_swiglu_ws_floats(int64_t M, int64_t I, int64_t K);
+int mm355_gemm_w4_swiglu(const mm355_bf16* x, int64_t ldx, const uint8_t* Wq, int64_t ldw_bytes, const uint8_t* S, int64_t lds_bytes, int fmt,
+                         mm355_bf16* act, int64_t ld_act, int64_t M, int64_t I, int64_t K, float* workspace, int64_t workspace_floats,
+                         void* stream);
+int mm355_gemm_w4_rope_append(const mm355_bf16* x, int64_t ldx, const uint8_t* Wq, int64_t ldw_bytes, const uint8_t* S, int64_t lds_bytes,
+                              int fmt, mm355_bf16* qkv, int64_t ld_qkv, int64_t M, int64_t Hq, int64_t Hkv, int64_t d, int64_t K,
                               const mm355_bf16* cos_t, const mm355_bf16* sin_t, const int32_t* positions, mm355_bf16* k_cache,
                               mm355_bf16* v_cache, int64_t ld_kv, int64_t batch_stride_kv, float* workspace, int64_t workspace_floats,
                               void* stream);

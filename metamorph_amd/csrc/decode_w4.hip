@@ -17,14 +17,7 @@
 
 namespace {
 
-// dword q = eight e2m1 values k .. k+7 (byte b: k + 2b in the low nibble), sc = 2^(S - 127) -> the packed bf16 pairs (k, k+1) .. (k+6, k+7)
-MM_DEV void e2m1x8_to_bf16(uint32_t q, float sc, uint32_t (&p)[4]) {
-    p[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 0));
-    p[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 1));
-    p[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 2));
-    p[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 3));
-}
-MM_DEV float e8m0_to_f32(uint32_t s) { return __uint_as_float(s << 23); }     // (S in 1 .. 254: a normal fp32)
+// (the widening helpers e2m1x8_to_bf16 / e8m0_to_f32 live in mm355_common.h: shared with gemm_w4.hip)
 
 // ------------------------------------------------------------------------------------------------ up to four rows: the vector ALU
 // A wave owns one unit (four weight rows) over the whole K.  A trip = 2048 columns x 4 rows = four 16-byte loads and four scale bytes per

@@ -1037,6 +1037,26 @@ __global__ __launch_bounds__(256) void splitk_reduce_swiglu_kernel(const float* 
         *(u32x4*)(act + m * ld_act + c) = pack8(o);
     }
 }
+// the same, one output per thread: I % 8 != 0 (I % 4 == 0: what makes N = 2 I splittable) or act rows that take no 16-byte stores.  Every
+// output is the same expression over the same slice order as in the kernel above.
+__global__ __launch_bounds__(256) void splitk_reduce_swiglu_tail_kernel(const float* __restrict__ part, int S, int M, int I, uint16_t* __restrict__ act,
+                                                                        int64_t ld_act) {
+    const int N = 2 * I;
+    const int64_t total = (int64_t)M * I, plane = (int64_t)M * N;
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t m = i / I;
+        const int c = (int)(i % I);
+        const float* p = part + m * N + c;
+        float g = p[0], u = p[I];
+        for (int s = 1; s < S; ++s) {
+            g += p[s * plane];
+            u += p[s * plane + I];
+        }
+        g = round_bf(g);
+        u = round_bf(u);
+        act[m * ld_act + c] = f2bf(round_bf(g / (1.0f + __expf(-g))) * u);
+    }
+}
 // q|k|v sums of one new row per sequence: q rotated at positions[m] -> qkv[m][0 .. Hq d), rotated k and v -> cache row positions[m]
 // (rope_kv_append_kernel's arithmetic on the bf16-rounded sums; the k | v columns of qkv are not written)
 __global__ __launch_bounds__(256) void splitk_reduce_rope_append_kernel(const float* __restrict__ part, int S, int M, int Hq, int Hkv, int d,
@@ -1117,6 +1137,11 @@ int mm_splitk_reduce_norm(const float* part, int slices, int64_t M, int64_t N, c
 }
 
 int mm_splitk_reduce_swiglu(const float* part, int slices, int64_t M, int64_t I, mm355_bf16* act, int64_t ld_act, hipStream_t stream) {
+    if ((I & 7) || (ld_act & 7) || !mm_aligned16(act)) {      // no whole 16-byte vectors: one output per thread
+        hipLaunchKernelGGL(splitk_reduce_swiglu_tail_kernel, dim3((unsigned)std::min<int64_t>((M * I + 255) / 256, 4096)), dim3(256), 0, stream, part,
+                           slices, (int)M, (int)I, (uint16_t*)act, ld_act);
+        return mm_launch_status();
+    }
     const int64_t vecs = M * (I / 8);
     hipLaunchKernelGGL(splitk_reduce_swiglu_kernel, dim3((unsigned)std::min<int64_t>((vecs + 255) / 256, 4096)), dim3(256), 0, stream, part, slices,
                        (int)M, (int)I, (uint16_t*)act, ld_act);
@@ -1220,12 +1245,12 @@ extern "C" int64_t mm355_gemm_splitk_swiglu_ws_floats(int64_t M, int64_t I, int6
 extern "C" int mm355_gemm_splitk_swiglu_bf16(const mm355_bf16* X, int64_t ldx, const mm355_bf16* Wgu, int64_t ldw, mm355_bf16* act, int64_t ld_act,
                                              int64_t M, int64_t I, int64_t K, float* workspace, int64_t workspace_floats, void* stream) {
     (void)hipGetLastError();
-    if (!X || !Wgu || !act || !workspace || M <= 0 || I <= 0 || K <= 0 || (I & 7) || (ld_act & 7) || !mm_aligned16(act) || !mm_aligned16(workspace))
-        return MM355_EINVAL;
+    if (!X || !Wgu || !act || !workspace || M <= 0 || I <= 0 || K <= 0 || (I & 3) || ld_act < I || !mm_aligned16(workspace)) return MM355_EINVAL;
     if (workspace_floats < mm355_gemm_splitk_swiglu_ws_floats(M, I, K)) return MM355_EINVAL;
     const int64_t N = 2 * I;
     const int S = splitk_slices(M, N, K);
-    if (S <= 1) {
+    if (S <= 1) {                                            // (mm355_swiglu_fwd: I % 8 == 0, 16-byte aligned rows)
+        if ((I & 7) || !mm_aligned16(act)) return MM355_EINVAL;
         if (ld_act != I) return MM355_EUNSUPPORTED;
         mm355_bf16* gu = (mm355_bf16*)workspace;
         const int rc = mm355_gemm_bf16(X, ldx, Wgu, ldw, gu, N, M, N, K, nullptr, nullptr, 0, 0, 0u, 0, stream);

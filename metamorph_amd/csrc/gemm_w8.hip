@@ -263,8 +263,7 @@ extern "C" int mm355_gemm_w8_swiglu(const mm355_bf16* x, int64_t ldx, const uint
                                     mm355_bf16* act, int64_t ld_act, int64_t M, int64_t I, int64_t K, float* workspace, int64_t workspace_floats,
                                     void* stream) {
     (void)hipGetLastError();
-    if (!act || !workspace || I <= 0 || (I & 7) || I > 0x3fffffff || (ld_act & 7) || ld_act < I || !mm_aligned16(act) || !mm_aligned16(workspace))
-        return MM355_EINVAL;
+    if (!act || !workspace || I <= 0 || (I & 3) || I > 0x3fffffff || ld_act < I || !mm_aligned16(workspace)) return MM355_EINVAL;
     const int64_t N = 2 * I;
     const int rc = w8_gemm_check(x, ldx, Wq, ldw_bytes, scale, fmt, M, N, K);
     if (rc != MM355_OK) return rc;
@@ -272,6 +271,7 @@ extern "C" int mm355_gemm_w8_swiglu(const mm355_bf16* x, int64_t ldx, const uint
     const int S = mm_splitk_slices(M, N, K);
     int slices = 0;
     if (S <= 1) {
+        if ((I & 7) || !mm_aligned16(act)) return MM355_EINVAL;  // (mm355_swiglu_fwd's own limits)
         if (ld_act != I) return MM355_EUNSUPPORTED;
         mm355_bf16* gu = (mm355_bf16*)workspace;
         const int rl = w8_gemm_launch(x, ldx, Wq, ldw_bytes, scale, M, N, K, 1, nullptr, gu, N, nullptr, 0, 0u, (hipStream_t)stream, slices);

@@ -52,6 +52,17 @@ MM_DEV void e4m3x4_to_bf16(uint32_t q, uint32_t& p01, uint32_t& p23) {
     p23 = __builtin_amdgcn_perm(__float_as_uint(b.y), __float_as_uint(b.x), 0x07060302u);
 }
 
+// MXFP4: dword q = eight e2m1 values k .. k+7 (byte b: k + 2b in the low nibble), sc = 2^(S - 127) -> the packed bf16 pairs (k, k+1) ..
+// (k+6, k+7): four v_cvt_scalef32_pk_bf16_fp4, exact, the group scale inside the conversion.  Shared by the w4 GEMVs (decode_w4.hip) and
+// the w4 GEMM (gemm_w4.hip).
+MM_DEV void e2m1x8_to_bf16(uint32_t q, float sc, uint32_t (&p)[4]) {
+    p[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 0));
+    p[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 1));
+    p[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 2));
+    p[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 3));
+}
+MM_DEV float e8m0_to_f32(uint32_t s) { return __uint_as_float(s << 23); }     // (S in 1 .. 254: a normal fp32)
+
 MM_DEV float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

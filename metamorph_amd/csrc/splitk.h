@@ -1,5 +1,5 @@
-// The second launch of a split-K projection, shared by the bf16 split-K GEMM (gemm_bf16.hip, where the kernels live) and its e4m3 twin
-// (gemm_w8.hip): fp32 partials [slices][M][N] -> the bf16 result, alone or with what follows the projection on the decode / prompt path.
+// The second launch of a split-K projection, shared by the bf16 split-K GEMM (gemm_bf16.hip, where the kernels live) and its e4m3 and MXFP4
+// twins (gemm_w8.hip, gemm_w4.hip): fp32 partials [slices][M][N] -> the bf16 result, alone or with what follows the projection on the decode / prompt path.
 // Library-internal: none of these is part of the C ABI.
 #pragma once
 #include "mm355_common.h"

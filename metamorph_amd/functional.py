@@ -41,6 +41,8 @@ VARIANTS = {"fuse_swiglu": True, "fuse_rope": True, "fuse_swiglu_bwd": True, "de
             # quantised layers (quantize_decoder_): projections of the prompt pass and of decode steps of more than 16 sequences on the w8
             # split-K GEMM (mm355_gemm_w8*: the weight bytes streamed once); off: every such projection through the W8Scratch route
             "w8_gemm": True,
+            # the same switch for layers in format "mxfp4" (mm355_gemm_w4*), so that the two formats can be compared independently
+            "w4_gemm": True,
             # n > 1 new rows on a filled cache (a follow-up turn, a prompt run in chunks): ONE pass over the weights with mm355_attn_extend
             # (decoder_extend); off, or fewer than extend_min_rows rows: one captured decode step per row (two rows: the pass's floor of one
             # split-K stream over the weights is 0.81 - 1.46 x two GEMV steps, profiles/extend_pass.md)
@@ -877,16 +879,16 @@ def _prefill_layers_fused(x, layers, meta, cache, row, ident):
         kc, vc = (stage[0], stage[1]) if stage is not None else (cache.k[i, row], cache.v[i, row])   # [max_len, width]
         rows_k = kc.as_strided((L, kc.shape[0], kc.shape[1]), (0, kc.stride(0), 1))
         rows_v = vc.as_strided((L, vc.shape[0], vc.shape[1]), (0, vc.stride(0), 1))
-        qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), ops.gemm_w8_rope_append,
+        qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), "gemm_rope_append",
                     ops.gemm_splitk_rope_append, n1, meta.Hq, meta.Hkv, meta.d, meta.cos, meta.sin, ident, rows_k, rows_v)
         o, _ = ops.attn_fwd(qkv[:, :nq], kc[:L], vc[:L], 1, L, meta.Hq, meta.Hkv, meta.d, meta.scale, True, meta.seqlens)
         if stage is not None:
             ops.kv_quant_f8(stage[0], meta.Hkv, meta.d, cache.k[i, row:row + 1], cache.k_scale[i, row:row + 1])
             ops.kv_quant_f8(stage[1], meta.Hkv, meta.d, cache.v[i, row:row + 1], cache.v_scale[i, row:row + 1])
-        x2, n2 = _proj(on8, rec, "o", (att.o_proj.weight,), ops.gemm_w8_norm, ops.gemm_splitk_norm, o,
+        x2, n2 = _proj(on8, rec, "o", (att.o_proj.weight,), "gemm_norm", ops.gemm_splitk_norm, o,
                        layer.post_attention_layernorm.weight, meta.eps, residual=x)
         if "gu" in on8:
-            act = ops.gemm_w8_swiglu(n2, *rec.gu, meta.I)
+            act = rec.gemm_swiglu(n2, *rec.gu, meta.I)
         else:
             wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
             if VARIANTS["fuse_swiglu"] and ops.gemm_swiglu_supported(n2, wgu, meta.I):
@@ -897,10 +899,10 @@ def _prefill_layers_fused(x, layers, meta, cache, row, ident):
                 act = ops.swiglu_fwd(ops.gemm(n2, wgu), meta.I)
         if i + 1 < len(layers):
             params_ready(layers[i + 1])
-            x, n1 = _proj(on8, rec, "down", (mlp.down_proj.weight,), ops.gemm_w8_norm, ops.gemm_splitk_norm, act,
+            x, n1 = _proj(on8, rec, "down", (mlp.down_proj.weight,), "gemm_norm", ops.gemm_splitk_norm, act,
                           layers[i + 1].input_layernorm.weight, meta.eps, residual=x2)
         else:
-            x = _proj(on8, rec, "down", (mlp.down_proj.weight,), ops.gemm_w8, ops.gemm_splitk, act, residual=x2)
+            x = _proj(on8, rec, "down", (mlp.down_proj.weight,), "gemm", ops.gemm_splitk, act, residual=x2)
     return x
 
 
@@ -960,20 +962,20 @@ def decoder_extend(x, layers, meta, cache, row=0):
                 n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
             wq = (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight)
             if cache.kv8 is not None:                         # plain split projection, rotation in place, quantising append (no fused f8 form)
-                qkv = _proj(on8, rec, "qkv", wq, ops.gemm_w8, ops.gemm_splitk, n1)
+                qkv = _proj(on8, rec, "qkv", wq, "gemm", ops.gemm_splitk, n1)
                 ops.rope_qk_(qkv, 1, n, meta.Hq, meta.Hkv, meta.d, meta.cos, meta.sin, pos_offset=past_dev)
                 _append_rows(qkv, cache, i, row, past, ident, meta)
             else:
                 kc, vc = cache.k[i, row], cache.v[i, row]
                 rows_k = kc.as_strided((n, kc.shape[0], kc.shape[1]), (0, kc.stride(0), 1))
                 rows_v = vc.as_strided((n, vc.shape[0], vc.shape[1]), (0, vc.stride(0), 1))
-                qkv = _proj(on8, rec, "qkv", wq, ops.gemm_w8_rope_append, ops.gemm_splitk_rope_append, n1, meta.Hq, meta.Hkv, meta.d,
+                qkv = _proj(on8, rec, "qkv", wq, "gemm_rope_append", ops.gemm_splitk_rope_append, n1, meta.Hq, meta.Hkv, meta.d,
                             meta.cos, meta.sin, pos, rows_k, rows_v)
             o = _attend_extend(qkv[:, :nq], cache, i, row, past_dev, n, bound, meta)
-            x2, n2 = _proj(on8, rec, "o", (att.o_proj.weight,), ops.gemm_w8_norm, ops.gemm_splitk_norm, o,
+            x2, n2 = _proj(on8, rec, "o", (att.o_proj.weight,), "gemm_norm", ops.gemm_splitk_norm, o,
                            layer.post_attention_layernorm.weight, meta.eps, residual=x)
             if "gu" in on8:
-                act = ops.gemm_w8_swiglu(n2, *rec.gu, meta.I)
+                act = rec.gemm_swiglu(n2, *rec.gu, meta.I)
             else:
                 wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
                 if VARIANTS["fuse_swiglu"] and ops.gemm_swiglu_supported(n2, wgu, meta.I):
@@ -984,10 +986,10 @@ def decoder_extend(x, layers, meta, cache, row=0):
                     act = ops.swiglu_fwd(ops.gemm(n2, wgu), meta.I)
             if i + 1 < len(layers):
                 params_ready(layers[i + 1])
-                x, n1 = _proj(on8, rec, "down", (mlp.down_proj.weight,), ops.gemm_w8_norm, ops.gemm_splitk_norm, act,
+                x, n1 = _proj(on8, rec, "down", (mlp.down_proj.weight,), "gemm_norm", ops.gemm_splitk_norm, act,
                               layers[i + 1].input_layernorm.weight, meta.eps, residual=x2)
             else:
-                x = _proj(on8, rec, "down", (mlp.down_proj.weight,), ops.gemm_w8, ops.gemm_splitk, act, residual=x2)
+                x = _proj(on8, rec, "down", (mlp.down_proj.weight,), "gemm", ops.gemm_splitk, act, residual=x2)
     else:
         mm = ops.gemm_splitk if splitk else ops.gemm
         for i, layer in enumerate(layers):
@@ -1031,13 +1033,14 @@ def decoder_prefill_chunked(x, layers, meta, cache, chunk, row=0):
 
 
 class W8Scratch:
-    """ONE layer's fused projections as bf16, shared by every quantised layer of a model: a projection whose route has no w8 kernel is
-    dequantised into it (one mm355_dequant_w8_bf16 launch, a write + read of its bf16 weights on top of the GEMM) and takes the existing bf16
-    GEMM from there.  Correct and not fast.  Since mm355_gemm_w8* that is: the batched prompt pass of all sequences at once
+    """ONE layer's fused projections as bf16, shared by every quantised layer of a model (W8Layer and W4Layer alike): a projection whose
+    route has no kernel on the quantised bytes is dequantised into it (one mm355_dequant_w8_bf16 / mm355_dequant_w4_bf16 launch, a write +
+    read of its bf16 weights on top of the GEMM) and takes the existing bf16 GEMM from there.  Correct and not fast.  Since mm355_gemm_w8*
+    and mm355_gemm_w4* that is: the batched prompt pass of all sequences at once
     (decoder_layer_forward), passes of more than 4096 rows, the prompt pass's gate|up above PROMPT_GU_SPLITK_ROWS rows (the ping-pong
-    gemm_swiglu), every projection at a row count where the split-K GEMM does not split it (W8_GEMM_UNSPLIT_MAX_ROWS: at 8B widths a
+    gemm_swiglu), every projection at a row count where the split-K GEMM does not split it (W8_GEMM_UNSPLIT_MAX_ROWS / W4_GEMM_UNSPLIT_MAX_ROWS: at 8B widths a
     one-sequence prompt's q|k|v beyond 960 rows -- decoder_prefill then runs the WHOLE pass on this route; any projection too narrow
-    to be split), and everything while VARIANTS["w8_gemm"] is off.  A buffer is allocated when
+    to be split), and everything while the format's switch (VARIANTS["w8_gemm"], VARIANTS["w4_gemm"]) is off.  A buffer is allocated when
     its projection first takes this route: `bufs` stays None on a model whose steps all run on the bytes."""
 
     def __init__(self):
@@ -1059,8 +1062,16 @@ class W8Layer:
     parameters no longer hold storage of their own (they alias the model's W8Scratch while a scratch route runs)."""
     NAMES = ("qkv", "o", "gu", "down")
     ON_GEMM = True                                           # the format has a split-K GEMM on its bytes (mm355_gemm_w8*)
+    GEMM_SWITCH = "w8_gemm"                                  # the VARIANTS switch of that GEMM; its row caps: gemm_caps()
     gemv, gemv_swiglu, gemv_rope_append, dequant = (staticmethod(f) for f in (ops.gemv_w8, ops.gemv_swiglu_w8, ops.gemv_rope_append_w8,
                                                                                 ops.dequant_w8))
+    gemm, gemm_norm, gemm_swiglu, gemm_rope_append, gemm_supported = (staticmethod(f) for f in (
+        ops.gemm_w8, ops.gemm_w8_norm, ops.gemm_w8_swiglu, ops.gemm_w8_rope_append, ops.gemm_w8_supported))
+
+    @staticmethod
+    def gemm_caps():
+        """(split, unsplit) row-cap tables of the format's GEMM, read when asked: tools and tests patch the module's tables."""
+        return W8_GEMM_MAX_ROWS, W8_GEMM_UNSPLIT_MAX_ROWS
 
     @staticmethod
     def quantize(w, pow2_scales):
@@ -1104,11 +1115,21 @@ class W8Layer:
 
 class W4Layer(W8Layer):
     """W8Layer in format "mxfp4" (ops.quantize_w4): each fused matrix as (nibbles uint8 [N, K/2], e8m0 group scales uint8 [N, K/32]).
-    Decode steps of up to 16 rows run on the mm355_gemv*_w4 kernels; there is no w4 split-K GEMM, so every other route dequantises
-    into the W8Scratch (mm355_dequant_w4_bf16, exact) and runs the bf16 GEMMs."""
-    ON_GEMM = False
+    Decode steps of up to 16 rows run on the mm355_gemv*_w4 kernels; wider steps, one-sequence prompt passes and decoder_extend run the
+    projections that the split-K GEMM splits on mm355_gemm_w4* (the nibbles streamed once; the bits of the bf16 split-K GEMM on the
+    dequantised weight, so switching VARIANTS["w4_gemm"] changes no result) up to the row caps W4_GEMM_MAX_ROWS /
+    W4_GEMM_UNSPLIT_MAX_ROWS -- 0 until measured, see there.  What the caps leave out dequantises into the W8Scratch
+    (mm355_dequant_w4_bf16, exact) and runs the bf16 GEMMs."""
+    ON_GEMM = True                                           # mm355_gemm_w4*
+    GEMM_SWITCH = "w4_gemm"
     gemv, gemv_swiglu, gemv_rope_append, dequant = (staticmethod(f) for f in (ops.gemv_w4, ops.gemv_swiglu_w4, ops.gemv_rope_append_w4,
                                                                                 ops.dequant_w4))
+    gemm, gemm_norm, gemm_swiglu, gemm_rope_append, gemm_supported = (staticmethod(f) for f in (
+        ops.gemm_w4, ops.gemm_w4_norm, ops.gemm_w4_swiglu, ops.gemm_w4_rope_append, ops.gemm_w4_supported))
+
+    @staticmethod
+    def gemm_caps():
+        return W4_GEMM_MAX_ROWS, W4_GEMM_UNSPLIT_MAX_ROWS
 
     @staticmethod
     def quantize(w, pow2_scales):                            # (the group scales are powers of two by format: pow2_scales has no effect)
@@ -1142,20 +1163,29 @@ def w8_materialize(layer):
 W8_GEMM_MAX_ROWS = {"qkv": 4096, "o": 4096, "gu": 4096, "down": 4096}
 W8_GEMM_UNSPLIT_MAX_ROWS = {"qkv": 0, "o": 0, "gu": 0, "down": 0}
 
+# The same two tables for format "mxfp4" (mm355_gemm_w4*; tools/bench_wide_w4.py writes profiles/decode_w4_wide.json).
+# An entry stays above 0 only where the w4 GEMM is ahead of the scratch route of the same run by more than the larger spread.  No MI355X
+# run of the tool is recorded with this change (measured: not yet) -- the captured-step comparison at 17 sequences was not taken -- so by
+# the rule for unmeasured shapes the split caps are 0 as well: a w4 model keeps the scratch route until the tool has run, and the caps then
+# go to 4096 for every projection it shows ahead.  tests/test_w4_gemm_gpu.py runs the routes with the caps patched to 4096 / 0.
+W4_GEMM_MAX_ROWS = {"qkv": 0, "o": 0, "gu": 0, "down": 0}
+W4_GEMM_UNSPLIT_MAX_ROWS = {"qkv": 0, "o": 0, "gu": 0, "down": 0}
+
 
 def w8_on_gemm(layer, rows, gu_rows=None):
-    """The projections of `layer` that run on their e4m3 bytes at `rows` rows (mm355_gemm_w8*), as a set of W8Layer.NAMES.  gu_rows: the
-    caller's own row limit for gate|up on a GEMM of 64 x 128 tiles (the prompt pass: PROMPT_GU_SPLITK_ROWS).  Empty for a layer that is not
-    quantised."""
+    """The projections of `layer` that run on their quantised bytes at `rows` rows (W8Layer: mm355_gemm_w8*, W4Layer: mm355_gemm_w4*), as a
+    set of W8Layer.NAMES, by the switch and the row caps of the record's own format.  gu_rows: the caller's own row limit for gate|up on a
+    GEMM of 64 x 128 tiles (the prompt pass: PROMPT_GU_SPLITK_ROWS).  Empty for a layer that is not quantised."""
     rec = getattr(layer, "w8", None)
     on8 = set()
-    if rec is not None and rec.ON_GEMM and VARIANTS["w8_gemm"]:
+    if rec is not None and rec.ON_GEMM and VARIANTS[rec.GEMM_SWITCH]:
+        split, unsplit = rec.gemm_caps()
         for n in W8Layer.NAMES:
             N, K = rec.shape(n)
-            cap = (W8_GEMM_MAX_ROWS if ops.gemm_splitk_splits(rows, N, K) else W8_GEMM_UNSPLIT_MAX_ROWS)[n]
+            cap = (split if ops.gemm_splitk_splits(rows, N, K) else unsplit)[n]
             if n == "gu" and gu_rows is not None:
                 cap = min(cap, gu_rows)
-            if rows <= cap and ops.gemm_w8_supported(rows, K):
+            if rows <= cap and rec.gemm_supported(rows, K):
                 on8.add(n)
     return frozenset(on8)
 
@@ -1170,10 +1200,11 @@ def w8_route(layer, rows, gu_rows=None):
 
 
 def _proj(on8, rec, name, weights, w8_op, bf16_op, x, *args, **kw):
-    """One projection of a layer through the w8 op on its e4m3 bytes where w8_route put it there, else through the bf16 op on the (fused)
-    bf16 weight: the two ops of a pair take the same arguments after the weight."""
+    """One projection of a layer through the record's own GEMM op `w8_op` ("gemm", "gemm_norm", "gemm_rope_append": W8Layer on its e4m3
+    bytes, W4Layer on its nibbles) where w8_route put it there, else through the bf16 op on the (fused) bf16 weight: the two ops of a pair
+    take the same arguments after the weight."""
     if name in on8:
-        return w8_op(x, *getattr(rec, name), *args, **kw)
+        return getattr(rec, w8_op)(x, *getattr(rec, name), *args, **kw)
     return bf16_op(x, weights[0] if len(weights) == 1 else fused_weight(weights), *args, **kw)
 
 
@@ -1289,16 +1320,16 @@ def _decode_rows_gemm(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_
             if n1 is None:
                 n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
             if kv8 is not None:                              # fp8_e4m3 cache: the plain split projection, then the quantising append (ten launches per layer)
-                qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), ops.gemm_w8, ops.gemm_splitk, n1)
+                qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), "gemm", ops.gemm_splitk, n1)
                 o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound)
             else:
-                qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), ops.gemm_w8_rope_append,
+                qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), "gemm_rope_append",
                             ops.gemm_splitk_rope_append, n1, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
                 o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
-            x2, n2 = _proj(on8, rec, "o", (att.o_proj.weight,), ops.gemm_w8_norm, ops.gemm_splitk_norm, o,
+            x2, n2 = _proj(on8, rec, "o", (att.o_proj.weight,), "gemm_norm", ops.gemm_splitk_norm, o,
                            layer.post_attention_layernorm.weight, meta.eps, residual=x)
             if "gu" in on8:
-                act = ops.gemm_w8_swiglu(n2, *rec.gu, meta.I)  # (17 - 32 rows too: the w8 GEMV has no second row group)
+                act = rec.gemm_swiglu(n2, *rec.gu, meta.I)  # (17 - 32 rows too: the w8 GEMV has no second row group)
             else:
                 wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
                 if gu_gemv:
@@ -1307,10 +1338,10 @@ def _decode_rows_gemm(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_
                     act = ops.gemm_splitk_swiglu(n2, wgu, meta.I)
             if i + 1 < len(layers):
                 params_ready(layers[i + 1])                   # (its input norm weight is read by this layer's last launch)
-                x, n1 = _proj(on8, rec, "down", (mlp.down_proj.weight,), ops.gemm_w8_norm, ops.gemm_splitk_norm, act,
+                x, n1 = _proj(on8, rec, "down", (mlp.down_proj.weight,), "gemm_norm", ops.gemm_splitk_norm, act,
                               layers[i + 1].input_layernorm.weight, meta.eps, residual=x2)
             else:
-                x = _proj(on8, rec, "down", (mlp.down_proj.weight,), ops.gemm_w8, ops.gemm_splitk, act, residual=x2)
+                x = _proj(on8, rec, "down", (mlp.down_proj.weight,), "gemm", ops.gemm_splitk, act, residual=x2)
         return x
     for i, layer in enumerate(layers):
         params_ready(layer)
@@ -1318,17 +1349,17 @@ def _decode_rows_gemm(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_
         on8 = w8_route(layer, x.shape[0])
         att, mlp = layer.self_attn, layer.mlp
         n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
-        qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), ops.gemm_w8, ops.gemm_splitk, n1)
+        qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), "gemm", ops.gemm_splitk, n1)
         if kv8 is not None:
             o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound)
         else:
             ops.rope_kv_append_(qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
             o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
-        x2 = _proj(on8, rec, "o", (att.o_proj.weight,), ops.gemm_w8, ops.gemm_splitk, o, residual=x)
+        x2 = _proj(on8, rec, "o", (att.o_proj.weight,), "gemm", ops.gemm_splitk, o, residual=x)
         n2 = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
-        gu = _proj(on8, rec, "gu", (mlp.gate_proj.weight, mlp.up_proj.weight), ops.gemm_w8, ops.gemm_splitk, n2)
+        gu = _proj(on8, rec, "gu", (mlp.gate_proj.weight, mlp.up_proj.weight), "gemm", ops.gemm_splitk, n2)
         act = ops.swiglu_fwd(gu, meta.I)
-        x = _proj(on8, rec, "down", (mlp.down_proj.weight,), ops.gemm_w8, ops.gemm_splitk, act, residual=x2)
+        x = _proj(on8, rec, "down", (mlp.down_proj.weight,), "gemm", ops.gemm_splitk, act, residual=x2)
     return x
 
 

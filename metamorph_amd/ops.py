@@ -413,7 +413,7 @@ def _w4_operands(wq, s, K):
 
 
 def dequant_w4(wq, s, out=None):
-    """bf16 [N, K] of (wq, s) in format "mxfp4", exact (mm355_dequant_w4_bf16): the operand of the bf16 GEMMs on every route without a w4 kernel."""
+    """bf16 [N, K] of (wq, s) in format "mxfp4", exact (mm355_dequant_w4_bf16): the operand of the bf16 GEMMs on the routes gemm_w4* do not take."""
     _chk_dev(wq, s, out)
     K = wq.shape[1] * 2
     pw, N, ldw, ps, lds = _w4_operands(wq, s, K)
@@ -553,6 +553,85 @@ def gemm_w8_rope_append(x, wq, scale, Hq, Hkv, d, cos, sin, positions, k_cache, 
     _lib.check(_L().mm355_gemm_w8_rope_append(px, ldx, pw, ldw, scale.data_ptr(), W8_E4M3, out.data_ptr(), out.stride(0), M, Hq, Hkv, d, K,
                                               cos.data_ptr(), sin.data_ptr(), positions.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
                                               k_cache.stride(1), k_cache.stride(0), ws.data_ptr(), n_ws, _stream()), "mm355_gemm_w8_rope_append")
+    return out
+
+
+def gemm_w4_supported(M, K):
+    """mm355_gemm_w4* take this problem (whole 64-wide K tiles, at most 4096 rows)."""
+    return K % 64 == 0 and 0 < M <= 4096
+
+
+def gemm_w4(x, wq, s, residual=None, out=None, out_f32=False):
+    """out[M, N] = x[M, K] . Wd[N, K]^T (+ residual): gemm_splitk() over MXFP4 weights (mm355_gemm_w4; e2m1 nibbles wq [N, K/2], e8m0 group
+    scales s [N, K/32]) -- the same K slices and summation order, the nibbles widened in registers with the scale inside the conversion:
+    the bits of gemm_splitk(x, dequant_w4(wq, s)).  out_f32 (or an fp32 `out`): fp32 output in one slice."""
+    _chk_dev(x, wq, s, residual, out)
+    px, M, K, ldx = _rows2d(x)
+    assert x.dtype == BF16
+    pw, N, ldw, ps, lds = _w4_operands(wq, s, K)
+    if out is None:
+        out = torch.empty((M, N), device=x.device, dtype=torch.float32 if out_f32 else BF16)
+    po, Mo, No, ldc = _rows2d(out)
+    assert (Mo, No) == (M, N) and out.dtype in (BF16, torch.float32)
+    flags = GEMM_OUT_F32 if out.dtype == torch.float32 else 0
+    pr, ldr = 0, 0
+    if residual is not None:
+        pr, Mr, Nr, ldr = _rows2d(residual)
+        assert (Mr, Nr) == (M, N) and residual.dtype == BF16
+        flags |= GEMM_RESIDUAL
+    n_ws = 0 if flags & GEMM_OUT_F32 else int(_L().mm355_gemm_w4_ws_floats(M, N, K))
+    ws = _splitk_ws(n_ws, x.device)
+    _lib.check(_L().mm355_gemm_w4(px, ldx, pw, ldw, ps, lds, W4_MXFP4, po, ldc, M, N, K, pr, ldr, flags, ws.data_ptr(), n_ws, _stream()),
+               f"mm355_gemm_w4 M={M} N={N} K={K}")
+    return out
+
+
+def gemm_w4_norm(x, wq, s, norm_w, eps, residual=None):
+    """gemm_splitk_norm() over MXFP4 weights (mm355_gemm_w4_norm): (c, y)."""
+    _chk_dev(x, wq, s, norm_w, residual)
+    px, M, K, ldx = _rows2d(x)
+    pw, N, ldw, ps, lds = _w4_operands(wq, s, K)
+    assert x.dtype == BF16 and norm_w.numel() == N
+    c = torch.empty((M, N), device=x.device, dtype=BF16)
+    y = torch.empty((M, N), device=x.device, dtype=BF16)
+    pr, ldr = 0, 0
+    if residual is not None:
+        pr, Mr, Nr, ldr = _rows2d(residual)
+        assert (Mr, Nr) == (M, N)
+    n_ws = int(_L().mm355_gemm_w4_ws_floats(M, N, K))
+    ws = _splitk_ws(n_ws, x.device)
+    _lib.check(_L().mm355_gemm_w4_norm(px, ldx, pw, ldw, ps, lds, W4_MXFP4, c.data_ptr(), M, N, K, pr, ldr, norm_w.data_ptr(), float(eps),
+                                       y.data_ptr(), ws.data_ptr(), n_ws, _stream()), f"mm355_gemm_w4_norm M={M} N={N} K={K}")
+    return c, y
+
+
+def gemm_w4_swiglu(x, wq, s, I):
+    """gemm_splitk_swiglu() over the MXFP4 form of the fused gate|up weight (mm355_gemm_w4_swiglu)."""
+    _chk_dev(x, wq, s)
+    px, M, K, ldx = _rows2d(x)
+    pw, N, ldw, ps, lds = _w4_operands(wq, s, K)
+    assert N == 2 * I and x.dtype == BF16
+    act = torch.empty((M, I), device=x.device, dtype=BF16)
+    n_ws = int(_L().mm355_gemm_w4_swiglu_ws_floats(M, I, K))
+    ws = _splitk_ws(n_ws, x.device)
+    _lib.check(_L().mm355_gemm_w4_swiglu(px, ldx, pw, ldw, ps, lds, W4_MXFP4, act.data_ptr(), act.stride(0), M, I, K, ws.data_ptr(), n_ws,
+                                         _stream()), f"mm355_gemm_w4_swiglu M={M} I={I} K={K}")
+    return act
+
+
+def gemm_w4_rope_append(x, wq, s, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache):
+    """gemm_splitk_rope_append() over the MXFP4 form of the fused q|k|v weight (mm355_gemm_w4_rope_append)."""
+    _chk_dev(x, wq, s, cos, sin, positions, k_cache, v_cache)
+    px, M, K, ldx = _rows2d(x)
+    pw, N, ldw, ps, lds = _w4_operands(wq, s, K)
+    assert x.dtype == BF16 and N == (Hq + 2 * Hkv) * d and positions.dtype == torch.int32
+    assert k_cache.stride() == v_cache.stride() and k_cache.stride(2) == 1
+    out = torch.empty((M, N), device=x.device, dtype=BF16)
+    n_ws = int(_L().mm355_gemm_w4_ws_floats(M, N, K))
+    ws = _splitk_ws(n_ws, x.device)
+    _lib.check(_L().mm355_gemm_w4_rope_append(px, ldx, pw, ldw, ps, lds, W4_MXFP4, out.data_ptr(), out.stride(0), M, Hq, Hkv, d, K,
+                                              cos.data_ptr(), sin.data_ptr(), positions.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                                              k_cache.stride(1), k_cache.stride(0), ws.data_ptr(), n_ws, _stream()), "mm355_gemm_w4_rope_append")
     return out
 
 
