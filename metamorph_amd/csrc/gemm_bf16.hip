@@ -1115,7 +1115,7 @@ int splitk_slices(int64_t M, int64_t N, int64_t K) {
 }
 }  // namespace
 
-// ---- splitk.h: the slice count and the reduce launches, for this file and for gemm_w8.hip
+// ---- splitk.h: the slice count and the reduce launches, for this file and for the quantised-weight driver (gemm_wq.h)
 int mm_splitk_slices(int64_t M, int64_t N, int64_t K) { return splitk_slices(M, N, K); }
 
 int mm_splitk_reduce(const float* part, int slices, int64_t M, int64_t N, const mm355_bf16* residual, int64_t ldr, mm355_bf16* C, int64_t ldc,
@@ -1158,11 +1158,7 @@ int mm_splitk_reduce_rope_append(const float* part, int slices, int64_t M, int64
     return mm_launch_status();
 }
 
-extern "C" int64_t mm355_gemm_splitk_ws_floats(int64_t M, int64_t N, int64_t K) {
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
-    const int S = splitk_slices(M, N, K);
-    return S > 1 ? (int64_t)S * M * N : 0;
-}
+extern "C" int64_t mm355_gemm_splitk_ws_floats(int64_t M, int64_t N, int64_t K) { return mm_splitk_ws_floats(M, N, K); }
 
 // the K slices of A . B^T as fp32 partials workspace[slice][M][N]; `slices` = how many were written (the caller reduces them)
 static int splitk_partials(const mm355_bf16* A, int64_t lda, const mm355_bf16* B, int64_t ldb, int64_t M, int64_t N, int64_t K, int S, float* workspace,
@@ -1237,11 +1233,7 @@ extern "C" int mm355_gemm_splitk_norm_bf16(const mm355_bf16* A, int64_t lda, con
     return mm_splitk_reduce_norm(workspace, slices, M, N, residual, ldr, C, norm_w, eps, Y, (hipStream_t)stream);
 }
 
-extern "C" int64_t mm355_gemm_splitk_swiglu_ws_floats(int64_t M, int64_t I, int64_t K) {
-    if (M <= 0 || I <= 0 || K <= 0) return 0;
-    const int S = splitk_slices(M, 2 * I, K);
-    return S > 1 ? (int64_t)S * M * 2 * I : M * I;          // not split: the bf16 [M][2 I] gate | up rows of the plain sequence
-}
+extern "C" int64_t mm355_gemm_splitk_swiglu_ws_floats(int64_t M, int64_t I, int64_t K) { return mm_splitk_swiglu_ws_floats(M, I, K); }
 extern "C" int mm355_gemm_splitk_swiglu_bf16(const mm355_bf16* X, int64_t ldx, const mm355_bf16* Wgu, int64_t ldw, mm355_bf16* act, int64_t ld_act,
                                              int64_t M, int64_t I, int64_t K, float* workspace, int64_t workspace_floats, void* stream) {
     (void)hipGetLastError();

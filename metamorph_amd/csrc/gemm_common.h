@@ -1,6 +1,6 @@
 // The GEMM argument block and the fused store of eight adjacent output columns (bias / GELU / residual / accumulate / fp32 or bf16
-// output) with the accumulator epilogue around it, shared by every kernel of gemm_bf16.hip and gemm_w8.hip so that all of them round exactly
-// the same way.
+// output) with the accumulator epilogue around it, shared by every kernel of gemm_bf16.hip and the quantised-weight skeleton of gemm_wq.h
+// (gemm_w8.hip, gemm_w4.hip) so that all of them round exactly the same way; and the workgroup -> tile map they share.
 #pragma once
 #include "mm355_common.h"
 
@@ -22,6 +22,23 @@ struct GemmArgs {
     int64_t ld_aux;
     int kslice;                                              // split-K (gemm_nt_kernel only): K elements per blockIdx.y slice, 0 = off; C is then the
 };                                                           // fp32 partial buffer [slices][M][ldc]
+
+// workgroup `bid` of a grid of ntm x ntn tiles -> its tile (tm, tn).  Workgroups go to the eight XCDs round-robin: each XCD gets one
+// contiguous range of the logical order, and that order walks the tiles in groups of GM tile rows, down a group's column first, so that
+// the workgroups resident together on an XCD share A and B panels in its L2.
+MM_DEV void gemm_tile_map(const int ntm, const int ntn, const int GM, const int bid, int& tm, int& tn) {
+    const int total = ntm * ntn;
+    const int q8 = total >> 3, r8 = total & 7;
+    const int xcd = bid & 7, idx = bid >> 3;
+    const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
+    const int gsize = GM * ntn;
+    const int grp = logical / gsize;
+    const int first_m = grp * GM;
+    const int gm = min(ntm - first_m, GM);
+    const int in_g = logical - grp * gsize;
+    tm = first_m + in_g % gm;
+    tn = in_g / gm;
+}
 
 // ragged-edge epilogue (N tail or unaligned leading dimensions): one element at a time, kept out of line
 // so the unrolled fast path stays small.
@@ -103,7 +120,7 @@ MM_DEV void epi_store8(const GemmArgs& a, const uint32_t fl, const bool vec_ok, 
     }
 }
 
-// Shared epilogue (every gemm_nt_kernel form and the w8 twin in gemm_w8.hip): accumulators -> wave-private LDS slab -> row-contiguous 16-B stores with the fused epilogue.
+// Shared epilogue (every gemm_nt_kernel form and gemm_wq_kernel in gemm_wq.h): accumulators -> wave-private LDS slab -> row-contiguous 16-B stores with the fused epilogue.
 template <int TM, int TN, int FM, int FN>
 MM_DEV void gemm_epilogue(f32x4 (&acc)[FM][FN], const GemmArgs& a, unsigned char* smem, int m0, int n0, int wm, int wn, int wave, int lane) {
     const int fr = lane & 15, fq = lane >> 4;

@@ -8,6 +8,18 @@
 
 // K slices of an M x N x K prompt-pass problem (1: not split)
 MM_INTERNAL int mm_splitk_slices(int64_t M, int64_t N, int64_t K);
+// floats of workspace a projection needs (the *_ws_floats queries of every format): the partials of a split problem ...
+static inline int64_t mm_splitk_ws_floats(int64_t M, int64_t N, int64_t K) {
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    const int S = mm_splitk_slices(M, N, K);
+    return S > 1 ? (int64_t)S * M * N : 0;
+}
+// ... and for the SwiGLU forms, not split: the bf16 [M][2 I] gate | up rows of the plain sequence
+static inline int64_t mm_splitk_swiglu_ws_floats(int64_t M, int64_t I, int64_t K) {
+    if (M <= 0 || I <= 0 || K <= 0) return 0;
+    const int S = mm_splitk_slices(M, 2 * I, K);
+    return S > 1 ? (int64_t)S * M * 2 * I : M * I;
+}
 // C = bf16(sum_s part[s] (+ residual)), slices added in order
 MM_INTERNAL int mm_splitk_reduce(const float* part, int slices, int64_t M, int64_t N, const mm355_bf16* residual, int64_t ldr, mm355_bf16* C,
                                  int64_t ldc, hipStream_t stream);

@@ -9,6 +9,7 @@ them) -- the "contiguous_gradients" behaviour of the reference's DeepSpeed ZeRO-
 from __future__ import annotations
 
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -1216,22 +1217,46 @@ def _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, k
                               meta.scale, workspace=ws)
 
 
-def _decode_rows16_w8(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound, kv8=None):
-    """_decode_rows16 on layers that carry a W8Layer record: the same five / seven launches per layer on the record's own kernels
-    (W8Layer: mm355_gemv*_w8, W4Layer: mm355_gemv*_w4)."""
+_Rows16 = namedtuple("_Rows16", "gemv gemv_swiglu gemv_rope_append qkv o gu down")
+
+
+def _bf16_rows16(layer):
+    """A bf16 layer in the shape of a W8Layer record, as _decode_rows16 reads one: the GEMVs and each fused projection as the operands
+    behind x (here the weight alone).  Built per layer and step: fused_weight and the parameters are asked for when the layer runs
+    (parameter generations, the ZeRO hooks), and the ops are read from `ops` then (tests and tools wrap them there)."""
+    att, mlp = layer.self_attn, layer.mlp
+    return _Rows16(ops.gemv, ops.gemv_swiglu, ops.gemv_rope_append,
+                   (fused_weight([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight]),), (att.o_proj.weight,),
+                   (fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight]),), (mlp.down_proj.weight,))
+
+
+def _decode_rows16(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound, kv8=None):
+    """<= 16 new rows (one per sequence) through every decoder layer against their cache rows k / v [layers, rows, max_len, width]:
+    every weight is streamed ONCE for all rows (mm355_gemv* take M <= 16: up to four rows on the vector ALU, 5 .. 16 on MFMA), attention per
+    row at its own length.  One launch sequence for every weight format: a quantised layer runs it on its record's own kernels (W8Layer:
+    mm355_gemv*_w8, W4Layer: mm355_gemv*_w4), a bf16 layer on mm355_gemv*_bf16 through _bf16_rows16."""
     nq = meta.Hq * meta.d
     fused = VARIANTS["decode_fused"] and meta.I % 2 == 0 and meta.d % 4 == 0
     for i, layer in enumerate(layers):
-        rec = layer.w8
+        rec = getattr(layer, "w8", None)
+        if rec is None:
+            params_ready(layer)
+            rec = _bf16_rows16(layer)
         if fused:
+            # five launches per layer: RMSNorm folded into the q|k|v and gate|up GEMVs' operand reads, RoPE + cache append and SwiGLU into
+            # their epilogues, the flash-decoding merge into the chunk that finishes last (same bits as the nine-launch sequence below).
+            # Five rows and more (the MFMA GEMVs): the norm runs as its own launch -- folded in, every workgroup would normalise ALL rows again
+            # (measured, cached step of 32 layers: four rows 3.50 -> 3.38 ms with the norms folded, eight rows slower) -- seven launches, same bits.
             fold = x.shape[0] <= VARIANTS["decode_fold_rows"]
-            if kv8 is not None:                              # fp8_e4m3 cache: norm, plain projection, quantising append, attention over the bytes
+            if kv8 is not None:
+                # fp8_e4m3 cache: the norm and the plain projection as launches of their own (no fused *_rope_append_f8 form), then the
+                # quantising append and attention over the bytes: seven launches per layer up to the fold limit, eight beyond
                 qkv = rec.gemv(ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps), *rec.qkv)
                 o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound)
             else:
                 n1 = x if fold else ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
                 qkv = rec.gemv_rope_append(n1, *rec.qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i],
-                                              norm_w=layer.input_layernorm.weight if fold else None, eps=meta.eps)
+                                           norm_w=layer.input_layernorm.weight if fold else None, eps=meta.eps)
                 o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
             x2 = rec.gemv(o, *rec.o, residual=x)
             n2 = x2 if fold else ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
@@ -1249,54 +1274,6 @@ def _decode_rows16_w8(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_
         n2 = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
         act = ops.swiglu_fwd(rec.gemv(n2, *rec.gu), meta.I)
         x = rec.gemv(act, *rec.down, residual=x2)
-    return x
-
-
-def _decode_rows16(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound, kv8=None):
-    """<= 16 new rows (one per sequence) through every decoder layer against their cache rows k / v [layers, rows, max_len, width]:
-    every weight is streamed ONCE for all rows (mm355_gemv* take M <= 16: up to four rows on the vector ALU, 5 .. 16 on MFMA), attention per
-    row at its own length."""
-    if getattr(layers[0], "w8", None) is not None:
-        return _decode_rows16_w8(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound, kv8)
-    nq = meta.Hq * meta.d
-    for i, layer in enumerate(layers):
-        params_ready(layer)
-        att, mlp = layer.self_attn, layer.mlp
-        wqkv = fused_weight([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight])
-        wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
-        if VARIANTS["decode_fused"] and meta.I % 2 == 0 and meta.d % 4 == 0:
-            # five launches per layer: RMSNorm folded into the q|k|v and gate|up GEMVs' operand reads, RoPE + cache append and SwiGLU into
-            # their epilogues, the flash-decoding merge into the chunk that finishes last (same bits as the nine-launch sequence below).
-            # Five rows and more (the MFMA GEMVs): the norm runs as its own launch -- folded in, every workgroup would normalise ALL rows again
-            # (measured, cached step of 32 layers: four rows 3.50 -> 3.38 ms with the norms folded, eight rows slower) -- seven launches, same bits.
-            fold = x.shape[0] <= VARIANTS["decode_fold_rows"]
-            if kv8 is not None:
-                # fp8_e4m3 cache: the norm and the plain projection as launches of their own (no fused *_rope_append_f8 form), then the
-                # quantising append and attention over the bytes: seven launches per layer up to the fold limit, eight beyond
-                qkv = ops.gemv(ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps), wqkv)
-                o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound)
-            else:
-                n1 = x if fold else ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
-                qkv = ops.gemv_rope_append(n1, wqkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i],
-                                           norm_w=layer.input_layernorm.weight if fold else None, eps=meta.eps)
-                o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
-            x2 = ops.gemv(o, att.o_proj.weight, residual=x)
-            n2 = x2 if fold else ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
-            act = ops.gemv_swiglu(n2, wgu, meta.I, norm_w=layer.post_attention_layernorm.weight if fold else None, eps=meta.eps)
-            x = ops.gemv(act, mlp.down_proj.weight, residual=x2)
-            continue
-        n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
-        qkv = ops.gemv(n1, wqkv)
-        if kv8 is not None:
-            o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound)
-        else:
-            ops.rope_kv_append_(qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
-            o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
-        x2 = ops.gemv(o, att.o_proj.weight, residual=x)
-        n2 = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
-        gu = ops.gemv(n2, wgu)
-        act = ops.swiglu_fwd(gu, meta.I)
-        x = ops.gemv(act, mlp.down_proj.weight, residual=x2)
     return x
 
 

@@ -220,12 +220,8 @@ def gemv_rows32_units(units):
     return (units + 3) // 4 > 1280
 
 
-def gemv(x, w, out=None, bias=None, residual=None, gelu=None):
-    """out[M,N] = x[M,K] . w[N,K]^T for M <= 16 rows (decode shape): streams the weight once at HBM rate (1 - 2 rows: vector ALU; 3 - 16: MFMA)."""
-    _chk_dev(x, w, out, bias, residual)
-    px, M, K, ldx = _rows2d(x)
-    pw, N, Kw, ldw = _rows2d(w)
-    assert K == Kw and x.dtype == BF16 and w.dtype == BF16
+def _gemv_out(x, M, N, out, bias, residual, gelu):
+    """What every plain GEMV takes behind its weight: the output (made here if None) and the epilogue as (out, po, ldy, pr, ldr, flags)."""
     if out is None:
         out = torch.empty((M, N), device=x.device, dtype=BF16)
     po, Mo, No, ldy = _rows2d(out)
@@ -240,6 +236,16 @@ def gemv(x, w, out=None, bias=None, residual=None, gelu=None):
         pr, Mr, Nr, ldr = _rows2d(residual)
         assert (Mr, Nr) == (M, N)
         flags |= GEMM_RESIDUAL
+    return out, po, ldy, pr, ldr, flags
+
+
+def gemv(x, w, out=None, bias=None, residual=None, gelu=None):
+    """out[M,N] = x[M,K] . w[N,K]^T for M <= 16 rows (decode shape): streams the weight once at HBM rate (1 - 2 rows: vector ALU; 3 - 16: MFMA)."""
+    _chk_dev(x, w, out, bias, residual)
+    px, M, K, ldx = _rows2d(x)
+    pw, N, Kw, ldw = _rows2d(w)
+    assert K == Kw and x.dtype == BF16 and w.dtype == BF16
+    out, po, ldy, pr, ldr, flags = _gemv_out(x, M, N, out, bias, residual, gelu)
     _lib.check(_L().mm355_gemv_bf16(px, ldx, pw, ldw, po, ldy, M, N, K, _p(bias), pr, ldr, flags, _stream()), f"mm355_gemv_bf16 M={M} N={N} K={K}")
     return out
 
@@ -300,72 +306,6 @@ def _w8_operands(wq, scale, K):
     return wq.data_ptr(), wq.shape[0], wq.stride(0) if wq.shape[0] > 1 else max(wq.stride(0), K)
 
 
-def dequant_w8(wq, scale, out=None):
-    """bf16 [N, K] = RNE(fp32(wq) * scale[:, None]) (mm355_dequant_w8_bf16): the operand of the bf16 GEMMs on the routes gemm_w8* do not take."""
-    _chk_dev(wq, scale, out)
-    pw, N, ldw = _w8_operands(wq, scale, wq.shape[1])
-    K = wq.shape[1]
-    out = torch.empty((N, K), device=wq.device, dtype=BF16) if out is None else out
-    assert out.dtype == BF16 and tuple(out.shape) == (N, K) and out.stride(1) == 1
-    _lib.check(_L().mm355_dequant_w8_bf16(pw, ldw, scale.data_ptr(), W8_E4M3, out.data_ptr(), out.stride(0) if N > 1 else max(out.stride(0), K),
-                                          N, K, _stream()), f"mm355_dequant_w8_bf16 N={N} K={K}")
-    return out
-
-
-def gemv_w8(x, wq, scale, out=None, bias=None, residual=None, gelu=None):
-    """out[M,N] = epilogue(scale[n] * x[M,K] . fp32(wq[N,K])^T) for M <= 16 rows: gemv() over e4m3 weight bytes with one fp32 scale per row."""
-    _chk_dev(x, wq, scale, out, bias, residual)
-    px, M, K, ldx = _rows2d(x)
-    assert x.dtype == BF16
-    pw, N, ldw = _w8_operands(wq, scale, K)
-    if out is None:
-        out = torch.empty((M, N), device=x.device, dtype=BF16)
-    po, Mo, No, ldy = _rows2d(out)
-    assert (Mo, No) == (M, N)
-    flags = GEMM_OUT_F32 if out.dtype == torch.float32 else 0
-    pr, ldr = 0, 0
-    if bias is not None:
-        flags |= GEMM_BIAS
-    if gelu is not None:
-        flags |= {"erf": GEMM_GELU_ERF, "tanh": GEMM_GELU_TANH}[gelu]
-    if residual is not None:
-        pr, Mr, Nr, ldr = _rows2d(residual)
-        assert (Mr, Nr) == (M, N)
-        flags |= GEMM_RESIDUAL
-    _lib.check(_L().mm355_gemv_w8(px, ldx, pw, ldw, scale.data_ptr(), W8_E4M3, po, ldy, M, N, K, _p(bias), pr, ldr, flags, _stream()),
-               f"mm355_gemv_w8 M={M} N={N} K={K}")
-    return out
-
-
-def gemv_swiglu_w8(x, wq, scale, I, norm_w=None, eps=0.0, out=None):
-    """gemv_swiglu() over the e4m3 bytes of the fused gate|up weight."""
-    _chk_dev(x, wq, scale, norm_w, out)
-    px, M, K, ldx = _rows2d(x)
-    assert x.dtype == BF16
-    pw, N, ldw = _w8_operands(wq, scale, K)
-    assert N == 2 * I
-    out = torch.empty((M, I), device=x.device, dtype=BF16) if out is None else out
-    _lib.check(_L().mm355_gemv_swiglu_w8(px, ldx, pw, ldw, scale.data_ptr(), W8_E4M3, out.data_ptr(), out.stride(0), M, I, K, _p(norm_w),
-                                         float(eps), _stream()), "mm355_gemv_swiglu_w8")
-    return out
-
-
-def gemv_rope_append_w8(x, wq, scale, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache, norm_w=None, eps=0.0, out=None):
-    """gemv_rope_append() over the e4m3 bytes of the fused q|k|v weight."""
-    _chk_dev(x, wq, scale, norm_w, cos, sin, positions, k_cache, v_cache, out)
-    px, M, K, ldx = _rows2d(x)
-    assert x.dtype == BF16
-    pw, N, ldw = _w8_operands(wq, scale, K)
-    assert N == (Hq + 2 * Hkv) * d and positions.dtype == torch.int32
-    assert k_cache.stride() == v_cache.stride() and k_cache.stride(2) == 1
-    out = torch.empty((M, N), device=x.device, dtype=BF16) if out is None else out
-    _lib.check(_L().mm355_gemv_rope_append_w8(px, ldx, pw, ldw, scale.data_ptr(), W8_E4M3, out.data_ptr(), out.stride(0), M, Hq, Hkv, d, K,
-                                              _p(norm_w), float(eps), cos.data_ptr(), sin.data_ptr(), positions.data_ptr(),
-                                              k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(1), k_cache.stride(0), _stream()),
-               "mm355_gemv_rope_append_w8")
-    return out
-
-
 # ------------------------------------------------------------------------------------------------ weight-only MXFP4 (decode)
 
 W4_MXFP4 = 2                                                 # MM355_W4_MXFP4
@@ -412,84 +352,99 @@ def _w4_operands(wq, s, K):
     return wq.data_ptr(), N, (wq.stride(0) if N > 1 else max(wq.stride(0), K // 2)), s.data_ptr(), (s.stride(0) if N > 1 else max(s.stride(0), K // 32))
 
 
-def dequant_w4(wq, s, out=None):
-    """bf16 [N, K] of (wq, s) in format "mxfp4", exact (mm355_dequant_w4_bf16): the operand of the bf16 GEMMs on the routes gemm_w4* do not take."""
-    _chk_dev(wq, s, out)
-    K = wq.shape[1] * 2
+# ------------------------------------------------------------------------------------------------ one wrapper per quantised-weight operation
+
+class _WFormat:
+    """One weight-only format as the wrappers below need it: the suffix of its C symbols (mm355_gemv_<sfx>, mm355_gemm_<sfx>_norm, ...),
+    weight columns per byte of wq, and `operands(wq, s, K)`: the format's own checks of the pair (wq, s) against K columns -> (N, the C
+    operands that follow x in every call of the format, its MM355_* constant last)."""
+
+    def __init__(self, sfx, cols_per_byte, operands):
+        self.sfx, self.cols_per_byte, self.operands = sfx, cols_per_byte, operands
+
+    def sym(self, pattern):
+        """"gemv_{}" -> mm355_gemv_w8, "gemm_{}_norm" -> mm355_gemm_w8_norm: (the library's function, its name for messages)."""
+        name = "mm355_" + pattern.format(self.sfx)
+        return getattr(_L(), name), name
+
+
+def _w8_c_operands(wq, scale, K):
+    pw, N, ldw = _w8_operands(wq, scale, K)
+    return N, (pw, ldw, scale.data_ptr(), W8_E4M3)
+
+
+def _w4_c_operands(wq, s, K):
     pw, N, ldw, ps, lds = _w4_operands(wq, s, K)
+    return N, (pw, ldw, ps, lds, W4_MXFP4)
+
+
+_W8 = _WFormat("w8", 1, _w8_c_operands)
+_W4 = _WFormat("w4", 2, _w4_c_operands)
+
+
+def _wq_dequant(fmt, wq, s, out):
+    _chk_dev(wq, s, out)
+    K = wq.shape[1] * fmt.cols_per_byte
+    N, cw = fmt.operands(wq, s, K)
     out = torch.empty((N, K), device=wq.device, dtype=BF16) if out is None else out
     assert out.dtype == BF16 and tuple(out.shape) == (N, K) and out.stride(1) == 1
-    _lib.check(_L().mm355_dequant_w4_bf16(pw, ldw, ps, lds, W4_MXFP4, out.data_ptr(), out.stride(0) if N > 1 else max(out.stride(0), K),
-                                          N, K, _stream()), f"mm355_dequant_w4_bf16 N={N} K={K}")
+    fn, name = fmt.sym("dequant_{}_bf16")
+    _lib.check(fn(*cw, out.data_ptr(), out.stride(0) if N > 1 else max(out.stride(0), K), N, K, _stream()), f"{name} N={N} K={K}")
     return out
 
 
-def gemv_w4(x, wq, s, out=None, bias=None, residual=None, gelu=None):
-    """out[M,N] = epilogue(x[M,K] . Wd[N,K]^T) for M <= 16 rows: gemv() over MXFP4 weights (e2m1 nibbles wq [N, K/2], e8m0 group scales s [N, K/32])."""
+def _wq_gemv(fmt, x, wq, s, out, bias, residual, gelu):
     _chk_dev(x, wq, s, out, bias, residual)
     px, M, K, ldx = _rows2d(x)
     assert x.dtype == BF16
-    pw, N, ldw, ps, lds = _w4_operands(wq, s, K)
-    if out is None:
-        out = torch.empty((M, N), device=x.device, dtype=BF16)
-    po, Mo, No, ldy = _rows2d(out)
-    assert (Mo, No) == (M, N)
-    flags = GEMM_OUT_F32 if out.dtype == torch.float32 else 0
-    pr, ldr = 0, 0
-    if bias is not None:
-        flags |= GEMM_BIAS
-    if gelu is not None:
-        flags |= {"erf": GEMM_GELU_ERF, "tanh": GEMM_GELU_TANH}[gelu]
-    if residual is not None:
-        pr, Mr, Nr, ldr = _rows2d(residual)
-        assert (Mr, Nr) == (M, N)
-        flags |= GEMM_RESIDUAL
-    _lib.check(_L().mm355_gemv_w4(px, ldx, pw, ldw, ps, lds, W4_MXFP4, po, ldy, M, N, K, _p(bias), pr, ldr, flags, _stream()),
-               f"mm355_gemv_w4 M={M} N={N} K={K}")
+    N, cw = fmt.operands(wq, s, K)
+    out, po, ldy, pr, ldr, flags = _gemv_out(x, M, N, out, bias, residual, gelu)
+    fn, name = fmt.sym("gemv_{}")
+    _lib.check(fn(px, ldx, *cw, po, ldy, M, N, K, _p(bias), pr, ldr, flags, _stream()), f"{name} M={M} N={N} K={K}")
     return out
 
 
-def gemv_swiglu_w4(x, wq, s, I, norm_w=None, eps=0.0, out=None):
-    """gemv_swiglu() over the MXFP4 form of the fused gate|up weight."""
+def _wq_gemv_swiglu(fmt, x, wq, s, I, norm_w, eps, out):
     _chk_dev(x, wq, s, norm_w, out)
     px, M, K, ldx = _rows2d(x)
     assert x.dtype == BF16
-    pw, N, ldw, ps, lds = _w4_operands(wq, s, K)
+    N, cw = fmt.operands(wq, s, K)
     assert N == 2 * I
     out = torch.empty((M, I), device=x.device, dtype=BF16) if out is None else out
-    _lib.check(_L().mm355_gemv_swiglu_w4(px, ldx, pw, ldw, ps, lds, W4_MXFP4, out.data_ptr(), out.stride(0), M, I, K, _p(norm_w),
-                                         float(eps), _stream()), "mm355_gemv_swiglu_w4")
+    fn, name = fmt.sym("gemv_swiglu_{}")
+    _lib.check(fn(px, ldx, *cw, out.data_ptr(), out.stride(0), M, I, K, _p(norm_w), float(eps), _stream()), name)
     return out
 
 
-def gemv_rope_append_w4(x, wq, s, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache, norm_w=None, eps=0.0, out=None):
-    """gemv_rope_append() over the MXFP4 form of the fused q|k|v weight."""
+def _wq_gemv_rope_append(fmt, x, wq, s, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache, norm_w, eps, out):
     _chk_dev(x, wq, s, norm_w, cos, sin, positions, k_cache, v_cache, out)
     px, M, K, ldx = _rows2d(x)
     assert x.dtype == BF16
-    pw, N, ldw, ps, lds = _w4_operands(wq, s, K)
+    N, cw = fmt.operands(wq, s, K)
     assert N == (Hq + 2 * Hkv) * d and positions.dtype == torch.int32
     assert k_cache.stride() == v_cache.stride() and k_cache.stride(2) == 1
     out = torch.empty((M, N), device=x.device, dtype=BF16) if out is None else out
-    _lib.check(_L().mm355_gemv_rope_append_w4(px, ldx, pw, ldw, ps, lds, W4_MXFP4, out.data_ptr(), out.stride(0), M, Hq, Hkv, d, K,
-                                              _p(norm_w), float(eps), cos.data_ptr(), sin.data_ptr(), positions.data_ptr(),
-                                              k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(1), k_cache.stride(0), _stream()),
-               "mm355_gemv_rope_append_w4")
+    fn, name = fmt.sym("gemv_rope_append_{}")
+    _lib.check(fn(px, ldx, *cw, out.data_ptr(), out.stride(0), M, Hq, Hkv, d, K, _p(norm_w), float(eps), cos.data_ptr(), sin.data_ptr(),
+                  positions.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(1), k_cache.stride(0), _stream()), name)
     return out
 
 
-def gemm_w8_supported(M, K):
-    """mm355_gemm_w8* take this problem (whole 64-wide K tiles, at most 4096 rows)."""
+def _wq_gemm_supported(M, K):
     return K % 64 == 0 and 0 < M <= 4096
 
 
-def gemm_w8(x, wq, scale, residual=None, out=None, out_f32=False):
-    """out[M, N] = scale[n] * x[M, K] . fp32(wq[N, K])^T (+ residual): gemm_splitk() over e4m3 weight bytes (mm355_gemm_w8) -- the same K
-    slices and summation order, the bytes widened in registers.  out_f32 (or an fp32 `out`): fp32 output in one slice (the lm_head)."""
-    _chk_dev(x, wq, scale, residual, out)
+def _wq_ws(fmt, query, device, *mnk):
+    """The fp32 workspace a GEMM form asks for at this problem: (tensor, floats)."""
+    n_ws = int(fmt.sym(query)[0](*mnk))
+    return _splitk_ws(n_ws, device), n_ws
+
+
+def _wq_gemm(fmt, x, wq, s, residual, out, out_f32):
+    _chk_dev(x, wq, s, residual, out)
     px, M, K, ldx = _rows2d(x)
     assert x.dtype == BF16
-    pw, N, ldw = _w8_operands(wq, scale, K)
+    N, cw = fmt.operands(wq, s, K)
     if out is None:
         out = torch.empty((M, N), device=x.device, dtype=torch.float32 if out_f32 else BF16)
     po, Mo, No, ldc = _rows2d(out)
@@ -500,18 +455,16 @@ def gemm_w8(x, wq, scale, residual=None, out=None, out_f32=False):
         pr, Mr, Nr, ldr = _rows2d(residual)
         assert (Mr, Nr) == (M, N) and residual.dtype == BF16
         flags |= GEMM_RESIDUAL
-    n_ws = 0 if flags & GEMM_OUT_F32 else int(_L().mm355_gemm_w8_ws_floats(M, N, K))
-    ws = _splitk_ws(n_ws, x.device)
-    _lib.check(_L().mm355_gemm_w8(px, ldx, pw, ldw, scale.data_ptr(), W8_E4M3, po, ldc, M, N, K, pr, ldr, flags, ws.data_ptr(), n_ws, _stream()),
-               f"mm355_gemm_w8 M={M} N={N} K={K}")
+    ws, n_ws = (_splitk_ws(0, x.device), 0) if flags & GEMM_OUT_F32 else _wq_ws(fmt, "gemm_{}_ws_floats", x.device, M, N, K)
+    fn, name = fmt.sym("gemm_{}")
+    _lib.check(fn(px, ldx, *cw, po, ldc, M, N, K, pr, ldr, flags, ws.data_ptr(), n_ws, _stream()), f"{name} M={M} N={N} K={K}")
     return out
 
 
-def gemm_w8_norm(x, wq, scale, norm_w, eps, residual=None):
-    """gemm_splitk_norm() over e4m3 weight bytes (mm355_gemm_w8_norm): (c, y)."""
-    _chk_dev(x, wq, scale, norm_w, residual)
+def _wq_gemm_norm(fmt, x, wq, s, norm_w, eps, residual):
+    _chk_dev(x, wq, s, norm_w, residual)
     px, M, K, ldx = _rows2d(x)
-    pw, N, ldw = _w8_operands(wq, scale, K)
+    N, cw = fmt.operands(wq, s, K)
     assert x.dtype == BF16 and norm_w.numel() == N
     c = torch.empty((M, N), device=x.device, dtype=BF16)
     y = torch.empty((M, N), device=x.device, dtype=BF16)
@@ -519,120 +472,134 @@ def gemm_w8_norm(x, wq, scale, norm_w, eps, residual=None):
     if residual is not None:
         pr, Mr, Nr, ldr = _rows2d(residual)
         assert (Mr, Nr) == (M, N)
-    n_ws = int(_L().mm355_gemm_w8_ws_floats(M, N, K))
-    ws = _splitk_ws(n_ws, x.device)
-    _lib.check(_L().mm355_gemm_w8_norm(px, ldx, pw, ldw, scale.data_ptr(), W8_E4M3, c.data_ptr(), M, N, K, pr, ldr, norm_w.data_ptr(), float(eps),
-                                       y.data_ptr(), ws.data_ptr(), n_ws, _stream()), f"mm355_gemm_w8_norm M={M} N={N} K={K}")
+    ws, n_ws = _wq_ws(fmt, "gemm_{}_ws_floats", x.device, M, N, K)
+    fn, name = fmt.sym("gemm_{}_norm")
+    _lib.check(fn(px, ldx, *cw, c.data_ptr(), M, N, K, pr, ldr, norm_w.data_ptr(), float(eps), y.data_ptr(), ws.data_ptr(), n_ws, _stream()),
+               f"{name} M={M} N={N} K={K}")
     return c, y
+
+
+def _wq_gemm_swiglu(fmt, x, wq, s, I):
+    _chk_dev(x, wq, s)
+    px, M, K, ldx = _rows2d(x)
+    N, cw = fmt.operands(wq, s, K)
+    assert N == 2 * I and x.dtype == BF16
+    act = torch.empty((M, I), device=x.device, dtype=BF16)
+    ws, n_ws = _wq_ws(fmt, "gemm_{}_swiglu_ws_floats", x.device, M, I, K)
+    fn, name = fmt.sym("gemm_{}_swiglu")
+    _lib.check(fn(px, ldx, *cw, act.data_ptr(), act.stride(0), M, I, K, ws.data_ptr(), n_ws, _stream()), f"{name} M={M} I={I} K={K}")
+    return act
+
+
+def _wq_gemm_rope_append(fmt, x, wq, s, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache):
+    _chk_dev(x, wq, s, cos, sin, positions, k_cache, v_cache)
+    px, M, K, ldx = _rows2d(x)
+    N, cw = fmt.operands(wq, s, K)
+    assert x.dtype == BF16 and N == (Hq + 2 * Hkv) * d and positions.dtype == torch.int32
+    assert k_cache.stride() == v_cache.stride() and k_cache.stride(2) == 1
+    out = torch.empty((M, N), device=x.device, dtype=BF16)
+    ws, n_ws = _wq_ws(fmt, "gemm_{}_ws_floats", x.device, M, N, K)
+    fn, name = fmt.sym("gemm_{}_rope_append")
+    _lib.check(fn(px, ldx, *cw, out.data_ptr(), out.stride(0), M, Hq, Hkv, d, K, cos.data_ptr(), sin.data_ptr(), positions.data_ptr(),
+                  k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(1), k_cache.stride(0), ws.data_ptr(), n_ws, _stream()), name)
+    return out
+
+
+# ---- the public names: format "fp8_e4m3" (e4m3 bytes wq [N, K], one fp32 scale per row) ...
+
+def dequant_w8(wq, scale, out=None):
+    """bf16 [N, K] = RNE(fp32(wq) * scale[:, None]) (mm355_dequant_w8_bf16): the operand of the bf16 GEMMs on the routes gemm_w8* do not take."""
+    return _wq_dequant(_W8, wq, scale, out)
+
+
+def gemv_w8(x, wq, scale, out=None, bias=None, residual=None, gelu=None):
+    """out[M,N] = epilogue(scale[n] * x[M,K] . fp32(wq[N,K])^T) for M <= 16 rows: gemv() over e4m3 weight bytes with one fp32 scale per row."""
+    return _wq_gemv(_W8, x, wq, scale, out, bias, residual, gelu)
+
+
+def gemv_swiglu_w8(x, wq, scale, I, norm_w=None, eps=0.0, out=None):
+    """gemv_swiglu() over the e4m3 bytes of the fused gate|up weight."""
+    return _wq_gemv_swiglu(_W8, x, wq, scale, I, norm_w, eps, out)
+
+
+def gemv_rope_append_w8(x, wq, scale, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache, norm_w=None, eps=0.0, out=None):
+    """gemv_rope_append() over the e4m3 bytes of the fused q|k|v weight."""
+    return _wq_gemv_rope_append(_W8, x, wq, scale, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache, norm_w, eps, out)
+
+
+def gemm_w8_supported(M, K):
+    """mm355_gemm_w8* take this problem (whole 64-wide K tiles, at most 4096 rows)."""
+    return _wq_gemm_supported(M, K)
+
+
+def gemm_w8(x, wq, scale, residual=None, out=None, out_f32=False):
+    """out[M, N] = scale[n] * x[M, K] . fp32(wq[N, K])^T (+ residual): gemm_splitk() over e4m3 weight bytes (mm355_gemm_w8) -- the same K
+    slices and summation order, the bytes widened in registers.  out_f32 (or an fp32 `out`): fp32 output in one slice (the lm_head)."""
+    return _wq_gemm(_W8, x, wq, scale, residual, out, out_f32)
+
+
+def gemm_w8_norm(x, wq, scale, norm_w, eps, residual=None):
+    """gemm_splitk_norm() over e4m3 weight bytes (mm355_gemm_w8_norm): (c, y)."""
+    return _wq_gemm_norm(_W8, x, wq, scale, norm_w, eps, residual)
 
 
 def gemm_w8_swiglu(x, wq, scale, I):
     """gemm_splitk_swiglu() over the e4m3 bytes of the fused gate|up weight (mm355_gemm_w8_swiglu)."""
-    _chk_dev(x, wq, scale)
-    px, M, K, ldx = _rows2d(x)
-    pw, N, ldw = _w8_operands(wq, scale, K)
-    assert N == 2 * I and x.dtype == BF16
-    act = torch.empty((M, I), device=x.device, dtype=BF16)
-    n_ws = int(_L().mm355_gemm_w8_swiglu_ws_floats(M, I, K))
-    ws = _splitk_ws(n_ws, x.device)
-    _lib.check(_L().mm355_gemm_w8_swiglu(px, ldx, pw, ldw, scale.data_ptr(), W8_E4M3, act.data_ptr(), act.stride(0), M, I, K, ws.data_ptr(), n_ws,
-                                         _stream()), f"mm355_gemm_w8_swiglu M={M} I={I} K={K}")
-    return act
+    return _wq_gemm_swiglu(_W8, x, wq, scale, I)
 
 
 def gemm_w8_rope_append(x, wq, scale, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache):
     """gemm_splitk_rope_append() over the e4m3 bytes of the fused q|k|v weight (mm355_gemm_w8_rope_append)."""
-    _chk_dev(x, wq, scale, cos, sin, positions, k_cache, v_cache)
-    px, M, K, ldx = _rows2d(x)
-    pw, N, ldw = _w8_operands(wq, scale, K)
-    assert x.dtype == BF16 and N == (Hq + 2 * Hkv) * d and positions.dtype == torch.int32
-    assert k_cache.stride() == v_cache.stride() and k_cache.stride(2) == 1
-    out = torch.empty((M, N), device=x.device, dtype=BF16)
-    n_ws = int(_L().mm355_gemm_w8_ws_floats(M, N, K))
-    ws = _splitk_ws(n_ws, x.device)
-    _lib.check(_L().mm355_gemm_w8_rope_append(px, ldx, pw, ldw, scale.data_ptr(), W8_E4M3, out.data_ptr(), out.stride(0), M, Hq, Hkv, d, K,
-                                              cos.data_ptr(), sin.data_ptr(), positions.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                                              k_cache.stride(1), k_cache.stride(0), ws.data_ptr(), n_ws, _stream()), "mm355_gemm_w8_rope_append")
-    return out
+    return _wq_gemm_rope_append(_W8, x, wq, scale, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache)
+
+
+# ---- ... and format "mxfp4" (e2m1 nibbles wq [N, K/2], e8m0 group scales s [N, K/32])
+
+def dequant_w4(wq, s, out=None):
+    """bf16 [N, K] of (wq, s) in format "mxfp4", exact (mm355_dequant_w4_bf16): the operand of the bf16 GEMMs on the routes gemm_w4* do not take."""
+    return _wq_dequant(_W4, wq, s, out)
+
+
+def gemv_w4(x, wq, s, out=None, bias=None, residual=None, gelu=None):
+    """out[M,N] = epilogue(x[M,K] . Wd[N,K]^T) for M <= 16 rows: gemv() over MXFP4 weights (e2m1 nibbles wq [N, K/2], e8m0 group scales s [N, K/32])."""
+    return _wq_gemv(_W4, x, wq, s, out, bias, residual, gelu)
+
+
+def gemv_swiglu_w4(x, wq, s, I, norm_w=None, eps=0.0, out=None):
+    """gemv_swiglu() over the MXFP4 form of the fused gate|up weight."""
+    return _wq_gemv_swiglu(_W4, x, wq, s, I, norm_w, eps, out)
+
+
+def gemv_rope_append_w4(x, wq, s, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache, norm_w=None, eps=0.0, out=None):
+    """gemv_rope_append() over the MXFP4 form of the fused q|k|v weight."""
+    return _wq_gemv_rope_append(_W4, x, wq, s, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache, norm_w, eps, out)
 
 
 def gemm_w4_supported(M, K):
     """mm355_gemm_w4* take this problem (whole 64-wide K tiles, at most 4096 rows)."""
-    return K % 64 == 0 and 0 < M <= 4096
+    return _wq_gemm_supported(M, K)
 
 
 def gemm_w4(x, wq, s, residual=None, out=None, out_f32=False):
     """out[M, N] = x[M, K] . Wd[N, K]^T (+ residual): gemm_splitk() over MXFP4 weights (mm355_gemm_w4; e2m1 nibbles wq [N, K/2], e8m0 group
     scales s [N, K/32]) -- the same K slices and summation order, the nibbles widened in registers with the scale inside the conversion:
     the bits of gemm_splitk(x, dequant_w4(wq, s)).  out_f32 (or an fp32 `out`): fp32 output in one slice."""
-    _chk_dev(x, wq, s, residual, out)
-    px, M, K, ldx = _rows2d(x)
-    assert x.dtype == BF16
-    pw, N, ldw, ps, lds = _w4_operands(wq, s, K)
-    if out is None:
-        out = torch.empty((M, N), device=x.device, dtype=torch.float32 if out_f32 else BF16)
-    po, Mo, No, ldc = _rows2d(out)
-    assert (Mo, No) == (M, N) and out.dtype in (BF16, torch.float32)
-    flags = GEMM_OUT_F32 if out.dtype == torch.float32 else 0
-    pr, ldr = 0, 0
-    if residual is not None:
-        pr, Mr, Nr, ldr = _rows2d(residual)
-        assert (Mr, Nr) == (M, N) and residual.dtype == BF16
-        flags |= GEMM_RESIDUAL
-    n_ws = 0 if flags & GEMM_OUT_F32 else int(_L().mm355_gemm_w4_ws_floats(M, N, K))
-    ws = _splitk_ws(n_ws, x.device)
-    _lib.check(_L().mm355_gemm_w4(px, ldx, pw, ldw, ps, lds, W4_MXFP4, po, ldc, M, N, K, pr, ldr, flags, ws.data_ptr(), n_ws, _stream()),
-               f"mm355_gemm_w4 M={M} N={N} K={K}")
-    return out
+    return _wq_gemm(_W4, x, wq, s, residual, out, out_f32)
 
 
 def gemm_w4_norm(x, wq, s, norm_w, eps, residual=None):
     """gemm_splitk_norm() over MXFP4 weights (mm355_gemm_w4_norm): (c, y)."""
-    _chk_dev(x, wq, s, norm_w, residual)
-    px, M, K, ldx = _rows2d(x)
-    pw, N, ldw, ps, lds = _w4_operands(wq, s, K)
-    assert x.dtype == BF16 and norm_w.numel() == N
-    c = torch.empty((M, N), device=x.device, dtype=BF16)
-    y = torch.empty((M, N), device=x.device, dtype=BF16)
-    pr, ldr = 0, 0
-    if residual is not None:
-        pr, Mr, Nr, ldr = _rows2d(residual)
-        assert (Mr, Nr) == (M, N)
-    n_ws = int(_L().mm355_gemm_w4_ws_floats(M, N, K))
-    ws = _splitk_ws(n_ws, x.device)
-    _lib.check(_L().mm355_gemm_w4_norm(px, ldx, pw, ldw, ps, lds, W4_MXFP4, c.data_ptr(), M, N, K, pr, ldr, norm_w.data_ptr(), float(eps),
-                                       y.data_ptr(), ws.data_ptr(), n_ws, _stream()), f"mm355_gemm_w4_norm M={M} N={N} K={K}")
-    return c, y
+    return _wq_gemm_norm(_W4, x, wq, s, norm_w, eps, residual)
 
 
 def gemm_w4_swiglu(x, wq, s, I):
     """gemm_splitk_swiglu() over the MXFP4 form of the fused gate|up weight (mm355_gemm_w4_swiglu)."""
-    _chk_dev(x, wq, s)
-    px, M, K, ldx = _rows2d(x)
-    pw, N, ldw, ps, lds = _w4_operands(wq, s, K)
-    assert N == 2 * I and x.dtype == BF16
-    act = torch.empty((M, I), device=x.device, dtype=BF16)
-    n_ws = int(_L().mm355_gemm_w4_swiglu_ws_floats(M, I, K))
-    ws = _splitk_ws(n_ws, x.device)
-    _lib.check(_L().mm355_gemm_w4_swiglu(px, ldx, pw, ldw, ps, lds, W4_MXFP4, act.data_ptr(), act.stride(0), M, I, K, ws.data_ptr(), n_ws,
-                                         _stream()), f"mm355_gemm_w4_swiglu M={M} I={I} K={K}")
-    return act
+    return _wq_gemm_swiglu(_W4, x, wq, s, I)
 
 
 def gemm_w4_rope_append(x, wq, s, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache):
     """gemm_splitk_rope_append() over the MXFP4 form of the fused q|k|v weight (mm355_gemm_w4_rope_append)."""
-    _chk_dev(x, wq, s, cos, sin, positions, k_cache, v_cache)
-    px, M, K, ldx = _rows2d(x)
-    pw, N, ldw, ps, lds = _w4_operands(wq, s, K)
-    assert x.dtype == BF16 and N == (Hq + 2 * Hkv) * d and positions.dtype == torch.int32
-    assert k_cache.stride() == v_cache.stride() and k_cache.stride(2) == 1
-    out = torch.empty((M, N), device=x.device, dtype=BF16)
-    n_ws = int(_L().mm355_gemm_w4_ws_floats(M, N, K))
-    ws = _splitk_ws(n_ws, x.device)
-    _lib.check(_L().mm355_gemm_w4_rope_append(px, ldx, pw, ldw, ps, lds, W4_MXFP4, out.data_ptr(), out.stride(0), M, Hq, Hkv, d, K,
-                                              cos.data_ptr(), sin.data_ptr(), positions.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                                              k_cache.stride(1), k_cache.stride(0), ws.data_ptr(), n_ws, _stream()), "mm355_gemm_w4_rope_append")
-    return out
+    return _wq_gemm_rope_append(_W4, x, wq, s, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache)
 
 
 def rope_kv_append_(qkv, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache):

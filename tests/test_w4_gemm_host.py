@@ -123,7 +123,7 @@ def test_gemm_w4_workspaces_equal_the_bf16_split_k_forms():
 
 @pytest.mark.parametrize("BM", [32, 64])
 def test_b_tile_layout_is_conflict_free_and_complete(BM):
-    """The nibble B tile of gemm_w4_kernel<BM> (csrc/gemm_w4.hip) in LDS: 128 weight rows x 32 bytes behind the x tile, written by LDS-DMA in
+    """The nibble B tile of gemm_wq_kernel<W4, BM> (W4::Lane, csrc/gemm_w4.hip) in LDS: 128 weight rows x 32 bytes behind the x tile, written by LDS-DMA in
     1-KiB pieces (one per wave: lane L -> piece byte 16 L, row L >> 1, slot L & 1, source chunk (L & 1) ^ ((row >> 3) & 1)), read by one
     ds_read_b64 per lane and fragment, of which the lane keeps dword fq & 1.  ds_read_b64 is served per 32-lane half with
     bank = (byte / 4) % 64 and lanes that read the same address are served together: in every half of every fragment read the DISTINCT

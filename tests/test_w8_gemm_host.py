@@ -50,15 +50,20 @@ def test_gemm_w8_validation_without_a_gpu():
 
     def gemm(x=P, ldx=64, wq=P, ldw=64, scale=P, fmt=1, c=P, ldc=8, M=17, N=8, K=64, res=0, ldr=0, flags=0, ws=P, nws=1 << 20):
         return L.mm355_gemm_w8(x, ldx, wq, ldw, scale, fmt, c, ldc, M, N, K, res, ldr, flags, ws, nws, 0)
+    assert gemm(fmt=2) == EINVAL                                 # the MXFP4 format: not this kernel's
     assert gemm(fmt=7) == EINVAL                                 # a format that does not exist
     assert gemm(K=48, ldx=48, ldw=48) == EINVAL                  # K % 64
     assert gemm(K=32, ldx=32, ldw=32) == EINVAL
     assert gemm(ldw=72) == EINVAL                                # ldw_bytes % 16
+    assert gemm(ldw=48) == EINVAL                                # ldw_bytes < K
+    assert gemm(ldx=68) == EINVAL                                # ldx % 8
     assert gemm(scale=0) == EINVAL                               # no scales
+    assert gemm(scale=P + 2) == EINVAL                           # ... or misaligned ones
     assert gemm(wq=P + 8) == EINVAL                              # misaligned weight bytes
     assert gemm(x=P + 2) == EINVAL
     assert gemm(c=P + 4) == EINVAL
     assert gemm(flags=8, res=0) == EINVAL                        # RESIDUAL without a residual
+    assert gemm(flags=8, res=P + 2) == EINVAL                    # ... with a misaligned one
     assert gemm(flags=1) == EINVAL                               # a flag the w8 GEMM does not take (BIAS)
     assert gemm(M=4097) == EUNSUPPORTED                          # larger passes stay on the scratch route
     # a problem that IS split, with a workspace that is too small / missing
@@ -67,6 +72,7 @@ def test_gemm_w8_validation_without_a_gpu():
     assert need > 0
     assert gemm(M=M, N=N, K=K, ldx=K, ldw=K, ldc=N, nws=need - 1) == EINVAL
     assert gemm(M=M, N=N, K=K, ldx=K, ldw=K, ldc=N, ws=0) == EINVAL
+    assert gemm(M=M, N=N, K=K, ldx=K, ldw=K, ldc=N, ws=P + 4) == EINVAL
 
     #                                                    C  M   N     K    res ldr norm eps Y  ws nws stream
     assert L.mm355_gemm_w8_norm(P, K, P, K, P, 2, P, M, N, K, 0, 0, P, 1e-5, P, P, need, 0) == EINVAL
@@ -78,10 +84,13 @@ def test_gemm_w8_validation_without_a_gpu():
     assert L.mm355_gemm_w8_swiglu(P, K, P, K, P, 3, P, 512, M, 512, K, P, need_s, 0) == EINVAL
     assert L.mm355_gemm_w8_swiglu(P, K, P, K + 8, P, 1, P, 512, M, 512, K, P, need_s, 0) == EINVAL     # ldw_bytes % 16
     assert L.mm355_gemm_w8_swiglu(P, K, P, K, P, 1, P, 512, M, 512, K, P, need_s - 1, 0) == EINVAL
+    assert L.mm355_gemm_w8_swiglu(P, K, P, K, P, 1, P, 510, M, 510, K, P, 1 << 30, 0) == EINVAL           # I % 4 (2 I must be splittable)
+    assert L.mm355_gemm_w8_swiglu(P, K, P, K, P, 1, P, 500, M, 512, K, P, need_s, 0) == EINVAL            # ld_act < I
     assert L.mm355_gemm_w8_swiglu(P, K, P, K, P, 1, P, 512, 4097, 512, K, P, 1 << 40, 0) == EUNSUPPORTED
     #                                                           qkv ld   M  Hq Hkv d   K  cos sin pos kc vc ldkv bs  ws nws stream
     assert L.mm355_gemm_w8_rope_append(P, K, P, K, P, 0, P, 1024, M, 4, 2, 128, K, P, P, P, P, P, 256, 4096, P, need, 0) == EINVAL
     assert L.mm355_gemm_w8_rope_append(P, K, P, K, P, 1, P, 1024, M, 4, 2, 128, K + 32, P, P, P, P, P, 256, 4096, P, need, 0) == EINVAL
+    assert L.mm355_gemm_w8_rope_append(P, K + 4, P, K, P, 1, P, 1024, M, 4, 2, 128, K, P, P, P, P, P, 256, 4096, P, need, 0) == EINVAL   # ldx % 8
     assert L.mm355_gemm_w8_rope_append(P, K, P, K, P, 1, P, 1024, M, 4, 2, 128, K, P, P, P, P, P, 256, 4096, P, need - 1, 0) == EINVAL
     assert L.mm355_gemm_w8_rope_append(P, K, P, K, P, 1, P, 1024, 4097, 4, 2, 128, K, P, P, P, P, P, 256, 4096, P, 1 << 40, 0) == EUNSUPPORTED
     # the 16-row GEMV keeps its own limit
@@ -103,7 +112,7 @@ def test_gemm_w8_workspaces_equal_the_bf16_split_k_forms():
 
 
 def test_b_tile_layout_is_conflict_free_and_complete():
-    """The byte B tile of gemm_w8_kernel (csrc/gemm_w8.hip) in LDS: 128 weight rows x 64 bytes, written by LDS-DMA in 1-KiB pieces (lane L ->
+    """The byte B tile of gemm_wq_kernel<W8, BM> (W8::Lane, csrc/gemm_w8.hip) in LDS: 128 weight rows x 64 bytes, written by LDS-DMA in 1-KiB pieces (lane L ->
     piece byte 16 L, row L >> 2, slot L & 3, source chunk (L & 3) ^ ((row >> 2) & 3)), read by one ds_read_b64 per lane and fragment.
     ds_read_b64 is served per 32-lane half with bank = (byte / 4) % 64: every half of every fragment read must touch each of the 64 banks
     exactly once, and a lane must find bytes k = kk*32 + fq*8 .. +7 of weight row wn*32 + j*16 + fr at the address it reads.
