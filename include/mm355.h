@@ -671,6 +671,40 @@ int mm355_softmax_rows_bwd(const mm355_bf16* y, const mm355_bf16* dy, mm355_bf16
                            float temperature, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The greedy loop's per-token tail on the device (metamorph_llama.py:502-597): with these the host reads nothing per token.
+ * argmax_rows_f32: out[r] (int32) = argmax of row r of the contiguous fp32 logits x [R, C], torch.argmax's rule: among equal maxima the
+ *         lowest index, a NaN beats every number, the lowest NaN index.  Two stages in fixed order (one partial per row and 4096-column
+ *         chunk, then one reduction per row), no atomics; workspace: mm355_argmax_rows_ws_bytes(R, C) bytes, 4-byte aligned.
+ * rows_select_bf16: out[r] = mask[r] ? a[r] : b[r] (int32 mask on the device; h % 8 == 0, 16-byte aligned rows): the lm_head input per
+ *         sequence, the projector row in image mode (:363-377), the normed hidden row otherwise.
+ * greedy_advance: one workgroup per sequence runs the loop's branch (:569-589) on device-resident state (int32 [B] each: in_image, n_img,
+ *         total_out, done, n_tokens, n_z) with tok[b] = this step's argmax:
+ *           done:                            nothing is written (state, logs and the x_in row stay)
+ *           !in_image && tok == start_id:    in_image = 1; log tok; next row = embed[tok]
+ *           in_image && n_img < N:           n_img++; log pred_z[b]; next row = fed[b] (the row the lm_head saw); n_img == N: in_image = 0
+ *           tok == end_id:                   in_image = 0; n_img = 0; log tok; next row = embed[tok]
+ *           else:                            log tok; next row = embed[tok]
+ *           total_out++; tok among the eos ids or total_out > max_new_tokens: done = 1
+ *         Writes row b of x_in [B, h], tok_log [B, token_cap] int32, z_log [B, z_cap, Dz] bf16 and decrements live[0] (sequences not yet
+ *         done; the caller initialises it) when a sequence finishes.  A log row at or beyond its cap is never written: the sequence is set
+ *         done instead and nothing else changes.  C (the logits width tok comes from) > embed_rows is MM355_EINVAL, so every id used as a
+ *         gather index lies in [0, embed_rows).  eos_ids: HOST memory, n_eos <= MM355_GREEDY_MAX_EOS.
+ *         The host-side model of the transition is metamorph_amd.functional.greedy_advance_host.
+ * ------------------------------------------------------------------------------------------------ */
+#define MM355_GREEDY_MAX_EOS 8
+int64_t mm355_argmax_rows_ws_bytes(int64_t R, int64_t C);
+int mm355_argmax_rows_f32(const float* x, int64_t R, int64_t C, int32_t* out, void* workspace, int64_t workspace_bytes,
+                          void* stream);
+int mm355_rows_select_bf16(const mm355_bf16* a, int64_t lda, const mm355_bf16* b, int64_t ldb, const int32_t* mask,
+                           mm355_bf16* out, int64_t ldo, int64_t R, int64_t h, void* stream);
+int mm355_greedy_advance(const int32_t* tok, int64_t B, int64_t C, int32_t* in_image, int32_t* n_img, int32_t* total_out,
+                         int32_t* done, int32_t* n_tokens, int32_t* n_z, int32_t* live, const mm355_bf16* embed,
+                         int64_t ld_embed, int64_t embed_rows, const mm355_bf16* fed, int64_t ld_fed, const mm355_bf16* pred_z,
+                         int64_t ld_z, mm355_bf16* x_in, int64_t ld_x, int64_t h, int64_t Dz, int32_t* tok_log,
+                         int64_t token_cap, mm355_bf16* z_log, int64_t z_cap, int start_id, int end_id, int num_image_tokens,
+                         int max_new_tokens, const int32_t* eos_ids, int n_eos, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * ZeRO-2 shard update (replaces DeepSpeed zero2.json + HF adamw_torch, train.py:82): AdamW on the
  * rank's fp32 master shard, writes the updated bf16 parameters.  grad_scale_dev (nullable) is a device
  * scalar multiplied into the gradient (1/world, clip coefficient).

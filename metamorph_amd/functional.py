@@ -47,7 +47,9 @@ VARIANTS = {"fuse_swiglu": True, "fuse_rope": True, "fuse_swiglu_bwd": True, "de
             # n > 1 new rows on a filled cache (a follow-up turn, a prompt run in chunks): ONE pass over the weights with mm355_attn_extend
             # (decoder_extend); off, or fewer than extend_min_rows rows: one captured decode step per row (two rows: the pass's floor of one
             # split-K stream over the weights is 0.81 - 1.46 x two GEMV steps, profiles/extend_pass.md)
-            "extend_pass": True, "extend_min_rows": 3}
+            "extend_pass": True, "extend_min_rows": 3,
+            # greedy_decode of ONE sequence through the device-resident loop that batches take (GreedyLoopGraph) instead of the host loop
+            "greedy_loop_b1": False}
 
 
 def set_variant(name, value):
@@ -1433,6 +1435,145 @@ class DecodeStepGraph:
         g.replay()
         self.cache.lengths = [n + 1 for n in self.cache.lengths]
         return x_out
+
+
+GREEDY_STATE = ("in_image", "n_img", "total_out", "done", "n_tokens", "n_z")     # rows of GreedyLoopGraph.state, arguments of mm355_greedy_advance
+
+
+def greedy_advance_host(state, tok, start_id, end_id, num_image_tokens, max_new_tokens, eos_ids, token_cap=None, z_cap=None):
+    """One iteration of the reference's greedy loop (metamorph_llama.py:569-589) for ONE sequence on plain ints: the specification of
+    mm355_greedy_advance.  state: dict over GREEDY_STATE, updated in place; tok: the argmax of this iteration's logits.  Returns
+    (log, next_row): log "tok" (the id goes to the token log), "z" (the image head's pred_z row goes to the z log) or None; next_row "embed"
+    (embed_tokens[tok]), "fed" (the row the lm_head saw: the projector output) or None.  A finished sequence changes nothing and returns
+    (None, None); so does one whose log is full (token_cap / z_cap rows), which is set done instead of written."""
+    s = state
+    if s["done"]:
+        return None, None
+    image_row = bool(s["in_image"]) and s["n_img"] < num_image_tokens
+    if (z_cap is not None and s["n_z"] >= z_cap) if image_row else (token_cap is not None and s["n_tokens"] >= token_cap):
+        s["done"] = 1
+        return None, None
+    if not s["in_image"] and tok == start_id:
+        s["in_image"] = 1
+    elif image_row:
+        s["n_img"] += 1
+        s["n_z"] += 1
+        if s["n_img"] == num_image_tokens:
+            s["in_image"] = 0
+    elif tok == end_id:
+        s["in_image"] = 0
+        s["n_img"] = 0
+    if not image_row:
+        s["n_tokens"] += 1
+    s["total_out"] += 1
+    if tok in eos_ids or s["total_out"] > max_new_tokens:
+        s["done"] = 1
+    return ("z", "fed") if image_row else ("tok", "embed")
+
+
+class GreedyLoopGraph:
+    """The greedy text-and-image loop (reference metamorph_llama.py:502-597) of a batch with the token loop on the device.  One step is
+    decoder_decode_row (all rows, whatever route the batch size takes) -> `head` (the model's final norm, image head for ALL rows, row select
+    by the device-resident mode, lm_head into the static fp32 `logits`) -> mm355_argmax_rows_f32 -> mm355_greedy_advance, which runs the
+    reference's branch per sequence (greedy_advance_host) and writes the next input rows into `x_in`: the step reads no host value, so it is
+    captured as ONE hipGraph on one stream per attention bound (decode_kv_bound) and replayed per token; set_variant("decode_graph", False)
+    runs the same launches eagerly.  The host replays at most max_new_tokens steps and reads the device's count of live sequences every
+    `poll` steps -- the only device -> host read of the loop (`host_reads` counts them, the final read of the results included).  A finished
+    sequence keeps riding along: mm355_greedy_advance writes nothing for it, its cache rows grow and nobody reads them (the cache's
+    max(L_b) + max_new_tokens + 2 rows cover max_new_tokens steps for every sequence), so the results do not depend on `poll`.
+    head(x [B, h], in_image int32 [B], logits_out f32 [B, C]) -> (fed [B, h], pred_z [B, Dz])."""
+
+    def __init__(self, layers, meta, cache, cos, sin, h, device, head, embed, C, Dz, start_id, end_id, num_image_tokens, max_new_tokens,
+                 eos_ids, poll=8):
+        if len(eos_ids) > ops.GREEDY_MAX_EOS:
+            raise ValueError(f"{len(eos_ids)} eos ids: the device loop takes up to {ops.GREEDY_MAX_EOS}")
+        if C > embed.shape[0]:
+            raise ValueError(f"{C} logits over an embedding of {embed.shape[0]} rows: an argmax id would be no row of it")
+        if int(poll) < 1:
+            raise ValueError(f"mm355_greedy_poll_steps = {poll}: the live counter is read every poll >= 1 steps")
+        B = cache.batch
+        self.args = (layers, meta, cache, cos, sin)
+        self.cache, self.head, self.embed, self.C = cache, head, embed, int(C)
+        self.max_new_tokens, self.poll = int(max_new_tokens), int(poll)
+        self.scalars = (int(start_id), int(end_id), int(num_image_tokens), self.max_new_tokens, sorted(int(e) for e in eos_ids))
+        cap = self.max_new_tokens + 1                        # iterations of the loop: total_out > max_new_tokens ends it
+        self.x_in = torch.zeros((B, h), device=device, dtype=BF16)
+        self.state = torch.zeros((len(GREEDY_STATE), B), device=device, dtype=torch.int32)
+        self.live = torch.full((1,), B, device=device, dtype=torch.int32)
+        self.logits = torch.empty((B, self.C), device=device, dtype=torch.float32)
+        self.tok = torch.zeros(B, device=device, dtype=torch.int32)
+        self.arg_ws = ops.argmax_rows_ws(B, self.C, device)
+        self.tok_log = torch.zeros((B, cap), device=device, dtype=torch.int32)
+        self.z_log = torch.zeros((B, cap, Dz), device=device, dtype=BF16)
+        self.graphs = {}                                     # kv bound -> graph
+        self.capture_ok = VARIANTS["decode_graph"]
+        self.host_reads = 0
+        self.steps = 0
+
+    def _tail(self, x):
+        fed, pred_z = self.head(x, self.state[0], self.logits)
+        ops.argmax_rows(self.logits, out=self.tok, ws=self.arg_ws)
+        ops.greedy_advance(self.tok, self.C, self.state, self.live, self.embed, fed, pred_z, self.x_in, self.tok_log, self.z_log,
+                           *self.scalars)
+
+    def _launches(self, bound=None):
+        self._tail(decoder_decode_row(self.x_in, *self.args, kv_bound=bound))
+
+    def _capture(self, bound):
+        cache = self.cache
+        keep = list(cache.lengths)
+        done = self.state[3].clone()
+        try:
+            self.state[3].fill_(1)                               # the warm-up runs for real: with every sequence done it logs and feeds nothing
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self._launches(bound)
+            torch.cuda.current_stream().wait_stream(side)
+            cache.set_lengths(keep)                              # (the warm-up's scratch cache row is overwritten by the next real step)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._launches(bound)
+            cache.lengths = keep                                 # capture records, it does not run: host mirror unchanged
+            self.graphs[bound] = g
+        except Exception as e:                                   # pragma: no cover - depends on the runtime
+            import warnings
+            warnings.warn(f"hipGraph capture of the greedy step failed ({e!r}); using eager launches")
+            self.capture_ok = False
+            self.graphs = {}
+            cache.set_lengths(keep)
+        self.state[3].copy_(done)
+
+    def _step(self):
+        if self.capture_ok:
+            bound = decode_kv_bound(self.cache)
+            if bound not in self.graphs:
+                self._capture(bound)
+        if not self.capture_ok:
+            return self._launches()
+        if self.cache.length >= self.cache.max_len:
+            raise ValueError(f"KV cache full ({self.cache.max_len} rows)")
+        self.graphs[bound].replay()
+        self.cache.lengths = [n + 1 for n in self.cache.lengths]
+
+    def run(self, x0):
+        """x0 [B, h]: the prompt pass's last hidden row of every sequence (pre final norm).  The first iteration's head and advance run on
+        it without a decoder step; then up to max_new_tokens steps.  Returns (ids, pred_z): per sequence its int32 ids and its [n_b, Dz]
+        bf16 image rows."""
+        self._tail(x0.contiguous())
+        for s in range(self.max_new_tokens):
+            self._step()
+            self.steps += 1
+            if self.steps % self.poll == 0 and s + 1 < self.max_new_tokens:
+                self.host_reads += 1
+                if int(self.live.item()) == 0:
+                    break
+        self.host_reads += 1
+        st = self.state.cpu()
+        if not bool(st[3].all()):                               # pragma: no cover - max_new_tokens steps finish every sequence by construction
+            raise RuntimeError(f"greedy loop: sequences still live after {self.steps} steps (state {st.tolist()})")
+        n_tok, n_z = st[4].tolist(), st[5].tolist()
+        return ([self.tok_log[b, :n_tok[b]].clone() for b in range(len(n_tok))], [self.z_log[b, :n_z[b]].clone() for b in range(len(n_z))])
 
 
 class GeluFn(Function):

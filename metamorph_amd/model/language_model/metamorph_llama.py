@@ -550,10 +550,20 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
                       temperature=None, top_p=None, num_beams=None, max_new_tokens=1024, use_cache=None, output_image=False):
         """Token mode / continuous 'image mode' greedy loop.  use_cache=False re-runs the prefix every step exactly like
         the reference (which forces use_cache=False, O(L^2)); the default keeps a KV cache and feeds one row per step
-        through the decode-shape kernels -- same state machine, same outputs."""
+        through the decode-shape kernels -- same state machine, same outputs.
+        A batch (inputs_embeds [B, L, h], B > 1; attention_mask all-valid or LEFT-padded, padding rows are never computed or cached) runs
+        the loop of every sequence at once with the token loop on the device (functional.GreedyLoopGraph): `output` is then a list of B
+        int32 id tensors and the image rows a list of B [n_b, Dz] tensors.  functional.set_variant("greedy_loop_b1", True) sends one
+        sequence through the same loop (return shapes as for one sequence)."""
         if use_cache is None or use_cache:
+            if inputs_embeds.shape[0] != 1 or F.VARIANTS["greedy_loop_b1"]:
+                return self._greedy_decode_loop(inputs_embeds, attention_mask, start_image_token_id, end_image_token_id, eos_token_id,
+                                                max_new_tokens, output_image)
             return self._greedy_decode_cached(inputs_embeds, start_image_token_id, end_image_token_id, eos_token_id,
                                               max_new_tokens, output_image)
+        if inputs_embeds.shape[0] != 1:
+            raise NotImplementedError(f"greedy_decode(use_cache=False) handles one sequence (as the reference's loop does), got "
+                                      f"{inputs_embeds.shape[0]}; a batch runs on the KV cache (use_cache=True)")
         in_image_mode = False
         generated, image_embeds = [], []
         total_image_tokens = 0
@@ -709,8 +719,7 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
 
     def _greedy_decode_cached(self, inputs_embeds, start_image_token_id, end_image_token_id, eos_token_id, max_new_tokens,
                               output_image):
-        if inputs_embeds.shape[0] != 1:
-            raise NotImplementedError("greedy_decode handles one sequence (as the reference's loop does)")
+        assert inputs_embeds.shape[0] == 1                     # (a batch takes _greedy_decode_loop)
         if inputs_embeds.dtype != BF16:
             raise TypeError(f"inputs_embeds must be bf16, got {inputs_embeds.dtype}")
         dev = inputs_embeds.device
@@ -764,11 +773,90 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         output = [torch.tensor(generated, dtype=torch.int32, device=dev)]
         return (output, emb) if output_image else output
 
+    # ------------------------------------------------------------------ the greedy loop of a batch, token loop on the device
+    def _lm_head_into(self, hid, out):
+        """fp32 logits of the rows `hid` into `out` [n, V]: the dispatch of _rows_logits / _lm_head_w8."""
+        n = hid.shape[0]
+        if self.w8_lm_head is not None:
+            q, scale = self.w8_lm_head
+            if n <= 16:
+                return ops.gemv_w8(hid, q, scale, out=out)
+            if F.VARIANTS["w8_gemm"] and ops.gemm_w8_supported(n, hid.shape[1]):
+                return ops.gemm_w8(hid, q, scale, out=out)
+            return ops.gemm(hid, ops.dequant_w8(q, scale), out=out)
+        w = self.lm_head.weight.data
+        if n <= 32 and ops.gemv_supported(hid, w):
+            return ops.gemv(hid, w, out=out)
+        return ops.gemm(hid, w, out=out)
+
+    def _head_rows_device(self, x, in_image, logits_out):
+        """_head_row for every sequence with the mode on the device: final norm, the image head (vision_head -> normalize -> mm_projector,
+        reference :363-377) for ALL rows, mm355_rows_select_bf16 by `in_image` (int32 [B]), fp32 logits into `logits_out`.  The launch
+        sequence does not depend on the modes.  Returns (the rows the lm_head saw, pred_z)."""
+        B = x.shape[0]
+        hid = self.model.norm(x).contiguous()
+        pred_z = self.vision_head(hid)
+        if self.normalize_vision:
+            pred_z = ops.bilinear_l2norm(pred_z.view(B, 1, -1).contiguous(), 1, 1, True).view(B, -1)
+        if self.apply_softmax:
+            pred_z = ops.softmax_rows(pred_z.contiguous(), 0.07)
+        pred_z = pred_z.contiguous()
+        fed = ops.rows_select(in_image, self.model.mm_projector(pred_z).contiguous(), hid)
+        self._lm_head_into(fed, logits_out)
+        return fed, pred_z
+
+    @staticmethod
+    def _left_pads(attention_mask, B, n):
+        """Padding rows in front of every sequence of a [B, n] prompt batch (None / all-valid: none); right padding is refused."""
+        pads = [0] * B
+        if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
+            m = attention_mask.to(torch.bool).cpu()
+            if tuple(m.shape) != (B, n):
+                raise ValueError(f"attention_mask {tuple(m.shape)} does not match the prompt batch {(B, n)}")
+            for b in range(B):
+                nb = int(m[b].sum())
+                if nb == 0 or not bool(m[b, n - nb:].all()):
+                    raise NotImplementedError("cached decoding takes LEFT-padded prompts (valid rows at the end); right padding puts pad rows "
+                                              "between the prompt and the generated tokens in the reference as well")
+                pads[b] = n - nb
+        return pads
+
+    def _greedy_decode_loop(self, inputs_embeds, attention_mask, start_image_token_id, end_image_token_id, eos_token_id, max_new_tokens,
+                            output_image):
+        """greedy_decode of B sequences: the prompt pass of _prefill_batch (same-length prompts as one batch, ragged ones one after the
+        other), then functional.GreedyLoopGraph -- one pass over the weights per step for all sequences, head, argmax and the reference's
+        mode state machine on the device.  The host reads the live counter every config.mm355_greedy_poll_steps steps (default 8: at most
+        7 wasted steps per call against one synchronisation per 8 tokens; a judgement, tools/bench_greedy_batch.py gives the numbers)."""
+        if inputs_embeds.dtype != BF16:
+            raise TypeError(f"inputs_embeds must be bf16, got {inputs_embeds.dtype}")
+        dev = inputs_embeds.device
+        B, n, h = inputs_embeds.shape
+        pads = self._left_pads(attention_mask, B, n)
+        F.params_ready(None)
+        max_new_tokens = int(max_new_tokens)
+        seqs = [inputs_embeds[b, pads[b]:].reshape(n - pads[b], h) for b in range(B)]
+        cache = HipKVCache(capacity=max(x.shape[0] for x in seqs) + max_new_tokens + 2)
+        outs = self._prefill_batch(seqs, cache, stepper=False, chunk=self._prefill_chunk_rows())
+        x0 = torch.stack([o[-1] for o in outs], 0)
+        embed = self.model.embed_tokens.weight.data
+        V = self.w8_lm_head[0].shape[0] if self.w8_lm_head is not None else self.lm_head.weight.shape[0]
+        loop = F.GreedyLoopGraph(self.model.layers, cache.meta, cache.kv, cache.meta.cos, cache.meta.sin, h, dev, self._head_rows_device,
+                                 embed, V, self._vision_head_out, start_image_token_id, end_image_token_id,
+                                 self.get_model().vision_tower.image_token_len, max_new_tokens, set(eos_token_id),
+                                 poll=getattr(self.config, "mm355_greedy_poll_steps", 8))
+        self._greedy_loop = loop                              # (tools / tests: steps, host_reads, the static logits of the last step)
+        ids, embs = loop.run(x0)
+        if B == 1:                                            # one sequence: the return shapes of _greedy_decode_cached
+            embs = embs[0] if embs[0].shape[0] else torch.tensor([], dtype=torch.float32, device=dev)
+        return (ids, embs) if output_image else ids
+
     # ------------------------------------------------------------------ HF generate() on the decode kernels (reference :711-738)
-    def _prefill_batch(self, seqs, cache):
+    def _prefill_batch(self, seqs, cache, stepper=True, chunk=None):
         """Prompt pass of a batch: seqs = one [L_b, h] tensor of prompt rows per sequence (padding already stripped) -> their hidden rows
         (pre final norm), one [L_b, h] tensor each; allocates and fills `cache.kv` and captures the per-token step.  Prompts of one length
-        (the beams of a beam search, an unpadded batch) go through the decoder as ONE batch; ragged prompts one after the other."""
+        (the beams of a beam search, an unpadded batch) go through the decoder as ONE batch; ragged prompts one after the other.
+        stepper=False: no DecodeStepGraph is captured (the greedy loop brings its own step); chunk: rows per slice of a chunked prompt pass
+        (functional.decoder_prefill_chunked), one sequence after the other."""
         dev = seqs[0].device
         B, h = len(seqs), seqs[0].shape[1]
         lens = [int(x.shape[0]) for x in seqs]
@@ -782,7 +870,7 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         cache.kv = F.KVCache(len(self.model.layers), cap, meta.Hkv * meta.d, dev, Hq=meta.Hq, d=meta.d, batch=B,
                              fmt=self._kv_cache_format(cache.kv_format))
         cache.meta = meta
-        if B > 1 and all(n == L0 for n in lens):
+        if B > 1 and all(n == L0 for n in lens) and (chunk is None or L0 <= chunk):
             _, mb = self._decode_meta(L0)
             mb.B, mb.cos, mb.sin = B, cos, sin
             rows = F.decoder_prefill(torch.cat(seqs, 0), self.model.layers, mb, cache.kv)
@@ -792,8 +880,12 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
             for b, x2d in enumerate(seqs):
                 _, mb = self._decode_meta(lens[b])
                 mb.cos, mb.sin = cos, sin
-                out.append(F.decoder_prefill(x2d.contiguous(), self.model.layers, mb, cache.kv, row=b))
-        cache.stepper = F.DecodeStepGraph(self.model.layers, meta, cache.kv, cos, sin, h, dev)
+                if chunk is None:
+                    out.append(F.decoder_prefill(x2d.contiguous(), self.model.layers, mb, cache.kv, row=b))
+                else:
+                    out.append(F.decoder_prefill_chunked(x2d.contiguous(), self.model.layers, mb, cache.kv, chunk, row=b))
+        if stepper:
+            cache.stepper = F.DecodeStepGraph(self.model.layers, meta, cache.kv, cos, sin, h, dev)
         return out
 
     def _decode_batch(self, x, cache):
@@ -862,17 +954,7 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
             # its attention mask (the reference: HF generate derives position_ids = cumsum(mask) - 1 from it, so every row is decoded
             # exactly as it would be alone).  Here the padding rows are never computed or cached: each sequence keeps its own length,
             # `pads` only restores the common length HF counts.
-            pads = [0] * B
-            if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
-                m = attention_mask.to(torch.bool).cpu()
-                if tuple(m.shape) != (B, n):
-                    raise ValueError(f"attention_mask {tuple(m.shape)} does not match the prompt batch {(B, n)}")
-                for b in range(B):
-                    nb = int(m[b].sum())
-                    if nb == 0 or not bool(m[b, n - nb:].all()):
-                        raise NotImplementedError("cached decoding takes LEFT-padded prompts (valid rows at the end); right padding puts pad rows "
-                                                  "between the prompt and the generated tokens in the reference as well")
-                    pads[b] = n - nb
+            pads = self._left_pads(attention_mask, B, n)
             cache.pads = pads
             seqs = [inputs_embeds[b, pads[b]:].reshape(n - pads[b], h) for b in range(B)]
             chunk = self._prefill_chunk_rows(cache)

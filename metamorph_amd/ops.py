@@ -1236,6 +1236,68 @@ def rows_gather(x2d, idx_i32, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ greedy loop tail (csrc/greedy.hip)
+
+GREEDY_MAX_EOS = 8                                           # MM355_GREEDY_MAX_EOS
+
+
+def argmax_rows_ws(R, C, device):
+    """the workspace of argmax_rows for [R, C] logits (mm355_argmax_rows_ws_bytes)"""
+    return torch.empty(int(_L().mm355_argmax_rows_ws_bytes(R, C)), device=device, dtype=torch.uint8)
+
+
+def argmax_rows(x2d, out=None, ws=None):
+    """out[r] (int32) = torch.argmax(x2d[r]) of contiguous fp32 rows: lowest index among equal maxima, NaN beats every number."""
+    _chk_dev(x2d, out, ws)
+    assert x2d.dim() == 2 and x2d.is_contiguous() and x2d.dtype == torch.float32
+    R, C = x2d.shape
+    if out is None:
+        out = torch.empty(R, device=x2d.device, dtype=torch.int32)
+    if ws is None:
+        ws = argmax_rows_ws(R, C, x2d.device)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == R
+    _lib.check(_L().mm355_argmax_rows_f32(x2d.data_ptr(), R, C, out.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
+               f"mm355_argmax_rows_f32 R={R} C={C}")
+    return out
+
+
+def rows_select(mask_i32, a2d, b2d, out=None):
+    """out[r] = a2d[r] if mask_i32[r] else b2d[r] (bf16 rows, int32 mask on the device)"""
+    _chk_dev(mask_i32, a2d, b2d, out)
+    pa, R, h, lda = _rows2d(a2d)
+    pb, Rb, hb, ldb = _rows2d(b2d)
+    assert (R, h) == (Rb, hb) and a2d.dtype == BF16 and b2d.dtype == BF16 and mask_i32.dtype == torch.int32 and mask_i32.numel() == R
+    if out is None:
+        out = torch.empty((R, h), device=a2d.device, dtype=BF16)
+    po, _, _, ldo = _rows2d(out)
+    _lib.check(_L().mm355_rows_select_bf16(pa, lda, pb, ldb, mask_i32.data_ptr(), po, ldo, R, h, _stream()), "mm355_rows_select_bf16")
+    return out
+
+
+def greedy_advance(tok, C, state, live, embed, fed, pred_z, x_in, tok_log, z_log, start_id, end_id, num_image_tokens, max_new_tokens,
+                   eos_ids):
+    """One transition of the greedy loop for every sequence on the device (mm355_greedy_advance; the model of it on plain ints is
+    functional.greedy_advance_host).  tok [B] int32: this step's argmax over C logits; state: int32 [6, B] rows in_image, n_img, total_out,
+    done, n_tokens, n_z; live: int32 [1]; embed [rows >= C, h]; fed [B, h] / pred_z [B, Dz]: the lm_head input rows and the image head's
+    rows; writes x_in [B, h], tok_log [B, token_cap] int32 and z_log [B, z_cap, Dz] bf16."""
+    _chk_dev(tok, state, live, embed, fed, pred_z, x_in, tok_log, z_log)
+    B = tok.numel()
+    assert tok.dtype == torch.int32 and state.dtype == torch.int32 and tuple(state.shape) == (6, B) and state.is_contiguous()
+    assert live.dtype == torch.int32 and tok_log.dtype == torch.int32 and tok_log.is_contiguous() and z_log.is_contiguous() and z_log.dtype == BF16
+    pe, rows, h, lde = _rows2d(embed)
+    pf, _, _, ldf = _rows2d(fed)
+    pz, _, Dz, ldz = _rows2d(pred_z)
+    px, _, _, ldx = _rows2d(x_in)
+    assert fed.shape == x_in.shape == (B, h) and pred_z.shape[0] == B and tok_log.shape[0] == B and z_log.shape[0] == B and z_log.shape[2] == Dz
+    eos = [int(e) for e in eos_ids]
+    arr = (_lib.ctypes.c_int32 * max(len(eos), 1))(*eos)
+    s = [state[i].data_ptr() for i in range(6)]
+    _lib.check(_L().mm355_greedy_advance(tok.data_ptr(), B, int(C), *s, live.data_ptr(), pe, lde, rows, pf, ldf, pz, ldz, px, ldx, h, Dz,
+                                         tok_log.data_ptr(), tok_log.shape[1], z_log.data_ptr(), z_log.shape[1], int(start_id), int(end_id),
+                                         int(num_image_tokens), int(max_new_tokens), _lib.ctypes.addressof(arr), len(eos), _stream()),
+               f"mm355_greedy_advance B={B} C={C} eos={len(eos)}")
+
+
 def rows_scatter_add_(dst2d, src2d, idx_i32):
     _chk_dev(dst2d, src2d, idx_i32)
     ps, R, h, lds = _rows2d(src2d)
