@@ -890,7 +890,7 @@ def test_swiglu_gelu(ops):
     dgu, act2 = ops.swiglu_bwd(gu.to(DEV), da.to(DEV), I)
     close(dgu[:, :I], g.grad, 1e-2, 1e-2, "swiglu dgate")
     close(dgu[:, I:], u.grad, 1e-2, 1e-2, "swiglu dup")
-    assert torch.equal(act2.cpu(), act.cpu())
+    assert torch.equal(act2.cpu(), act.cpu())                    # (every gate pattern and 650 x 14 336: tests/test_helpers_gpu.py)
     x, dy = rnd(40, 256, seed=3), rnd(40, 256, seed=4)
     for kind, fn in ((0, R.gelu_erf), (1, R.gelu_tanh)):
         xf = x.float().requires_grad_(True)
@@ -1163,7 +1163,8 @@ def test_softmax_rows(ops):
     (y * dy.float()).sum().backward()
     got = ops.softmax_rows(x.to(DEV), 0.07)
     close(got, y, 2e-2, 1e-6, "softmax rows")
-    assert abs(float(got.float().sum(-1).mean()) - 1.0) < 5e-3
+    # every row, not their mean: within C * 2^-9, and within 2^-8 (one bf16 step per element, summed over a row that sums to 1)
+    assert bool(((got.double().sum(-1) - 1.0).abs() <= min(C * 2.0 ** -9, 2.0 ** -8)).all())
     dx = ops.softmax_rows_bwd(got, dy.to(DEV), 0.07)
     close(dx, xf.grad, 5e-2, 3e-2 * float(xf.grad.abs().max()), "softmax rows bwd")
 
@@ -1635,7 +1636,7 @@ def test_adamw_and_norm(ops):
         R.adamw_step(p, gr, m, v, step, 1e-2, 0.9, 0.95, 1e-8, 0.1, grad_scale=0.5)
         ops.adamw_shard_(pd, md, vd, gr.to(DEV), pout, 1e-2, 0.9, 0.95, 1e-8, 0.1, step, coef)
     close(pd, p, 1e-5, 1e-6, "adamw master")
-    assert torch.equal(pout.cpu(), p.bfloat16()) or (pout.float().cpu() - p).abs().max() < 1e-2
+    assert torch.equal(pout, pd.bfloat16())                      # p_out is the device's own master rounded to bf16, bit for bit
     x = rnd(4099, seed=2)
     s = torch.zeros(1, device=DEV)
     ops.sumsq_(x.to(DEV), s)
