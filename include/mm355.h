@@ -705,6 +705,34 @@ int mm355_greedy_advance(const int32_t* tok, int64_t B, int64_t C, int32_t* in_i
                          int max_new_tokens, const int32_t* eos_ids, int n_eos, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Sampled decoding in the same loop: the two kernels that stand where argmax_rows_f32 stands (functional.GreedyLoopGraph(sampler=...)).
+ * philox_uniform_rows: u[r] = (word 0 of Philox4x32-10 with key (seed low 32, seed high 32) and counter (counters[r], stream_ids[r], 0, 0)
+ *         >> 8) * 2^-24, in [0, 1); stream_ids, counters (int32, read as uint32) and u are device arrays of R entries.  Stateless: a draw
+ *         is a function of (seed, stream id, counter) alone -- in the loop the counter is the sequence's total_out, so warm-up launches,
+ *         captures, polling and the batch a sequence rides in cannot move it.  The host model: functional.philox_uniform_host.
+ * sample_rows_f32: out[r] (int32) = one draw from row r of the contiguous fp32 logits x [R, C] (bounds on R and C as for argmax_rows_f32)
+ *         under HF's temperature -> top-k -> top-p -> multinomial, written without a sort.  With m the row maximum:
+ *           m NaN, +inf or -inf:  out[r] = argmax_rows_f32's index, stats = (m, 0)
+ *           w_i = exp((x_i - m) * inv_temperature) in fp32 (v_exp_f32: a few 1e-6 relative); -inf weighs 0
+ *           top-k:  i is kept iff #{j: x_j > x_i} < top_k (0 or >= C: off; ties at the k-th value are all kept)
+ *           top-p:  of those, i is kept iff sum_{x_j > x_i} w_j < top_p * sum_{kept by top-k} w_j (>= 1: off; the maximum is always kept)
+ *           so the kept set is {x_i >= tau}, tau a value of the row (no filter: its minimum); Z = sum of w over it
+ *           out[r] = the smallest kept i with w_0 + .. + w_i (kept terms, index order) > u[r] * Z; if rounding leaves none, the last kept i
+ *         stats (nullable, fp32 [R, 2]) receives (tau, Z).  One workgroup per row, so a row's result is a bit-reproducible function of the
+ *         row, u[r] and the scalars, whatever R and the other rows are.  tau comes from two 5-round selects (256 linear bins over the
+ *         row's range, then the four bytes of an order-preserving key) on integer LDS histograms: counts for top-k, weights in fixed point
+ *         (w * 2^40, exact integer sums) for top-p, whose boundary can therefore sit one token off the fp32 one where the mass above a
+ *         token is within ~1e-6 * Z of top_p * Z.  Z and the pick's prefixes are fp32 trees (per-lane partials over C / 16384 terms,
+ *         wave butterflies, 16 chunk sums per wave and the 16 wave sums in index order); no floating-point atomics anywhere.  The workspace is unused by this one-workgroup
+ *         form (sample_rows_ws_bytes returns 0, workspace may be null); inv_temperature not finite or <= 0, top_k < 0, top_p outside
+ *         (0, 1]: MM355_EINVAL.  The host model: functional.sample_row_host.
+ * ------------------------------------------------------------------------------------------------ */
+int mm355_philox_uniform_rows(uint64_t seed, const int32_t* stream_ids, const int32_t* counters, float* u, int64_t R, void* stream);
+int64_t mm355_sample_rows_ws_bytes(int64_t R, int64_t C);
+int mm355_sample_rows_f32(const float* x, int64_t R, int64_t C, float inv_temperature, int top_k, float top_p, const float* u,
+                          int32_t* out, float* stats, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * ZeRO-2 shard update (replaces DeepSpeed zero2.json + HF adamw_torch, train.py:82): AdamW on the
  * rank's fp32 master shard, writes the updated bf16 parameters.  grad_scale_dev (nullable) is a device
  * scalar multiplied into the gradient (1/world, clip coefficient).

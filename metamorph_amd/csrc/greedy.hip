@@ -1,7 +1,7 @@
 // The greedy loop's per-token tail on the device (reference metamorph_llama.py:502-597): argmax of the fp32 logits rows, the row select
 // that picks the lm_head input per sequence, and the reference loop's mode state machine with the gather of the next input row.  With
 // these three the host reads nothing per token: one captured graph is one whole token for every sequence (functional.GreedyLoopGraph).
-#include "mm355_common.h"
+#include "argrows.h"
 
 #include <limits.h>
 
@@ -9,23 +9,6 @@ namespace {
 
 constexpr int ARG_NT = 256;
 constexpr int ARG_CHUNK = 4096;                              // columns per (row, chunk) partial: 16 per thread
-
-// torch.argmax's order: a NaN beats every number, among equals (and among NaNs) the lowest index wins.  A total order on (value, index)
-// pairs with distinct indices, so any reduction tree gives the same winner.
-MM_DEV bool arg_beats(float cv, int ci, float bv, int bi) {
-    const bool cn = cv != cv, bn = bv != bv;
-    if (cn || bn) return cn && (!bn || ci < bi);
-    return cv > bv || (cv == bv && ci < bi);
-}
-
-MM_DEV void arg_wave(float& v, int& i) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o, 64);
-        const int oi = __shfl_xor(i, o, 64);
-        if (arg_beats(ov, oi, v, i)) { v = ov; i = oi; }
-    }
-}
 
 // the workgroup's winner in thread 0 (blockDim.x = ARG_NT)
 MM_DEV void arg_block(float& v, int& i, float* sv, int* si) {

@@ -8,6 +8,7 @@ them) -- the "contiguous_gradients" behaviour of the reference's DeepSpeed ZeRO-
 """
 from __future__ import annotations
 
+import math
 import os
 from collections import namedtuple
 
@@ -1471,6 +1472,73 @@ def greedy_advance_host(state, tok, start_id, end_id, num_image_tokens, max_new_
     return ("z", "fed") if image_row else ("tok", "embed")
 
 
+def philox4x32_10(counter4, key2):
+    """Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11) on plain ints: four 32-bit counter
+    words and two key words -> four output words.  The specification of the generator in mm355_philox_uniform_rows."""
+    c = [int(v) & 0xFFFFFFFF for v in counter4]
+    k0, k1 = (int(v) & 0xFFFFFFFF for v in key2)
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c[0], 0xCD9E8D57 * c[2]
+        c = [(p1 >> 32) ^ c[1] ^ k0, p1 & 0xFFFFFFFF, (p0 >> 32) ^ c[3] ^ k1, p0 & 0xFFFFFFFF]
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return tuple(c)
+
+
+def philox_uniform_host(seed, stream_id, counter):
+    """The uniform in [0, 1) of (seed, stream id, counter): key = the seed's low and high 32 bits, counter = (counter, stream id, 0, 0),
+    the top 24 bits of output word 0 times 2^-24 (exact in fp32).  What mm355_philox_uniform_rows writes for one row."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return (philox4x32_10((counter, stream_id, 0, 0), (seed & 0xFFFFFFFF, seed >> 32))[0] >> 8) * 2.0 ** -24
+
+
+def sample_row_host(x, inv_t, top_k, top_p, u, eps=0.0, tau=None):
+    """One row of mm355_sample_rows_f32 in fp64: the specification of the sampler, as greedy_advance_host is of the transition.  x: the row
+    (any float sequence), u in [0, 1).  Returns (candidates, tau_lo, tau_hi, Z).
+    Weights w_i = exp((x_i - m) * inv_t), m the maximum.  top-k keeps i iff #{x_j > x_i} < top_k (0 or >= C: off); of those, top-p keeps
+    i iff the weight above x_i is < top_p * Zk, Zk the weight top-k kept (>= 1: off): the kept set is {x_i >= tau}.
+    eps = 0: tau_lo = tau_hi = tau, Z the kept weight and candidates the one index whose interval [P_(i-1), P_i) of the kept weights'
+    running sum in index order holds u * Z.  eps > 0 gives the bands an fp32 implementation is held to: the top-p comparison is taken at
+    (top_p -+ eps) * Zk -- tau_hi is the tau of the smaller threshold, tau_lo that of the larger one, both values of the row, the top-k
+    part exact -- and candidates are the kept indices of positive weight whose interval meets [(u - eps) Z, (u + eps) Z], plus the last
+    kept index where (u + eps) Z reaches Z (rounding may leave no index).  tau: evaluate Z and the candidates for the kept set
+    {x_i >= tau} (an implementation's own tau out of the band) instead of the eps = 0 one.
+    A maximum that is NaN or infinite: ([torch.argmax's index], m, m, 0.0)."""
+    import numpy as np
+    x = np.asarray(x, dtype=np.float64)
+    C = x.shape[0]
+    nan = np.isnan(x)
+    m = float("nan") if nan.any() else float(x.max())
+    if not math.isfinite(m):
+        return [int(np.argmax(nan)) if nan.any() else int(np.argmax(x))], m, m, 0.0
+    w = np.exp((x - m) * float(inv_t))
+    vals, inv, counts = np.unique(x, return_inverse=True, return_counts=True)       # ascending distinct values
+    mass = np.bincount(inv.reshape(-1), weights=w, minlength=len(vals))
+    n_above = counts[::-1].cumsum()[::-1] - counts
+    m_above = np.concatenate((mass[::-1].cumsum()[::-1][1:], [0.0]))                # (summed from the top: no cancellation)
+    k_on = 0 < int(top_k) < C
+    kept_k = n_above < int(top_k) if k_on else np.ones(len(vals), dtype=bool)
+    j_k = int(np.argmax(kept_k))                                                    # kept_k is a suffix of the ascending values
+    Zk = m_above[j_k] + mass[j_k]
+
+    def tau_of(p):
+        if float(top_p) >= 1.0:
+            return float(vals[j_k])
+        kept = kept_k & (m_above < p * Zk)
+        kept[-1] = True
+        return float(vals[int(np.argmax(kept))])
+    tau_lo, tau_hi = tau_of(float(top_p) + eps), tau_of(float(top_p) - eps)
+    t = tau_of(float(top_p)) if tau is None else float(tau)
+    idx = np.nonzero(x >= t)[0]
+    P = np.cumsum(w[idx])
+    Z = math.fsum(w[idx])
+    lo, hi = (u - eps) * Z, (u + eps) * Z
+    prev = np.concatenate(([0.0], P[:-1]))
+    cand = idx[(w[idx] > 0) & (P > lo) & (prev <= hi)].tolist()
+    if hi >= Z and int(idx[-1]) not in cand:
+        cand.append(int(idx[-1]))
+    return [int(c) for c in cand], tau_lo, tau_hi, Z
+
+
 class GreedyLoopGraph:
     """The greedy text-and-image loop (reference metamorph_llama.py:502-597) of a batch with the token loop on the device.  One step is
     decoder_decode_row (all rows, whatever route the batch size takes) -> `head` (the model's final norm, image head for ALL rows, row select
@@ -1481,10 +1549,14 @@ class GreedyLoopGraph:
     `poll` steps -- the only device -> host read of the loop (`host_reads` counts them, the final read of the results included).  A finished
     sequence keeps riding along: mm355_greedy_advance writes nothing for it, its cache rows grow and nobody reads them (the cache's
     max(L_b) + max_new_tokens + 2 rows cover max_new_tokens steps for every sequence), so the results do not depend on `poll`.
-    head(x [B, h], in_image int32 [B], logits_out f32 [B, C]) -> (fed [B, h], pred_z [B, Dz])."""
+    head(x [B, h], in_image int32 [B], logits_out f32 [B, C]) -> (fed [B, h], pred_z [B, Dz]).
+    sampler = (inv_temperature, top_k, top_p, seed, stream_ids): the id is drawn instead of taken as the argmax -- mm355_philox_uniform_rows
+    (seed, stream_ids[b], the sequence's total_out) -> mm355_sample_rows_f32 (sample_row_host) in place of the argmax, everything else as
+    it is.  The uniforms are stateless, so the warm-up launch and the capture consume no draw and a sequence's draws depend on (seed, its
+    stream id, its total_out) only; an image row ignores the id as before, its draw is unused.  `seed` records the seed."""
 
     def __init__(self, layers, meta, cache, cos, sin, h, device, head, embed, C, Dz, start_id, end_id, num_image_tokens, max_new_tokens,
-                 eos_ids, poll=8):
+                 eos_ids, poll=8, sampler=None):
         if len(eos_ids) > ops.GREEDY_MAX_EOS:
             raise ValueError(f"{len(eos_ids)} eos ids: the device loop takes up to {ops.GREEDY_MAX_EOS}")
         if C > embed.shape[0]:
@@ -1502,7 +1574,18 @@ class GreedyLoopGraph:
         self.live = torch.full((1,), B, device=device, dtype=torch.int32)
         self.logits = torch.empty((B, self.C), device=device, dtype=torch.float32)
         self.tok = torch.zeros(B, device=device, dtype=torch.int32)
-        self.arg_ws = ops.argmax_rows_ws(B, self.C, device)
+        self.sampler, self.seed = None, None
+        if sampler is None:
+            self.arg_ws = ops.argmax_rows_ws(B, self.C, device)
+        else:
+            inv_t, top_k, top_p, seed, stream_ids = sampler
+            if len(stream_ids) != B:
+                raise ValueError(f"{len(stream_ids)} stream ids for {B} sequences")
+            self.sampler = (float(inv_t), int(top_k), float(top_p))
+            self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+            self.stream_ids = torch.tensor([int(i) for i in stream_ids], dtype=torch.int32).to(device)
+            self.u = torch.zeros(B, device=device, dtype=torch.float32)
+            self.smp_ws = ops.sample_rows_ws(B, self.C, device)
         self.tok_log = torch.zeros((B, cap), device=device, dtype=torch.int32)
         self.z_log = torch.zeros((B, cap, Dz), device=device, dtype=BF16)
         self.graphs = {}                                     # kv bound -> graph
@@ -1512,7 +1595,11 @@ class GreedyLoopGraph:
 
     def _tail(self, x):
         fed, pred_z = self.head(x, self.state[0], self.logits)
-        ops.argmax_rows(self.logits, out=self.tok, ws=self.arg_ws)
+        if self.sampler is None:
+            ops.argmax_rows(self.logits, out=self.tok, ws=self.arg_ws)
+        else:
+            ops.philox_uniform_rows(self.seed, self.stream_ids, self.state[2], out=self.u)
+            ops.sample_rows(self.logits, *self.sampler, self.u, out=self.tok, ws=self.smp_ws)
         ops.greedy_advance(self.tok, self.C, self.state, self.live, self.embed, fed, pred_z, self.x_in, self.tok_log, self.z_log,
                            *self.scalars)
 

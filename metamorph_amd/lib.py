@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes
 import os
 import re
-from ctypes import c_char_p, c_float, c_int, c_int64, c_uint32, c_void_p
+from ctypes import c_char_p, c_float, c_int, c_int64, c_uint32, c_uint64, c_void_p
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MM355_LIB_PATH") or os.path.join(PKG, "lib", "libmm355.so")   # (override: timing-only ablation builds, tools/)
@@ -27,7 +27,7 @@ _lib = None
 _load_error = None
 
 _CTYPE = {
-    "int": c_int, "int64_t": c_int64, "uint32_t": c_uint32, "float": c_float,
+    "int": c_int, "int64_t": c_int64, "uint32_t": c_uint32, "uint64_t": c_uint64, "float": c_float,
 }
 
 

@@ -19,6 +19,7 @@ from __future__ import annotations
 
 
 import copy
+import math
 import numpy as np
 import torch
 import torch.nn as nn
@@ -547,18 +548,29 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
     @torch.no_grad()
     def greedy_decode(self, position_ids, attention_mask, inputs_embeds, start_image_token_id=DEFAULT_IMAGE_START_ID,
                       end_image_token_id=DEFAULT_IMAGE_END_ID, eos_token_id=(128001, 128009), do_sample=None,
-                      temperature=None, top_p=None, num_beams=None, max_new_tokens=1024, use_cache=None, output_image=False):
+                      temperature=None, top_p=None, num_beams=None, max_new_tokens=1024, use_cache=None, output_image=False,
+                      top_k=None, seed=None, stream_ids=None):
         """Token mode / continuous 'image mode' greedy loop.  use_cache=False re-runs the prefix every step exactly like
         the reference (which forces use_cache=False, O(L^2)); the default keeps a KV cache and feeds one row per step
         through the decode-shape kernels -- same state machine, same outputs.
         A batch (inputs_embeds [B, L, h], B > 1; attention_mask all-valid or LEFT-padded, padding rows are never computed or cached) runs
         the loop of every sequence at once with the token loop on the device (functional.GreedyLoopGraph): `output` is then a list of B
         int32 id tensors and the image rows a list of B [n_b, Dz] tensors.  functional.set_variant("greedy_loop_b1", True) sends one
-        sequence through the same loop (return shapes as for one sequence)."""
+        sequence through the same loop (return shapes as for one sequence).
+        do_sample truthy AND temperature > 0 samples instead: every id is drawn from softmax(logits / temperature) after top_k (None / 0:
+        off) and top_p (None / 1: off) in HF's order, by mm355_sample_rows_f32 inside the same device loop (also for one sequence; image
+        rows are emitted as before).  Sequence b draws from the Philox stream (seed, stream_ids[b]) at its own output position, so a
+        sequence's ids do not depend on the batch it rides in; seed=None takes 64 bits from torch's CPU generator (torch.manual_seed
+        repeats a run), stream_ids defaults to range(B).  Any other do_sample / temperature (None or 0.0, the reference demo's call) is
+        the greedy loop, bit for bit."""
+        sampler = self._sampler_of(do_sample, temperature, top_k, top_p, num_beams, seed, stream_ids, inputs_embeds.shape[0])
+        if sampler is not None and not (use_cache is None or use_cache):
+            raise NotImplementedError("greedy_decode(do_sample=True, use_cache=False): sampling runs in the device loop on the KV cache "
+                                      "(use_cache=True)")
         if use_cache is None or use_cache:
-            if inputs_embeds.shape[0] != 1 or F.VARIANTS["greedy_loop_b1"]:
+            if inputs_embeds.shape[0] != 1 or F.VARIANTS["greedy_loop_b1"] or sampler is not None:
                 return self._greedy_decode_loop(inputs_embeds, attention_mask, start_image_token_id, end_image_token_id, eos_token_id,
-                                                max_new_tokens, output_image)
+                                                max_new_tokens, output_image, sampler=sampler)
             return self._greedy_decode_cached(inputs_embeds, start_image_token_id, end_image_token_id, eos_token_id,
                                               max_new_tokens, output_image)
         if inputs_embeds.shape[0] != 1:
@@ -821,8 +833,40 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
                 pads[b] = n - nb
         return pads
 
+    @staticmethod
+    def _sampler_of(do_sample, temperature, top_k, top_p, num_beams, seed, stream_ids, B):
+        """greedy_decode's sampling arguments -> GreedyLoopGraph's `sampler` tuple, or None for the greedy loop (do_sample falsy, or
+        temperature None / 0).  Refuses bad values by name before any device work."""
+        if not do_sample or temperature is None:
+            return None
+        temperature = float(temperature)
+        if not math.isfinite(temperature) or temperature < 0:
+            raise ValueError(f"greedy_decode: temperature = {temperature} must be finite and >= 0 (0: greedy)")
+        if temperature == 0:
+            return None
+        top_k = 0 if top_k is None else top_k
+        if isinstance(top_k, float) and not top_k.is_integer():
+            raise ValueError(f"greedy_decode: top_k = {top_k} must be an integer >= 0 (0: off)")
+        if int(top_k) < 0 or int(top_k) > 2**31 - 1:
+            raise ValueError(f"greedy_decode: top_k = {top_k} must be an integer >= 0 (0: off)")
+        top_p = 1.0 if top_p is None else float(top_p)
+        if not (0.0 < top_p <= 1.0):                             # (a NaN fails both comparisons)
+            raise ValueError(f"greedy_decode: top_p = {top_p} must lie in (0, 1] (1: off)")
+        if num_beams not in (None, 1):
+            raise ValueError(f"greedy_decode: num_beams = {num_beams} with do_sample=True: the device loop samples one continuation per "
+                             "sequence, beam search is not part of it (repeat the prompt and give each copy its own stream id)")
+        inv_t = 1.0 / temperature
+        if not math.isfinite(inv_t):
+            raise ValueError(f"greedy_decode: temperature = {temperature} is too small to divide by (0: greedy)")
+        if seed is None:
+            seed = int(torch.randint(-2**63, 2**63 - 1, (1,), dtype=torch.int64).item())
+        stream_ids = list(range(B)) if stream_ids is None else [int(i) for i in stream_ids]
+        if len(stream_ids) != B or any(i < 0 or i > 2**31 - 1 for i in stream_ids):
+            raise ValueError(f"greedy_decode: stream_ids = {stream_ids}: one id in [0, 2^31) per sequence ({B})")
+        return (inv_t, int(top_k), top_p, int(seed) & 0xFFFFFFFFFFFFFFFF, stream_ids)
+
     def _greedy_decode_loop(self, inputs_embeds, attention_mask, start_image_token_id, end_image_token_id, eos_token_id, max_new_tokens,
-                            output_image):
+                            output_image, sampler=None):
         """greedy_decode of B sequences: the prompt pass of _prefill_batch (same-length prompts as one batch, ragged ones one after the
         other), then functional.GreedyLoopGraph -- one pass over the weights per step for all sequences, head, argmax and the reference's
         mode state machine on the device.  The host reads the live counter every config.mm355_greedy_poll_steps steps (default 8: at most
@@ -843,7 +887,7 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         loop = F.GreedyLoopGraph(self.model.layers, cache.meta, cache.kv, cache.meta.cos, cache.meta.sin, h, dev, self._head_rows_device,
                                  embed, V, self._vision_head_out, start_image_token_id, end_image_token_id,
                                  self.get_model().vision_tower.image_token_len, max_new_tokens, set(eos_token_id),
-                                 poll=getattr(self.config, "mm355_greedy_poll_steps", 8))
+                                 poll=getattr(self.config, "mm355_greedy_poll_steps", 8), sampler=sampler)
         self._greedy_loop = loop                              # (tools / tests: steps, host_reads, the static logits of the last step)
         ids, embs = loop.run(x0)
         if B == 1:                                            # one sequence: the return shapes of _greedy_decode_cached

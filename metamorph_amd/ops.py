@@ -1261,6 +1261,46 @@ def argmax_rows(x2d, out=None, ws=None):
     return out
 
 
+def sample_rows_ws(R, C, device):
+    """the workspace of sample_rows for [R, C] logits (mm355_sample_rows_ws_bytes)"""
+    return torch.empty(int(_L().mm355_sample_rows_ws_bytes(R, C)), device=device, dtype=torch.uint8)
+
+
+def sample_rows(x2d, inv_temperature, top_k, top_p, u, out=None, stats=None, ws=None):
+    """out[r] (int32) = one draw from softmax(x2d[r] * inv_temperature) after top-k and top-p (HF's order; top_k 0 and top_p 1 are off)
+    with the uniform u[r] in [0, 1) (mm355_sample_rows_f32; the model of it is functional.sample_row_host).  stats: optional fp32 [R, 2],
+    receives (tau, Z) per row."""
+    _chk_dev(x2d, u, out, stats, ws)
+    assert x2d.dim() == 2 and x2d.is_contiguous() and x2d.dtype == torch.float32
+    R, C = x2d.shape
+    assert u.dtype == torch.float32 and u.is_contiguous() and u.numel() == R
+    if out is None:
+        out = torch.empty(R, device=x2d.device, dtype=torch.int32)
+    if ws is None:
+        ws = sample_rows_ws(R, C, x2d.device)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == R
+    assert stats is None or (stats.dtype == torch.float32 and stats.is_contiguous() and tuple(stats.shape) == (R, 2))
+    _lib.check(_L().mm355_sample_rows_f32(x2d.data_ptr(), R, C, float(inv_temperature), int(top_k), float(top_p), u.data_ptr(), out.data_ptr(),
+                                          _p(stats), _p(ws) if ws.numel() else 0, ws.numel() * ws.element_size(), _stream()),
+               f"mm355_sample_rows_f32 R={R} C={C} inv_temperature={inv_temperature} top_k={top_k} top_p={top_p}")
+    return out
+
+
+def philox_uniform_rows(seed, stream_ids, counters, out=None):
+    """out[r] (fp32 in [0, 1)) = the Philox4x32-10 uniform of (seed, stream_ids[r], counters[r]) (int32 device arrays;
+    mm355_philox_uniform_rows, on the host functional.philox_uniform_host)"""
+    _chk_dev(stream_ids, counters, out)
+    R = stream_ids.numel()
+    assert stream_ids.dtype == torch.int32 and counters.dtype == torch.int32 and counters.numel() == R
+    assert stream_ids.is_contiguous() and counters.is_contiguous()
+    if out is None:
+        out = torch.empty(R, device=stream_ids.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == R
+    _lib.check(_L().mm355_philox_uniform_rows(int(seed) & (2**64 - 1), stream_ids.data_ptr(), counters.data_ptr(), out.data_ptr(), R, _stream()),
+               f"mm355_philox_uniform_rows R={R}")
+    return out
+
+
 def rows_select(mask_i32, a2d, b2d, out=None):
     """out[r] = a2d[r] if mask_i32[r] else b2d[r] (bf16 rows, int32 mask on the device)"""
     _chk_dev(mask_i32, a2d, b2d, out)
