@@ -549,6 +549,40 @@ int mm355_attn_extend_f8(const mm355_bf16* q, int64_t ld_q, const uint8_t* k_cac
                          int64_t workspace_floats, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The decode step's attention for B sequences whose first shared_len cached rows are the SAME rows, stored once (csrc/attn_decode_shared.hip):
+ * n sampled continuations of one prompt.
+ *   attn_decode_shared: q [B][Hq*d] (ld_q), ALREADY rotated; k_shared / v_shared [shared_len][Hkv*d] (row stride ld_shared), one copy;
+ *         k_cache / v_cache [B][rows][Hkv*d] as mm355_attn_decode takes them; kv_lens[B] int32 on the device; o [B][Hq*d] (ld_o).  Query row b
+ *         attends the keys j in [0, kv_lens[b]): key j < shared_len is row j of k_shared / v_shared, key j >= shared_len is row j of sequence
+ *         b's own block (the own rows keep their absolute index, so the append kernels' position is still RoPE position and cache row).  o =
+ *         softmax(scale * q K^T) V with the softmax in fp32 and the scale applied on the fp32 side.  kv_lens[b] >= shared_len is the caller's
+ *         promise; kv_lens[b] == shared_len (no own rows) and shared_len == 0 are right.  Never read, whatever kv_lens[] says: rows [0,
+ *         shared_len) of any sequence's own block, shared rows >= shared_len, own rows >= min(kv_lens[b], max_kv_len).  shared_len and
+ *         max_kv_len (shared_len <= max_kv_len <= rows) are host launch parameters.  Shared rows: mm355_attn_extend's kernel with packed row
+ *         b * G + g (G = Hq / Hkv), so a shared K / V tile is read once per KV head and 64 / G sequences, the key tiles dealt to several
+ *         workgroups; own rows: one more workgroup per (sequence, KV head) in the same launch; a second launch merges the partials.  The
+ *         split is a function of (B, Hq, Hkv, shared_len) alone: the same arguments give the same bits.  The workspace
+ *         (mm355_attn_decode_shared_ws_floats floats, 16-byte aligned, never 0 for valid arguments) is always needed.
+ *   attn_decode_shared_f8: the same over e4m3 bytes and scales, for the shared rows ([shared_len][Hkv] scales, row stride ld_shared_scale) and
+ *         the own rows (as mm355_attn_decode_f8 takes them), widened to bf16 on the way into LDS: equal to mm355_attn_decode_shared on the
+ *         dequantised cache bit for bit.
+ *   Before any launch: fmt other than MM355_KV8_E4M3, a NULL pointer or scale, shared_len < 0 or > max_kv_len, Hq % Hkv != 0, q / o not
+ *   16-byte aligned or ld_q / ld_o % 8 != 0, cache pointers or strides not 16-byte (e4m3: 8-byte) aligned, a row stride shorter than a row, a
+ *   workspace that is missing or too small: MM355_EINVAL; d % 8 != 0, d > 128 or a GQA group other than 1, 2, 4, 8: MM355_EUNSUPPORTED.
+ * ------------------------------------------------------------------------------------------------ */
+int64_t mm355_attn_decode_shared_ws_floats(int64_t B, int64_t Hq, int64_t Hkv, int64_t d, int64_t shared_len, int64_t max_kv_len);
+int mm355_attn_decode_shared(const mm355_bf16* q, int64_t ld_q, const mm355_bf16* k_shared, const mm355_bf16* v_shared, int64_t ld_shared,
+                             const mm355_bf16* k_cache, const mm355_bf16* v_cache, int64_t ld_kv, int64_t batch_stride_kv,
+                             const int32_t* kv_lens, int64_t shared_len, int64_t max_kv_len, mm355_bf16* o, int64_t ld_o, int64_t B,
+                             int64_t Hq, int64_t Hkv, int64_t d, float scale, float* workspace, int64_t workspace_floats, void* stream);
+int mm355_attn_decode_shared_f8(const mm355_bf16* q, int64_t ld_q, const uint8_t* k_shared, const uint8_t* v_shared, int64_t ld_shared_bytes,
+                                const float* k_shared_scale, const float* v_shared_scale, int64_t ld_shared_scale, const uint8_t* k_cache,
+                                const uint8_t* v_cache, int64_t ld_kv_bytes, int64_t batch_stride_kv_bytes, const float* k_scale,
+                                const float* v_scale, int64_t ld_scale, int64_t batch_stride_scale, int fmt, const int32_t* kv_lens,
+                                int64_t shared_len, int64_t max_kv_len, mm355_bf16* o, int64_t ld_o, int64_t B, int64_t Hq, int64_t Hkv,
+                                int64_t d, float scale, float* workspace, int64_t workspace_floats, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Elementwise: SwiGLU (HF LlamaMLP; K12), GELU (projector / vision_head), scaling helpers.
  * gu = [M][2I] with gate in columns [0,I) and up in [I,2I).
  * ------------------------------------------------------------------------------------------------ */

@@ -14,11 +14,12 @@
 // The e4m3 form differs in the tile mover alone: 8 bytes per 8 columns plus the head-row's scale, widened to bf16 (exact: mm355.h, the
 // KV8 contract) where the tile is written into LDS.  Everything after that is the same code on the same bits.
 // Cache rows >= past[b] + n are never read: ragged tiles clamp their row index to the last visible row of the workgroup.
-#include "attn2.h"
+// The tile mover, the 64-key softmax step and the fold of the partials live in attn_tile.h, shared with attn_decode_shared.hip.
+#include "attn_tile.h"
 #include <algorithm>
 
 namespace {
-using namespace attn2;
+using namespace attn_tile;
 
 struct XArgs {
     const uint16_t* q; int64_t ld_q;
@@ -48,50 +49,10 @@ Plan make_plan(int64_t B, int64_t n, int64_t Hq, int64_t Hkv, int64_t max_kv_len
     return p;
 }
 
-template <int NV, bool F8> struct Stage;
-template <int NV> struct Stage<NV, false> { u32x4 r[NV]; };
-template <int NV> struct Stage<NV, true> { u32x2 r[NV]; float s[NV]; };
-
-// rows [row0, row0 + 64) of one KV head -> registers; rows past `end` repeat row end - 1 (masked by the caller), columns >= d are zero
-template <int DP, int NV, bool F8>
-MM_DEV void load_tile(Stage<NV, F8>& st, const unsigned char* base, const float* sbase, int64_t ld, int64_t ld_sc, int row0, int end, int d, int tid) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int v = tid + i * NT, row = v / (DP / 8), c = v % (DP / 8);
-        const bool on = v < Geo<DP>::V64 && c * 8 < d;
-        const int rr = min(row0 + row, end - 1);
-        if constexpr (F8) {
-            st.r[i] = on ? *(const u32x2*)(base + (int64_t)rr * ld + c * 8) : u32x2{0u, 0u};
-            st.s[i] = on ? sbase[(int64_t)rr * ld_sc] : 0.f;
-        } else {
-            st.r[i] = on ? *(const u32x4*)(base + (int64_t)rr * ld + c * 16) : u32x4{0u, 0u, 0u, 0u};
-        }
-    }
-}
-template <int DP, int NV, bool F8>
-MM_DEV void store_tile(const Stage<NV, F8>& st, unsigned char* s, int tid) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int v = tid + i * NT, row = v / (DP / 8), c = v % (DP / 8);
-        if (v >= Geo<DP>::V64) continue;
-        u32x4 w;
-        if constexpr (F8) {                                  // e4m3 -> fp32 is exact, times a power of two is exact and a bf16 value
-            const mm_f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)st.r[i].x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)st.r[i].x, true);
-            const mm_f32x2 e = __builtin_amdgcn_cvt_pk_f32_fp8((int)st.r[i].y, false), f = __builtin_amdgcn_cvt_pk_f32_fp8((int)st.r[i].y, true);
-            const float sc = st.s[i];
-            w.x = pack2bf(a.x * sc, a.y * sc); w.y = pack2bf(b.x * sc, b.y * sc);
-            w.z = pack2bf(e.x * sc, e.y * sc); w.w = pack2bf(f.x * sc, f.y * sc);
-        } else {
-            w = st.r[i];
-        }
-        *(u32x4*)(s + offN<Geo<DP>::DS>(row, c)) = w;
-    }
-}
-
 template <int DP, bool F8>
 __global__ __launch_bounds__(NT) void extend_kernel(XArgs a) {
     using G_ = Geo<DP>;
-    constexpr int DS = G_::DS, KS = G_::KS, NF = G_::NF;
+    constexpr int KS = G_::KS, NF = G_::NF;
     constexpr int NV = (G_::V64 + NT - 1) / NT;
     constexpr int EPI = 4 * 16 * DP * 2;                    // bf16 output staging
     constexpr int SMEM = 2 * G_::T64 > EPI ? 2 * G_::T64 : EPI;
@@ -145,7 +106,6 @@ __global__ __launch_bounds__(NT) void extend_kernel(XArgs a) {
         store_tile<DP, NV, F8>(rk, sK, tid);
         store_tile<DP, NV, F8>(rv, sV, tid);
         __syncthreads();
-        constexpr float RESCALE_THR = 6.0f;                  // log2 units: keep the old running max while it grows < 2^6
         for (int t = t0; t < t1; ++t) {
             const int kv0 = t * 64;
             const bool more = t + 1 < t1;
@@ -153,65 +113,8 @@ __global__ __launch_bounds__(NT) void extend_kernel(XArgs a) {
                 load_tile<DP, NV, F8>(rk, kbase, ksb, a.ld_kv, a.ld_sc, kv0 + 64, kv_end, d, tid);
                 load_tile<DP, NV, F8>(rv, vbase, vsb, a.ld_kv, a.ld_sc, kv0 + 64, kv_end, d, tid);
             }
-            if (wave_on && kv0 <= wave_hi) {                 // a wave whose rows all precede this tile has nothing to do here
-                f32x4 st[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) st[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int kk = 0; kk < KS; ++kk) {
-                        const bf16x8 kf = *(const bf16x8*)(sK + offN<DS>(j * 16 + fr, kk * 4 + fq));
-                        st[j] = mfma16(kf, qf[kk], st[j]);
-                    }
-                if (kv0 + 63 > wave_lo) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            if (kv0 + j * 16 + fq * 4 + r > klim) st[j][r] = -INFINITY;
-                }
-                float mx = -INFINITY;                         // max of the RAW scores (scale > 0 commutes with max)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) mx = fmaxf(mx, st[j][r]);
-                mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-                mx *= sl2;
-                // deferred rescale: move the running max (and touch the O accumulators) only when some row's max grew by more than 2^THR
-                const bool grow = mx > m_run + RESCALE_THR || m_run == -INFINITY;
-                if (__any(grow && mx > -INFINITY)) {
-                    const float mn = fmaxf(m_run, mx);
-                    const float alpha = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m_run - mn);
-                    l_run *= alpha;
-#pragma unroll
-                    for (int j = 0; j < NF; ++j) ot[j] *= alpha;
-                    m_run = mn;
-                }
-                const float mref = m_run;
-                float rs = 0.f;
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float p = (mref == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(fmaf(st[j][r], sl2, -mref));
-                        st[j][r] = p;
-                        rs += p;
-                    }
-                rs += __shfl_xor(rs, 16, 64);
-                rs += __shfl_xor(rs, 32, 64);
-                l_run += rs;
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
-                    const bf16x8 pb = pack_acc(st[2 * kk], st[2 * kk + 1]);
-#pragma unroll
-                    for (int j = 0; j < NF; ++j) {
-                        const bf16x8 va = read_nat_perm<DS>(sV, kk * 32, j, fr, fq);      // V^T[d][keys perm]
-                        ot[j] = mfma16(va, pb, ot[j]);
-                    }
-                }
-            }
+            if (wave_on && kv0 <= wave_hi)                   // a wave whose rows all precede this tile has nothing to do here
+                softmax_tile<DP>(sK, sV, qf, ot, m_run, l_run, kv0, kv0 + 63 > wave_lo, klim, sl2, fr, fq);
             __syncthreads();                                 // every wave is done reading this tile
             if (more) {
                 store_tile<DP, NV, F8>(rk, sK, tid);
@@ -264,23 +167,8 @@ __global__ __launch_bounds__(NT) void extend_merge_kernel(XArgs a) {
     if (p >= a.R || c >= a.d) return;
     const int64_t row0 = ((int64_t)b * a.Hkv + hk) * a.nsplit * a.rpad + p;
     const float* ml = a.ws + (int64_t)gridDim.z * a.Hkv * a.nsplit * a.rpad * DP;
-    float M = -INFINITY;
-    for (int s = 0; s < a.nsplit; ++s) M = fmaxf(M, ml[(row0 + s * a.rpad) * 2]);
-    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-    float l = 0.f;
-    for (int s = 0; s < a.nsplit; ++s) {
-        const int64_t row = row0 + s * a.rpad;
-        const float m = ml[row * 2];
-        if (m == -INFINITY) continue;
-        const float w = __builtin_amdgcn_exp2f(m - M);
-        l += w * ml[row * 2 + 1];
-        acc += w * *(const f32x4*)(a.ws + row * DP + c);
-    }
-    const float inv = l > 0.f ? 1.0f / l : 0.f;
+    const u32x2 w = merge_partials<DP>(a.ws, ml, row0, a.rpad, a.nsplit, c);
     const int i = p / a.G, g = p - i * a.G;
-    u32x2 w;
-    w.x = pack2bf(acc[0] * inv, acc[1] * inv);
-    w.y = pack2bf(acc[2] * inv, acc[3] * inv);
     *(u32x2*)(a.o + ((int64_t)b * a.n + i) * a.ld_o + (int64_t)(hk * a.G + g) * a.d + c) = w;
 }
 

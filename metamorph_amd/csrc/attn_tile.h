@@ -1,0 +1,137 @@
+// What attn_extend.hip and attn_decode_shared.hip share on top of attn2.h: the K / V tile mover (bf16 and e4m3 cache), one 64-key step of the
+// "swapped" online softmax (S^T = K Q^T, O^T += V^T P^T, log2 domain, deferred rescale) and the fold of per-key-run partials.
+#pragma once
+#include "attn2.h"
+
+namespace attn_tile {
+using namespace attn2;
+
+template <int NV, bool F8> struct Stage;
+template <int NV> struct Stage<NV, false> { u32x4 r[NV]; };
+template <int NV> struct Stage<NV, true> { u32x2 r[NV]; float s[NV]; };
+
+// rows [row0, row0 + 64) of one KV head -> registers; rows past `end` repeat row end - 1 (masked by the caller), columns >= d are zero
+template <int DP, int NV, bool F8>
+MM_DEV void load_tile(Stage<NV, F8>& st, const unsigned char* base, const float* sbase, int64_t ld, int64_t ld_sc, int row0, int end, int d, int tid) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int v = tid + i * NT, row = v / (DP / 8), c = v % (DP / 8);
+        const bool on = v < Geo<DP>::V64 && c * 8 < d;
+        const int rr = min(row0 + row, end - 1);
+        if constexpr (F8) {
+            st.r[i] = on ? *(const u32x2*)(base + (int64_t)rr * ld + c * 8) : u32x2{0u, 0u};
+            st.s[i] = on ? sbase[(int64_t)rr * ld_sc] : 0.f;
+        } else {
+            st.r[i] = on ? *(const u32x4*)(base + (int64_t)rr * ld + c * 16) : u32x4{0u, 0u, 0u, 0u};
+        }
+    }
+}
+template <int DP, int NV, bool F8>
+MM_DEV void store_tile(const Stage<NV, F8>& st, unsigned char* s, int tid) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int v = tid + i * NT, row = v / (DP / 8), c = v % (DP / 8);
+        if (v >= Geo<DP>::V64) continue;
+        u32x4 w;
+        if constexpr (F8) {                                  // e4m3 -> fp32 is exact, times a power of two is exact and a bf16 value
+            const mm_f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)st.r[i].x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)st.r[i].x, true);
+            const mm_f32x2 e = __builtin_amdgcn_cvt_pk_f32_fp8((int)st.r[i].y, false), f = __builtin_amdgcn_cvt_pk_f32_fp8((int)st.r[i].y, true);
+            const float sc = st.s[i];
+            w.x = pack2bf(a.x * sc, a.y * sc); w.y = pack2bf(b.x * sc, b.y * sc);
+            w.z = pack2bf(e.x * sc, e.y * sc); w.w = pack2bf(f.x * sc, f.y * sc);
+        } else {
+            w = st.r[i];
+        }
+        *(u32x4*)(s + offN<Geo<DP>::DS>(row, c)) = w;
+    }
+}
+
+// One wave, 16 packed rows (lane's row = fr), the 64 keys [kv0, kv0 + 64) in sK / sV: scores, mask (key > klim of the lane's row, looked at
+// only when `ragged`), running maximum m_run (log2 domain) with deferred rescale, sum l_run, O^T accumulators ot.
+template <int DP>
+MM_DEV void softmax_tile(const unsigned char* sK, const unsigned char* sV, const bf16x8 (&qf)[Geo<DP>::KS], f32x4 (&ot)[Geo<DP>::NF], float& m_run,
+                         float& l_run, int kv0, bool ragged, int klim, float sl2, int fr, int fq) {
+    constexpr int DS = Geo<DP>::DS, KS = Geo<DP>::KS, NF = Geo<DP>::NF;
+    constexpr float RESCALE_THR = 6.0f;                      // log2 units: keep the old running max while it grows < 2^6
+    f32x4 st[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) st[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int kk = 0; kk < KS; ++kk) {
+            const bf16x8 kf = *(const bf16x8*)(sK + offN<DS>(j * 16 + fr, kk * 4 + fq));
+            st[j] = mfma16(kf, qf[kk], st[j]);
+        }
+    if (ragged) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (kv0 + j * 16 + fq * 4 + r > klim) st[j][r] = -INFINITY;
+    }
+    float mx = -INFINITY;                                    // max of the RAW scores (scale > 0 commutes with max)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mx = fmaxf(mx, st[j][r]);
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    mx *= sl2;
+    // deferred rescale: move the running max (and touch the O accumulators) only when some row's max grew by more than 2^THR
+    const bool grow = mx > m_run + RESCALE_THR || m_run == -INFINITY;
+    if (__any(grow && mx > -INFINITY)) {
+        const float mn = fmaxf(m_run, mx);
+        const float alpha = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m_run - mn);
+        l_run *= alpha;
+#pragma unroll
+        for (int j = 0; j < NF; ++j) ot[j] *= alpha;
+        m_run = mn;
+    }
+    const float mref = m_run;
+    float rs = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float p = (mref == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(fmaf(st[j][r], sl2, -mref));
+            st[j][r] = p;
+            rs += p;
+        }
+    rs += __shfl_xor(rs, 16, 64);
+    rs += __shfl_xor(rs, 32, 64);
+    l_run += rs;
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+        const bf16x8 pb = pack_acc(st[2 * kk], st[2 * kk + 1]);
+#pragma unroll
+        for (int j = 0; j < NF; ++j) {
+            const bf16x8 va = read_nat_perm<DS>(sV, kk * 32, j, fr, fq);      // V^T[d][keys perm]
+            ot[j] = mfma16(va, pb, ot[j]);
+        }
+    }
+}
+
+// sum_s 2^(m_s - M) O_s / sum_s 2^(m_s - M) l_s over the `nslots` partials of one packed row, columns [c, c + 4): partial s has its O at
+// po + (row0 + s * stride) * DP and its (m, l) at ml + (row0 + s * stride) * 2; a partial that saw no key has m = -inf
+template <int DP>
+MM_DEV u32x2 merge_partials(const float* po, const float* ml, int64_t row0, int64_t stride, int nslots, int c) {
+    float M = -INFINITY;
+    for (int s = 0; s < nslots; ++s) M = fmaxf(M, ml[(row0 + s * stride) * 2]);
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    float l = 0.f;
+    for (int s = 0; s < nslots; ++s) {
+        const int64_t row = row0 + s * stride;
+        const float m = ml[row * 2];
+        if (m == -INFINITY) continue;
+        const float w = __builtin_amdgcn_exp2f(m - M);
+        l += w * ml[row * 2 + 1];
+        acc += w * *(const f32x4*)(po + row * DP + c);
+    }
+    const float inv = l > 0.f ? 1.0f / l : 0.f;
+    u32x2 w;
+    w.x = pack2bf(acc[0] * inv, acc[1] * inv);
+    w.y = pack2bf(acc[2] * inv, acc[3] * inv);
+    return w;
+}
+}  // namespace attn_tile

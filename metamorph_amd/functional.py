@@ -50,7 +50,11 @@ VARIANTS = {"fuse_swiglu": True, "fuse_rope": True, "fuse_swiglu_bwd": True, "de
             # split-K stream over the weights is 0.81 - 1.46 x two GEMV steps, profiles/extend_pass.md)
             "extend_pass": True, "extend_min_rows": 3,
             # greedy_decode of ONE sequence through the device-resident loop that batches take (GreedyLoopGraph) instead of the host loop
-            "greedy_loop_b1": False}
+            "greedy_loop_b1": False,
+            # n continuations of one prompt (greedy_decode(num_return_sequences=n)): the prompt's cache rows stored once in sequence 0 and read
+            # once per KV head and step by mm355_attn_decode_shared (KVCache.set_shared); off, or where that kernel does not take the shape:
+            # the rows are copied into every sequence's block and the step runs on mm355_attn_decode.  The prompt runs once either way.
+            "shared_prefix_attn": True}
 
 
 def set_variant(name, value):
@@ -778,6 +782,9 @@ class KVCache:
         self.lengths = [0] * batch                                               # host mirror of pos_dev
         self.pos_dev = torch.zeros(batch, device=device, dtype=torch.int32)      # row the next token of sequence b is written to
         self.len_dev = torch.ones(batch, device=device, dtype=torch.int32)       # = pos + 1: rows visible to that token
+        self.Hq, self.d = Hq, d
+        self.shared_len = 0                                                      # > 0: rows [0, shared_len) of sequence 0 are every sequence's first rows
+        self.shared_ws = None
         self.ws = None
         if Hq is not None:                                                       # (sized for the whole batch: beyond 16 rows one attention launch serves all of them)
             self.ws = torch.zeros(int(ops._L().mm355_attn_decode_ws_floats(batch, Hq, d, max_len)), device=device,
@@ -787,6 +794,36 @@ class KVCache:
     def kv8(self):
         """(k_scale, v_scale) of an fp8_e4m3 cache, None for a bf16 one"""
         return None if self.k_scale is None else (self.k_scale, self.v_scale)
+
+    @property
+    def shared(self):
+        """(shared_len, workspace of mm355_attn_decode_shared) while the first rows are shared, else None"""
+        return (self.shared_len, self.shared_ws) if self.shared_len > 0 else None
+
+    def set_shared(self, n):
+        """Declare rows [0, n) of sequence 0 the first n rows of EVERY sequence (n continuations of one prompt: the prompt's rows are stored
+        and read once; rows [0, n) of the other sequences' blocks are never read again).  Every sequence must hold at least n rows
+        (set_lengths first); n = 0 ends the sharing.  The decode step then attends through mm355_attn_decode_shared."""
+        n = int(n)
+        if n < 0 or n > min(self.lengths):
+            raise ValueError(f"shared prefix of {n} rows on sequences of {self.lengths} rows: every sequence must hold the shared rows")
+        if n > 0:
+            if self.Hq is None or self.d is None:
+                raise ValueError("a shared prefix needs a cache built with Hq and d (they size the attention workspace)")
+            Hkv = self.k.shape[-1] // self.d
+            n_ws = int(ops._L().mm355_attn_decode_shared_ws_floats(self.batch, self.Hq, Hkv, self.d, n, self.max_len))
+            if n_ws <= 0:
+                raise ValueError(f"mm355_attn_decode_shared has no workspace for batch={self.batch} Hq={self.Hq} Hkv={Hkv} d={self.d}")
+            self.shared_ws = torch.empty(n_ws, device=self.k.device, dtype=torch.float32)
+        else:
+            self.shared_ws = None
+        self.shared_len = n
+
+    def copy_prefix(self, n):
+        """rows [0, n) of sequence 0 (scales included) into every other sequence's block: the fan-out of one prompt to the batch"""
+        for t in (self.k, self.v, self.k_scale, self.v_scale):
+            if t is not None and self.batch > 1:
+                t[:, 1:, :n].copy_(t[:, :1, :n].expand(-1, self.batch - 1, -1, -1))
 
     def nbytes(self):
         """bytes of the cached rows (and their scales)"""
@@ -941,6 +978,9 @@ def decoder_extend(x, layers, meta, cache, row=0):
     where _prefill_layers_fused does not apply (more than 4096 rows, q|k|v not split, d % 16 != 0) the plain decoder_layer_forward route
     with mm355_rope_qk_pos and a row copy into the cache."""
     n, h = x.shape
+    if cache.shared_len > 0:
+        raise ValueError(f"decoder_extend on a cache with a shared prefix of {cache.shared_len} rows: sequences 1.. do not hold the prefix "
+                         "(only sequence 0 stores it), so their rows cannot be extended in place")
     past = int(cache.lengths[row])
     if past < 1:
         raise ValueError(f"decoder_extend needs a filled cache, sequence {row} holds no rows: the first rows of a sequence go through decoder_prefill")
@@ -1212,12 +1252,27 @@ def _proj(on8, rec, name, weights, w8_op, bf16_op, x, *args, **kw):
     return bf16_op(x, weights[0] if len(weights) == 1 else fused_weight(weights), *args, **kw)
 
 
-def _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound):
+def _attend_decode(q, i, meta, k, v, kv8, len_dev, ws, kv_bound, shared=None):
+    """Attention of the step's new rows (one per sequence, already appended) over layer i of the cache: every sequence over its own rows
+    (mm355_attn_decode / _f8), or, on a cache whose first rows are shared (KVCache.shared: (shared_len, workspace)), over rows [0,
+    shared_len) of sequence 0 and then its own rows (mm355_attn_decode_shared / _f8)."""
+    H = (meta.Hq, meta.Hkv, meta.d, meta.scale)
+    if shared is not None:
+        P, sws = shared
+        if kv8 is not None:
+            return ops.attn_decode_shared_f8(q, k[i, 0], v[i, 0], kv8[0][i, 0], kv8[1][i, 0], k[i], v[i], kv8[0][i], kv8[1][i], len_dev, P,
+                                             kv_bound, *H, workspace=sws)
+        return ops.attn_decode_shared(q, k[i, 0], v[i, 0], k[i], v[i], len_dev, P, kv_bound, *H, workspace=sws)
+    if kv8 is not None:
+        return ops.attn_decode_f8(q, k[i], v[i], kv8[0][i], kv8[1][i], len_dev, kv_bound, *H, workspace=ws)
+    return ops.attn_decode(q, k[i], v[i], len_dev, kv_bound, *H, workspace=ws)
+
+
+def _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound, shared=None):
     """The new q|k|v rows against layer i of an fp8_e4m3 cache (k / v: the bytes, kv8: the scales): RoPE + quantising append, then attention
     over the bytes -- the row just appended included.  Two launches; the projection in front is the plain one."""
     ops.rope_kv_append_f8_(qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i], kv8[0][i], kv8[1][i])
-    return ops.attn_decode_f8(qkv[:, :meta.Hq * meta.d], k[i], v[i], kv8[0][i], kv8[1][i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d,
-                              meta.scale, workspace=ws)
+    return _attend_decode(qkv[:, :meta.Hq * meta.d], i, meta, k, v, kv8, len_dev, ws, kv_bound, shared)
 
 
 _Rows16 = namedtuple("_Rows16", "gemv gemv_swiglu gemv_rope_append qkv o gu down")
@@ -1233,7 +1288,7 @@ def _bf16_rows16(layer):
                    (fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight]),), (mlp.down_proj.weight,))
 
 
-def _decode_rows16(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound, kv8=None):
+def _decode_rows16(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound, kv8=None, shared=None):
     """<= 16 new rows (one per sequence) through every decoder layer against their cache rows k / v [layers, rows, max_len, width]:
     every weight is streamed ONCE for all rows (mm355_gemv* take M <= 16: up to four rows on the vector ALU, 5 .. 16 on MFMA), attention per
     row at its own length.  One launch sequence for every weight format: a quantised layer runs it on its record's own kernels (W8Layer:
@@ -1255,12 +1310,12 @@ def _decode_rows16(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bou
                 # fp8_e4m3 cache: the norm and the plain projection as launches of their own (no fused *_rope_append_f8 form), then the
                 # quantising append and attention over the bytes: seven launches per layer up to the fold limit, eight beyond
                 qkv = rec.gemv(ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps), *rec.qkv)
-                o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound)
+                o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound, shared)
             else:
                 n1 = x if fold else ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
                 qkv = rec.gemv_rope_append(n1, *rec.qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i],
                                            norm_w=layer.input_layernorm.weight if fold else None, eps=meta.eps)
-                o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
+                o = _attend_decode(qkv[:, :nq], i, meta, k, v, None, len_dev, ws, kv_bound, shared)
             x2 = rec.gemv(o, *rec.o, residual=x)
             n2 = x2 if fold else ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
             act = rec.gemv_swiglu(n2, *rec.gu, meta.I, norm_w=layer.post_attention_layernorm.weight if fold else None, eps=meta.eps)
@@ -1269,10 +1324,10 @@ def _decode_rows16(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bou
         n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
         qkv = rec.gemv(n1, *rec.qkv)
         if kv8 is not None:
-            o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound)
+            o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound, shared)
         else:
             ops.rope_kv_append_(qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
-            o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
+            o = _attend_decode(qkv[:, :nq], i, meta, k, v, None, len_dev, ws, kv_bound, shared)
         x2 = rec.gemv(o, *rec.o, residual=x)
         n2 = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
         act = ops.swiglu_fwd(rec.gemv(n2, *rec.gu), meta.I)
@@ -1280,7 +1335,7 @@ def _decode_rows16(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bou
     return x
 
 
-def _decode_rows_gemm(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound, kv8=None):
+def _decode_rows_gemm(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound, kv8=None, shared=None):
     """17 new rows and more (one per sequence) through every decoder layer in ONE pass over the weights (round 6; rounds 5: chunks of 16 rows,
     i.e. the 15 GB read once per chunk).  The GEMV kernels hold one 16-row MFMA operand; beyond it the projections take the split-K GEMM of
     the prompt pass (mm355_gemm_splitk_bf16: 64 x 128 tiles x K slices -- at 32 rows a weight-streaming problem with ~3 workgroups per CU),
@@ -1301,11 +1356,11 @@ def _decode_rows_gemm(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_
                 n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
             if kv8 is not None:                              # fp8_e4m3 cache: the plain split projection, then the quantising append (ten launches per layer)
                 qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), "gemm", ops.gemm_splitk, n1)
-                o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound)
+                o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound, shared)
             else:
                 qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), "gemm_rope_append",
                             ops.gemm_splitk_rope_append, n1, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
-                o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
+                o = _attend_decode(qkv[:, :nq], i, meta, k, v, None, len_dev, ws, kv_bound, shared)
             x2, n2 = _proj(on8, rec, "o", (att.o_proj.weight,), "gemm_norm", ops.gemm_splitk_norm, o,
                            layer.post_attention_layernorm.weight, meta.eps, residual=x)
             if "gu" in on8:
@@ -1331,10 +1386,10 @@ def _decode_rows_gemm(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_
         n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
         qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), "gemm", ops.gemm_splitk, n1)
         if kv8 is not None:
-            o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound)
+            o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound, shared)
         else:
             ops.rope_kv_append_(qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
-            o = ops.attn_decode(qkv[:, :nq], k[i], v[i], len_dev, kv_bound, meta.Hq, meta.Hkv, meta.d, meta.scale, workspace=ws)
+            o = _attend_decode(qkv[:, :nq], i, meta, k, v, None, len_dev, ws, kv_bound, shared)
         x2 = _proj(on8, rec, "o", (att.o_proj.weight,), "gemm", ops.gemm_splitk, o, residual=x)
         n2 = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
         gu = _proj(on8, rec, "gu", (mlp.gate_proj.weight, mlp.up_proj.weight), "gemm", ops.gemm_splitk, n2)
@@ -1370,9 +1425,9 @@ def decoder_decode_row(x, layers, meta, cache, cos, sin, kv_bound=None):
         # the bound is a launch parameter (number of key groups): a sequence longer than it would silently attend to its first `bound` keys
         raise ValueError(f"decode bound {bound} is below the longest sequence + 1 ({cache.length + 1}); lengths change only through set_lengths")
     if B <= 16:
-        y = _decode_rows16(x, layers, meta, cos, sin, cache.k, cache.v, cache.pos_dev, cache.len_dev, cache.ws, bound, cache.kv8)
+        y = _decode_rows16(x, layers, meta, cos, sin, cache.k, cache.v, cache.pos_dev, cache.len_dev, cache.ws, bound, cache.kv8, cache.shared)
     else:
-        y = _decode_rows_gemm(x, layers, meta, cos, sin, cache.k, cache.v, cache.pos_dev, cache.len_dev, cache.ws, bound, cache.kv8)
+        y = _decode_rows_gemm(x, layers, meta, cos, sin, cache.k, cache.v, cache.pos_dev, cache.len_dev, cache.ws, bound, cache.kv8, cache.shared)
     cache.pos_dev.add_(1)
     cache.len_dev.add_(1)
     cache.lengths = [n + 1 for n in cache.lengths]

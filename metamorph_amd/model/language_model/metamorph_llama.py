@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import copy
 import math
+import operator
 import numpy as np
 import torch
 import torch.nn as nn
@@ -549,7 +550,7 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
     def greedy_decode(self, position_ids, attention_mask, inputs_embeds, start_image_token_id=DEFAULT_IMAGE_START_ID,
                       end_image_token_id=DEFAULT_IMAGE_END_ID, eos_token_id=(128001, 128009), do_sample=None,
                       temperature=None, top_p=None, num_beams=None, max_new_tokens=1024, use_cache=None, output_image=False,
-                      top_k=None, seed=None, stream_ids=None):
+                      top_k=None, seed=None, stream_ids=None, num_return_sequences=None):
         """Token mode / continuous 'image mode' greedy loop.  use_cache=False re-runs the prefix every step exactly like
         the reference (which forces use_cache=False, O(L^2)); the default keeps a KV cache and feeds one row per step
         through the decode-shape kernels -- same state machine, same outputs.
@@ -562,7 +563,27 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         rows are emitted as before).  Sequence b draws from the Philox stream (seed, stream_ids[b]) at its own output position, so a
         sequence's ids do not depend on the batch it rides in; seed=None takes 64 bits from torch's CPU generator (torch.manual_seed
         repeats a run), stream_ids defaults to range(B).  Any other do_sample / temperature (None or 0.0, the reference demo's call) is
-        the greedy loop, bit for bit."""
+        the greedy loop, bit for bit.
+        num_return_sequences = n > 1 (one prompt, an active sampler): n continuations of the prompt, returned in the batch shapes (a list
+        of n id tensors, a list of n image-row tensors); continuation b draws from the stream (seed, stream_ids[b]), stream_ids defaults
+        to range(n).  The prompt runs through the decoder ONCE into sequence 0 of a cache of n sequences, and every step reads its rows
+        once for all continuations (mm355_attn_decode_shared; functional.set_variant("shared_prefix_attn", False), or a head shape that
+        kernel does not take: the prompt's cache rows are copied to every sequence and the step is the batch's).  Refused by name: n > 1
+        without an active sampler (n greedy continuations are n copies), with more than one prompt, or with use_cache=False.  None or 1:
+        as without the argument."""
+        copies = self._copies_of(num_return_sequences)
+        if copies > 1:
+            if not (use_cache is None or use_cache):
+                raise ValueError(f"greedy_decode(num_return_sequences={copies}, use_cache=False): the continuations share the prompt's KV "
+                                 "cache rows (use_cache=True)")
+            if inputs_embeds.shape[0] != 1:
+                raise ValueError(f"greedy_decode(num_return_sequences={copies}) takes one prompt, got {inputs_embeds.shape[0]}")
+            sampler = self._sampler_of(do_sample, temperature, top_k, top_p, num_beams, seed, stream_ids, copies)
+            if sampler is None:
+                raise ValueError(f"greedy_decode(num_return_sequences={copies}) needs an active sampler (do_sample=True and temperature > "
+                                 "0): greedy continuations of one prompt are all the same sequence")
+            return self._greedy_decode_loop(inputs_embeds, attention_mask, start_image_token_id, end_image_token_id, eos_token_id,
+                                            max_new_tokens, output_image, sampler=sampler, copies=copies)
         sampler = self._sampler_of(do_sample, temperature, top_k, top_p, num_beams, seed, stream_ids, inputs_embeds.shape[0])
         if sampler is not None and not (use_cache is None or use_cache):
             raise NotImplementedError("greedy_decode(do_sample=True, use_cache=False): sampling runs in the device loop on the KV cache "
@@ -834,6 +855,22 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         return pads
 
     @staticmethod
+    def _copies_of(num_return_sequences):
+        """greedy_decode's num_return_sequences -> the number of continuations per prompt (None: 1); anything but a positive integer is
+        refused by name."""
+        if num_return_sequences is None:
+            return 1
+        try:
+            if isinstance(num_return_sequences, bool):
+                raise TypeError
+            n = operator.index(num_return_sequences)
+        except TypeError:
+            n = 0
+        if n < 1:
+            raise ValueError(f"greedy_decode: num_return_sequences = {num_return_sequences!r} must be a positive integer")
+        return n
+
+    @staticmethod
     def _sampler_of(do_sample, temperature, top_k, top_p, num_beams, seed, stream_ids, B):
         """greedy_decode's sampling arguments -> GreedyLoopGraph's `sampler` tuple, or None for the greedy loop (do_sample falsy, or
         temperature None / 0).  Refuses bad values by name before any device work."""
@@ -866,11 +903,13 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         return (inv_t, int(top_k), top_p, int(seed) & 0xFFFFFFFFFFFFFFFF, stream_ids)
 
     def _greedy_decode_loop(self, inputs_embeds, attention_mask, start_image_token_id, end_image_token_id, eos_token_id, max_new_tokens,
-                            output_image, sampler=None):
+                            output_image, sampler=None, copies=1):
         """greedy_decode of B sequences: the prompt pass of _prefill_batch (same-length prompts as one batch, ragged ones one after the
         other), then functional.GreedyLoopGraph -- one pass over the weights per step for all sequences, head, argmax and the reference's
         mode state machine on the device.  The host reads the live counter every config.mm355_greedy_poll_steps steps (default 8: at most
-        7 wasted steps per call against one synchronisation per 8 tokens; a judgement, tools/bench_greedy_batch.py gives the numbers)."""
+        7 wasted steps per call against one synchronisation per 8 tokens; a judgement, tools/bench_greedy_batch.py gives the numbers).
+        copies > 1 (one prompt): `copies` continuations of it, the prompt pass of _prefill_shared; sampler=None then walks the greedy loop
+        `copies` times over (tests)."""
         if inputs_embeds.dtype != BF16:
             raise TypeError(f"inputs_embeds must be bf16, got {inputs_embeds.dtype}")
         dev = inputs_embeds.device
@@ -880,8 +919,13 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         max_new_tokens = int(max_new_tokens)
         seqs = [inputs_embeds[b, pads[b]:].reshape(n - pads[b], h) for b in range(B)]
         cache = HipKVCache(capacity=max(x.shape[0] for x in seqs) + max_new_tokens + 2)
-        outs = self._prefill_batch(seqs, cache, stepper=False, chunk=self._prefill_chunk_rows())
-        x0 = torch.stack([o[-1] for o in outs], 0)
+        if copies > 1:
+            if B != 1:
+                raise ValueError(f"{copies} continuations take one prompt, got {B}")
+            x0 = self._prefill_shared(seqs[0], cache, copies, chunk=self._prefill_chunk_rows())
+        else:
+            outs = self._prefill_batch(seqs, cache, stepper=False, chunk=self._prefill_chunk_rows())
+            x0 = torch.stack([o[-1] for o in outs], 0)
         embed = self.model.embed_tokens.weight.data
         V = self.w8_lm_head[0].shape[0] if self.w8_lm_head is not None else self.lm_head.weight.shape[0]
         loop = F.GreedyLoopGraph(self.model.layers, cache.meta, cache.kv, cache.meta.cos, cache.meta.sin, h, dev, self._head_rows_device,
@@ -890,7 +934,7 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
                                  poll=getattr(self.config, "mm355_greedy_poll_steps", 8), sampler=sampler)
         self._greedy_loop = loop                              # (tools / tests: steps, host_reads, the static logits of the last step)
         ids, embs = loop.run(x0)
-        if B == 1:                                            # one sequence: the return shapes of _greedy_decode_cached
+        if B == 1 and copies == 1:                            # one sequence: the return shapes of _greedy_decode_cached
             embs = embs[0] if embs[0].shape[0] else torch.tensor([], dtype=torch.float32, device=dev)
         return (ids, embs) if output_image else ids
 
@@ -931,6 +975,37 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         if stepper:
             cache.stepper = F.DecodeStepGraph(self.model.layers, meta, cache.kv, cos, sin, h, dev)
         return out
+
+    def _prefill_shared(self, x2d, cache, n, chunk=None):
+        """Prompt pass of n continuations of ONE prompt x2d [L, h]: the prompt runs once into sequence 0 of a cache of n sequences; returns
+        the prompt's last hidden row (pre final norm) n times, [n, h].  Afterwards every sequence holds L rows and, on the shared route
+        (functional.VARIANTS["shared_prefix_attn"] and a head shape mm355_attn_decode_shared takes), rows [0, L) of sequence 0 are every
+        sequence's first rows (KVCache.set_shared); else they are copied into every sequence's block (KVCache.copy_prefix) and the step
+        runs on the batch's attention."""
+        dev = x2d.device
+        L, h = int(x2d.shape[0]), x2d.shape[1]
+        cap = cache.capacity if cache.capacity is not None else L + 1024 + 2
+        if cap < L + 1:
+            raise ValueError(f"HipKVCache capacity {cap} is smaller than the prompt ({L} rows)")
+        cos, sin = self.model.rope_tables(cap, dev)
+        _, meta = self._decode_meta(L)
+        meta.cos, meta.sin = cos, sin
+        kv = cache.kv = F.KVCache(len(self.model.layers), cap, meta.Hkv * meta.d, dev, Hq=meta.Hq, d=meta.d, batch=n,
+                                  fmt=self._kv_cache_format(cache.kv_format))
+        cache.meta = meta
+        _, mb = self._decode_meta(L)
+        mb.cos, mb.sin = cos, sin
+        if chunk is None:
+            rows = F.decoder_prefill(x2d.contiguous(), self.model.layers, mb, kv, row=0)
+        else:
+            rows = F.decoder_prefill_chunked(x2d.contiguous(), self.model.layers, mb, kv, chunk, row=0)
+        if F.VARIANTS["shared_prefix_attn"] and ops.attn_decode_shared_supported(meta.Hq, meta.Hkv, meta.d):
+            kv.set_lengths([L] * n)
+            kv.set_shared(L)
+        else:
+            kv.copy_prefix(L)
+            kv.set_lengths([L] * n)
+        return rows[-1:].expand(n, h).contiguous()
 
     def _decode_batch(self, x, cache):
         """New rows x [B, n, h] (the hook of n = 1: one row per sequence and step) appended against the batch's cache, every position in ONE
