@@ -483,20 +483,22 @@ int mm355_gemm_w4_rope_append(const mm355_bf16* x, int64_t ldx, const uint8_t* W
                               void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Cached decode over an FP8 KV cache (csrc/decode_kv8.hip).  fmt MM355_KV8_E4M3: one cached head-row -- the d post-RoPE bf16 values of one
- * KV head of one token -- is d OCP e4m3fn bytes plus ONE fp32 scale: scale = the smallest power of two with amax / scale <= 448 (a row of
- * zeros: 1), q[c] = RNE_e4m3(x[c] / scale) (exact shift, nothing saturates, subnormals rounded, -0 kept; non-finite inputs are outside the
- * contract).  fp32(q[c]) * scale is exact and a bf16 value, so every reader equals the bf16 kernels on the dequantised rows bit for bit.
+ * Cached decode over an FP8 KV cache (writing it: csrc/decode_kv8.hip; attention over it: csrc/attn_decode.hip).  fmt MM355_KV8_E4M3: one
+ * cached head-row -- the d post-RoPE bf16 values of one KV head of one token -- is d OCP e4m3fn bytes plus ONE fp32 scale: scale = the
+ * smallest power of two with amax / scale <= 448 (a row of zeros: 1), q[c] = RNE_e4m3(x[c] / scale) (exact shift, nothing saturates,
+ * subnormals rounded, -0 kept; non-finite inputs are outside the contract).  fp32(q[c]) * scale is exact and a bf16 value, so every
+ * reader equals the bf16 kernels on the dequantised rows bit for bit.
  * Bytes: [.., rows, Hkv * d] with row stride ld_*_bytes; scales: [.., rows, Hkv] fp32 with row stride ld_scale (floats); the batch strides
  * separate the sequences.
  *   kv_quant_f8: n_rows already-rotated bf16 rows src[r][Hkv * d] (row stride ld_src elements: e.g. the k columns of a fused q|k|v
  *         activation) -> cache row row0 + r % rows_per_seq of sequence r / rows_per_seq.  One head-row per 16-lane group.
  *   rope_kv_append_f8: the twin of mm355_rope_kv_append (device positions, graph-replayable): q rotated in place with the same bits, the
  *         rotated k rounded to bf16 as that kernel stores it and then quantised, v quantised; bytes and scales into cache row positions[b].
- *   attn_decode_f8(_variant): the twin of mm355_attn_decode(_variant), variants 0 and 2: s_j = k_scale[j] * sum_c fp32(K8[j][c]) *
- *         (fp32(q[c]) * scale), o[c] = sum_j (p_j * v_scale[j]) * fp32(V8[j][c]) / l -- each scale once per key, the sums in the order of
- *         the bf16 kernel (8 consecutive columns per lane, now one 8-byte load), the same workspace (mm355_attn_decode_ws_floats), the same
- *         max_kv_len launch parameter and counter reset.  Equal to mm355_attn_decode on the dequantised cache, barring fp32 underflow.
+ *   attn_decode_f8(_variant): the kernel of mm355_attn_decode(_variant) instantiated for e4m3 rows, variants 0 and 2:
+ *         s_j = k_scale[j] * sum_c fp32(K8[j][c]) * (fp32(q[c]) * scale), o[c] = sum_j (p_j * v_scale[j]) * fp32(V8[j][c]) / l -- each
+ *         scale once per key, the sums in the order of the bf16 form (8 consecutive columns per lane, one 8-byte load), the same workspace
+ *         (mm355_attn_decode_ws_floats), the same max_kv_len launch parameter and counter reset.  Equal to mm355_attn_decode on the
+ *         dequantised cache, barring fp32 underflow.
  *   Before any launch: fmt other than MM355_KV8_E4M3, a NULL scale pointer, pointers or strides that are not 8-byte (src / qkv: 16-byte)
  *   aligned: MM355_EINVAL; d % 8 != 0 or d > 128: MM355_EUNSUPPORTED (rope_kv_append_f8 needs d % 16 == 0 as its twin does).
  * ------------------------------------------------------------------------------------------------ */

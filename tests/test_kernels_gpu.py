@@ -1577,6 +1577,67 @@ def test_attn_decode_empty_cache_gives_zero_rows(ops, variant):
     assert float(out[1].float().abs().max()) > 0
 
 
+def test_attn_decode_entry_points_check_their_arguments(ops):
+    """The status codes of mm355_attn_decode_variant and mm355_attn_decode_f8_variant (include/mm355.h: -1 = EINVAL, -2 = EUNSUPPORTED), one
+    argument wrong at a time around a call that is accepted.  The two formats answer a head size they cannot take differently (bf16: -1, e4m3:
+    -2); a GQA group outside {1, 2, 4, 8} is -2 for both and is looked at last."""
+    L = ops._L()
+    st = torch.cuda.current_stream().cuda_stream
+    q = rnd(1, 512, seed=1).to(DEV)
+    kc, vc = rnd(1, 8, 256, seed=2).to(DEV), rnd(1, 8, 256, seed=3).to(DEV)
+    k8, v8 = torch.zeros(1, 8, 256, dtype=torch.uint8, device=DEV), torch.zeros(1, 8, 256, dtype=torch.uint8, device=DEV)
+    ks, vs = torch.ones(1, 8, 2, dtype=torch.float32, device=DEV), torch.ones(1, 8, 2, dtype=torch.float32, device=DEV)
+    kv = torch.ones(1, dtype=torch.int32, device=DEV)
+    o = torch.zeros(1, 512, dtype=torch.bfloat16, device=DEV)
+    ws = torch.zeros(int(L.mm355_attn_decode_ws_floats(1, 4, 128, 8)), dtype=torch.float32, device=DEV)
+    good = dict(q=q.data_ptr(), k=kc.data_ptr(), v=vc.data_ptr(), ld=256, bs=2048, ks=ks.data_ptr(), vs=vs.data_ptr(), ldsc=2, fmt=1, B=1, Hq=2,
+                Hkv=2, d=128, variant=0)
+
+    def bf16(**kw):
+        a = {**good, **kw}
+        return L.mm355_attn_decode_variant(a["q"], 512, a["k"], a["v"], a["ld"], a["bs"], kv.data_ptr(), 8, o.data_ptr(), 512, a["B"], a["Hq"],
+                                           a["Hkv"], a["d"], 0.1, ws.data_ptr(), a["variant"], st)
+
+    def f8(**kw):
+        a = {**good, "k": k8.data_ptr(), "v": v8.data_ptr(), **kw}
+        return L.mm355_attn_decode_f8_variant(a["q"], 512, a["k"], a["v"], a["ld"], a["bs"], a["ks"], a["vs"], a["ldsc"], 16, a["fmt"],
+                                              kv.data_ptr(), 8, o.data_ptr(), 512, a["B"], a["Hq"], a["Hkv"], a["d"], 0.1, ws.data_ptr(),
+                                              a["variant"], st)
+
+    for variant in (0, 1, 2):
+        assert bf16(variant=variant) == 0
+    for variant in (0, 2):
+        assert f8(variant=variant) == 0
+    # the pair that differs: a head size beyond 128 or off the 8-column grid
+    assert bf16(d=136) == -1 and f8(d=136) == -2
+    assert bf16(d=124) == -1 and f8(d=124) == -2
+    assert f8(d=136, ld=260) == -2                                              # (e4m3 looks at d before the strides)
+    # bf16: strides in elements, 16-byte caches, no row-width check
+    assert bf16(ld=252) == -1 and bf16(bs=2052) == -1
+    assert bf16(k=kc.data_ptr() + 8) == -1 and bf16(v=vc.data_ptr() + 8) == -1
+    assert bf16(ld=128) == 0                                                    # ld_kv < Hkv * d is the caller's business (rows overlap, still in the cache)
+    assert bf16(B=65536) == -1 and bf16(Hq=65536, Hkv=65536, d=8) == -1
+    assert bf16(variant=-1) == -1 and bf16(variant=3) == -1
+    # e4m3: format and scales, strides in bytes, 8-byte caches, 4-byte scales, rows and scale rows at least Hkv heads wide
+    assert f8(fmt=7) == -1 and f8(fmt=0) == -1
+    assert f8(ks=0) == -1 and f8(vs=0) == -1
+    assert f8(ld=260) == -1 and f8(bs=2052) == -1
+    assert f8(k=k8.data_ptr() + 4) == -1 and f8(v=v8.data_ptr() + 4) == -1
+    assert f8(ks=ks.data_ptr() + 2) == -1 and f8(vs=vs.data_ptr() + 2) == -1
+    assert f8(ld=248) == -1 and f8(ldsc=1) == -1
+    assert f8(B=65536) == -1 and f8(Hq=65536, Hkv=65536, d=8) == -1
+    assert f8(variant=1) == -1 and f8(variant=-1) == -1 and f8(variant=3) == -1
+    # both: whole GQA groups of 1, 2, 4 or 8 heads; the group size is looked at after everything else
+    for call in (bf16, f8):
+        assert call(Hq=3, Hkv=2) == -1
+        assert call(Hq=3, Hkv=1) == -2 and call(Hq=16, Hkv=1, d=8) == -2
+        assert call(Hq=3, Hkv=1, variant=2) == -2
+        assert call(Hq=3, Hkv=1, variant=3) == -1 and call(Hq=3, Hkv=1, B=65536) == -1
+    assert bf16(Hq=3, Hkv=1, variant=1) == -2
+    assert bf16(Hq=3, Hkv=1, d=136) == -1 and f8(Hq=3, Hkv=1, d=136) == -2
+    torch.cuda.synchronize()
+
+
 # ------------------------------------------------------------------------------------------------ vision
 
 def test_im2col_matches_conv(ops):
