@@ -769,6 +769,46 @@ int mm355_sample_rows_f32(const float* x, int64_t R, int64_t C, float inv_temper
                           int32_t* out, float* stats, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Logits processors and per-token log-probabilities in the same loop (functional.GreedyLoopGraph(processors=...)).  Both kernels run one
+ * workgroup per row of the contiguous fp32 logits x [R, C] (bounds on R and C as for argmax_rows_f32), use no floating-point atomics and
+ * read no host value at run time (they can be captured); a row's result is a bit-reproducible function of that row's inputs, whatever R
+ * and the other rows are.  `seen` is a device bitmap, uint32 [R, seen_words], seen_words >= ceil(C / 32): bit (i & 31) of word (i >> 5)
+ * of row r is id i of sequence r; bits at positions >= C are ignored, whatever they hold.
+ * logits_process_rows_f32: edits x in place, per row in HF's order (RepetitionPenaltyLogitsProcessor, MinNewTokensLengthLogitsProcessor,
+ *         SuppressTokensLogitsProcessor):
+ *           1. every i < C whose bit is set:  x_i = x_i < 0 ? x_i * penalty : x_i / penalty, in fp32 with a correctly rounded division
+ *              (NaN stays NaN, -0.0 stays -0.0, +-inf keep their sign); skipped when penalty == 1 or seen is null
+ *           2. min_new_tokens > 0 and total_out[r] (int32 [R], the loop's state row) < min_new_tokens:  x[e] = -inf for every eos id e
+ *           3. x[s] = -inf for every id s of suppress_ids (int32, DEVICE memory, n_suppress entries, any length)
+ *         Ids outside [0, C) in either list are skipped and never cause a write outside the row; an entry that is neither marked nor
+ *         listed keeps its bits.  eos_ids: HOST memory, n_eos <= MM355_GREEDY_MAX_EOS, as for greedy_advance.  With nothing to edit no
+ *         kernel is launched.  MM355_EINVAL before any launch: x null, R or C out of bounds, penalty not finite or <= 0, penalty != 1
+ *         with a null seen, seen_words < ceil(C / 32) (penalty != 1), min_new_tokens > 0 with a null total_out, n_eos above the cap or
+ *         n_eos > 0 with a null list, n_suppress < 0 or n_suppress > 0 with a null list.  The host model, which the kernel equals bit for
+ *         bit: functional.logits_process_host.
+ * token_note_rows_f32: runs after the pick (tok [R], the id argmax_rows_f32 or sample_rows_f32 wrote) and BEFORE greedy_advance, on the
+ *         state greedy_advance is about to read (in_image, n_img, done, n_tokens: int32 [R] each).  Row r logs an id iff !done[r] and
+ *         !(in_image[r] && n_img[r] < num_image_tokens) and n_tokens[r] < token_cap and 0 <= tok[r] < C -- the rows for which
+ *         greedy_advance writes tok_log[r][n_tokens[r]].  For such a row:
+ *           seen (nullable):      the bit of tok[r] is set (one thread's read-modify-write of one word)
+ *           logp_log (nullable, fp32 [R, token_cap]):  logp_log[r][n_tokens[r]] = x[tok] - m - ln(sum_i exp(x_i - m)), m the row maximum,
+ *                                 -inf entries weigh 0; a NaN in the row, m = +inf or m = -inf (a row of -inf only): NaN; x[tok] = -inf
+ *                                 under a finite m: -inf
+ *         For every other row nothing is written anywhere.  The log-probability is that of the row the kernel finds in x: the PROCESSED
+ *         logits (after logits_process_rows_f32, before temperature, top-k and top-p); with no processor active it is the model's own
+ *         log-softmax.  exp is v_exp_f32 (a few 1e-6 relative), the sum a fixed-order fp32 tree (thread t of 1024 adds the columns
+ *         t, t + 1024, ... in that order, then the wave butterflies and the 16 wave sums in index order): within 1e-4 + 2^-22 |logp| of
+ *         the fp64 value.  MM355_EINVAL: a null x, tok or state row, R or C out of bounds, token_cap outside [0, INT_MAX], seen and
+ *         logp_log both null, seen with seen_words < ceil(C / 32).  The host model: functional.token_note_host.
+ * ------------------------------------------------------------------------------------------------ */
+int mm355_logits_process_rows_f32(float* x, int64_t R, int64_t C, float penalty, const uint32_t* seen, int64_t seen_words,
+                                  const int32_t* total_out, int min_new_tokens, const int32_t* eos_ids, int n_eos,
+                                  const int32_t* suppress_ids, int64_t n_suppress, void* stream);
+int mm355_token_note_rows_f32(const float* x, int64_t R, int64_t C, const int32_t* tok, const int32_t* in_image, const int32_t* n_img,
+                              const int32_t* done, const int32_t* n_tokens, int num_image_tokens, int64_t token_cap, uint32_t* seen,
+                              int64_t seen_words, float* logp_log, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * ZeRO-2 shard update (replaces DeepSpeed zero2.json + HF adamw_torch, train.py:82): AdamW on the
  * rank's fp32 master shard, writes the updated bf16 parameters.  grad_scale_dev (nullable) is a device
  * scalar multiplied into the gradient (1/world, clip coefficient).

@@ -57,21 +57,9 @@ MM_DEV uint64_t shfl_down64(uint64_t v, int o) {
     return ((uint64_t)(uint32_t)__shfl_down((int)(v >> 32), o, 64) << 32) | (uint32_t)__shfl_down((int)v, o, 64);
 }
 
-// f(value, column) over the columns tid, tid + 1024, ... of a row in that order, 16 loads in flight per thread: one workgroup reads the
-// row out of L2, and with one load per trip a pass is 125 dependent L2 latencies long
+// f(value, column) over the columns tid, tid + 1024, ... of a row in that order (argrows.h)
 template <class Fn>
-MM_DEV void for_cols(const float* __restrict__ row, int C, Fn f) {
-    constexpr int U = 16;
-    int c = threadIdx.x;
-    for (; (int64_t)c + (U - 1) * SMP_NT < C; c += U * SMP_NT) {
-        float v[U];
-#pragma unroll
-        for (int j = 0; j < U; ++j) v[j] = row[c + j * SMP_NT];
-#pragma unroll
-        for (int j = 0; j < U; ++j) f(v[j], c + j * SMP_NT);
-    }
-    for (; c < C; c += SMP_NT) f(row[c], c);
-}
+MM_DEV void for_cols(const float* __restrict__ row, int C, Fn f) { row_for_cols<SMP_NT>(row, C, f); }
 
 // Wave 0 over a 256-bin histogram: the highest bin b whose bins b .. 255 together reach `need`, and what is left of `need` inside that bin.
 // frac > 0 (round 0 of the mass select): need = frac * (sum of all bins).  Integers throughout, so the order of the adds cannot matter.

@@ -8,6 +8,7 @@ them) -- the "contiguous_gradients" behaviour of the reference's DeepSpeed ZeRO-
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 import os
 from collections import namedtuple
@@ -1594,6 +1595,89 @@ def sample_row_host(x, inv_t, top_k, top_p, u, eps=0.0, tau=None):
     return [int(c) for c in cand], tau_lo, tau_hi, Z
 
 
+def seen_bits_host(ids, C, words=None):
+    """The bitmap of mm355_logits_process_rows_f32 / mm355_token_note_rows_f32 for one sequence: uint32 [words >= ceil(C / 32)], bit
+    (i & 31) of word (i >> 5) set for every id i of `ids` (each in [0, C))."""
+    import numpy as np
+    bits = np.zeros(ops.seen_words(C) if words is None else int(words), dtype=np.uint32)
+    for i in ids:
+        i = int(i)
+        if not 0 <= i < C:
+            raise ValueError(f"id {i} outside [0, {C})")
+        bits[i >> 5] |= np.uint32(1 << (i & 31))
+    return bits
+
+
+def logits_process_host(row_f32, seen_bits, penalty, total_out, min_new_tokens, eos_ids, suppress_ids):
+    """One row of mm355_logits_process_rows_f32 in numpy.float32: its specification, which the kernel equals bit for bit.  row_f32: the C
+    logits; seen_bits: the sequence's uint32 bitmap (seen_bits_host) or None; total_out: the loop's count of outputs of the sequence.
+    HF's order: every marked i < C becomes x_i * penalty where x_i < 0, x_i / penalty otherwise (skipped for penalty 1 or no bitmap; bits
+    at positions >= C are ignored); then, while total_out < min_new_tokens (> 0), every eos id becomes -inf; then every suppressed id
+    does.  Ids outside [0, C) in either list are skipped.  Returns a new float32 array."""
+    import numpy as np
+    x = np.array(row_f32, dtype=np.float32, copy=True)
+    C = x.shape[0]
+    p = np.float32(penalty)
+    if seen_bits is not None and p != np.float32(1.0):
+        words = np.asarray(seen_bits, dtype=np.uint32)
+        marked = ((words[np.arange(C) >> 5] >> (np.arange(C) & 31).astype(np.uint32)) & np.uint32(1)).astype(bool)
+        with np.errstate(all="ignore"):
+            x[marked] = np.where(x[marked] < 0, x[marked] * p, x[marked] / p)
+    if int(min_new_tokens) > 0 and int(total_out) < int(min_new_tokens):
+        for e in eos_ids:
+            if 0 <= int(e) < C:
+                x[int(e)] = -np.inf
+    for s in ([] if suppress_ids is None else suppress_ids):
+        if 0 <= int(s) < C:
+            x[int(s)] = -np.inf
+    return x
+
+
+def token_note_host(row, tok, done, in_image, n_img, n_tokens, num_image_tokens, token_cap):
+    """One row of mm355_token_note_rows_f32: (logs, logp).  logs: the row logs an id -- not done, no image row (in_image and n_img <
+    num_image_tokens), n_tokens < token_cap and 0 <= tok < C -- which is when greedy_advance_host returns the log "tok".  logp (float64,
+    NaN where tok is no column): row[tok] - m - ln(sum_i exp(row_i - m)) in fp64, m the maximum; a NaN in the row, m = +inf or a row of
+    -inf only give NaN, row[tok] = -inf under a finite m gives -inf.  The kernel's fp32 value is held to it within 1e-4 + 2^-22 |logp|."""
+    import numpy as np
+    x = np.asarray(row, dtype=np.float64)
+    C, tok = x.shape[0], int(tok)
+    logs = (not done) and not (in_image and n_img < num_image_tokens) and 0 <= n_tokens < token_cap and 0 <= tok < C
+    if not 0 <= tok < C:
+        return logs, float("nan")
+    m = float("nan") if np.isnan(x).any() else float(x.max())
+    if not math.isfinite(m):
+        return logs, float("nan")
+    with np.errstate(all="ignore"):
+        return logs, float(x[tok] - m - math.log(math.fsum(np.exp(x - m))))
+
+
+@dataclasses.dataclass
+class LogitsProcessors:
+    """What GreedyLoopGraph(processors=...) applies to the logits between the head and the pick, and what it notes after the pick.
+    repetition_penalty (1: off), min_new_tokens (0: off; counts the loop's total_out, so image rows count) and suppress_ids (an int32
+    DEVICE tensor, or None: off) are the arguments of mm355_logits_process_rows_f32; want_logprobs logs the log-probability of every
+    emitted id (of the processed row, before temperature / top-k / top-p: mm355_token_note_rows_f32); marks: ids marked as seen before
+    the first step -- one list for every sequence or one list per sequence (None: a sequence's bitmap starts empty, HF's behaviour when
+    it is handed inputs_embeds)."""
+    repetition_penalty: float = 1.0
+    min_new_tokens: int = 0
+    suppress_ids: object = None
+    want_logprobs: bool = False
+    marks: object = None
+
+    @property
+    def penalised(self):
+        return float(self.repetition_penalty) != 1.0
+
+    @property
+    def edits(self):
+        return self.penalised or int(self.min_new_tokens) > 0 or (self.suppress_ids is not None and self.suppress_ids.numel() > 0)
+
+    @property
+    def active(self):
+        return self.edits or bool(self.want_logprobs)
+
+
 class GreedyLoopGraph:
     """The greedy text-and-image loop (reference metamorph_llama.py:502-597) of a batch with the token loop on the device.  One step is
     decoder_decode_row (all rows, whatever route the batch size takes) -> `head` (the model's final norm, image head for ALL rows, row select
@@ -1608,10 +1692,17 @@ class GreedyLoopGraph:
     sampler = (inv_temperature, top_k, top_p, seed, stream_ids): the id is drawn instead of taken as the argmax -- mm355_philox_uniform_rows
     (seed, stream_ids[b], the sequence's total_out) -> mm355_sample_rows_f32 (sample_row_host) in place of the argmax, everything else as
     it is.  The uniforms are stateless, so the warm-up launch and the capture consume no draw and a sequence's draws depend on (seed, its
-    stream id, its total_out) only; an image row ignores the id as before, its draw is unused.  `seed` records the seed."""
+    stream id, its total_out) only; an image row ignores the id as before, its draw is unused.  `seed` records the seed.
+    processors = a LogitsProcessors with anything active: the tail becomes head -> mm355_logits_process_rows_f32 (only where a processor
+    edits: penalty, min_new_tokens, suppress_ids) -> the pick as above, on the processed row -> mm355_token_note_rows_f32 (only where the
+    penalty needs the ids marked or the log-probabilities are wanted) -> mm355_greedy_advance, all inside the same captured graph (and in
+    the first, uncaptured tail).  `seen` [B, seen_words(C)] holds the bitmap of the ids each sequence has logged (int32 storage of the
+    uint32 words, ~16 KB per sequence at 128 256 logits), `logp_log` [B, cap] fp32 the log-probability of every logged id under the
+    PROCESSED logits (before temperature, top-k and top-p; with no processor editing, the model's own log-softmax); run() then returns them
+    as a third list.  processors None (or nothing active in it): none of this is allocated or launched."""
 
     def __init__(self, layers, meta, cache, cos, sin, h, device, head, embed, C, Dz, start_id, end_id, num_image_tokens, max_new_tokens,
-                 eos_ids, poll=8, sampler=None):
+                 eos_ids, poll=8, sampler=None, processors=None):
         if len(eos_ids) > ops.GREEDY_MAX_EOS:
             raise ValueError(f"{len(eos_ids)} eos ids: the device loop takes up to {ops.GREEDY_MAX_EOS}")
         if C > embed.shape[0]:
@@ -1643,18 +1734,55 @@ class GreedyLoopGraph:
             self.smp_ws = ops.sample_rows_ws(B, self.C, device)
         self.tok_log = torch.zeros((B, cap), device=device, dtype=torch.int32)
         self.z_log = torch.zeros((B, cap, Dz), device=device, dtype=BF16)
+        self.processors = processors if processors is not None and processors.active else None
+        if self.processors is not None:
+            self._init_processors(B, cap, device)
         self.graphs = {}                                     # kv bound -> graph
         self.capture_ok = VARIANTS["decode_graph"]
         self.host_reads = 0
         self.steps = 0
 
+    def _init_processors(self, B, cap, device):
+        p = self.processors
+        penalty, min_new = float(p.repetition_penalty), int(p.min_new_tokens)
+        if not (math.isfinite(penalty) and penalty > 0):
+            raise ValueError(f"repetition_penalty = {penalty} must be finite and > 0 (1: off)")
+        if min_new < 0:
+            raise ValueError(f"min_new_tokens = {min_new} must be >= 0 (0: off)")
+        sup = p.suppress_ids
+        if sup is not None and (sup.dtype != torch.int32 or sup.dim() != 1 or not sup.is_cuda):
+            raise ValueError("suppress_ids: a 1-D int32 device tensor")
+        if p.marks is not None and not p.penalised:
+            raise ValueError("initial marks without an active repetition penalty: nothing would read them")
+        self._process = (penalty, min_new, sup.contiguous() if sup is not None and sup.numel() else None) if p.edits else None
+        if p.penalised:
+            words = ops.seen_words(self.C)
+            bits = np.zeros((B, words), dtype=np.uint32)
+            if p.marks is not None:
+                marks = list(p.marks)
+                per_row = marks if marks and isinstance(marks[0], (list, tuple)) else [marks] * B
+                if len(per_row) != B:
+                    raise ValueError(f"{len(per_row)} lists of marked ids for {B} sequences")
+                for b in range(B):
+                    bits[b] = seen_bits_host(per_row[b], self.C, words)
+            self.seen = torch.from_numpy(bits.view(np.int32)).to(device)
+        if p.want_logprobs:
+            self.logp_log = torch.zeros((B, cap), device=device, dtype=torch.float32)
+
     def _tail(self, x):
         fed, pred_z = self.head(x, self.state[0], self.logits)
+        p = self.processors
+        if p is not None and self._process is not None:
+            penalty, min_new, sup = self._process
+            ops.logits_process_rows(self.logits, penalty, self.seen if p.penalised else None, self.state[2], min_new, self.scalars[4], sup)
         if self.sampler is None:
             ops.argmax_rows(self.logits, out=self.tok, ws=self.arg_ws)
         else:
             ops.philox_uniform_rows(self.seed, self.stream_ids, self.state[2], out=self.u)
             ops.sample_rows(self.logits, *self.sampler, self.u, out=self.tok, ws=self.smp_ws)
+        if p is not None and (p.penalised or p.want_logprobs):
+            ops.token_note_rows(self.logits, self.tok, self.state, self.scalars[2], self.tok_log.shape[1],
+                                seen=self.seen if p.penalised else None, logp_log=self.logp_log if p.want_logprobs else None)
         ops.greedy_advance(self.tok, self.C, self.state, self.live, self.embed, fed, pred_z, self.x_in, self.tok_log, self.z_log,
                            *self.scalars)
 
@@ -1701,7 +1829,7 @@ class GreedyLoopGraph:
     def run(self, x0):
         """x0 [B, h]: the prompt pass's last hidden row of every sequence (pre final norm).  The first iteration's head and advance run on
         it without a decoder step; then up to max_new_tokens steps.  Returns (ids, pred_z): per sequence its int32 ids and its [n_b, Dz]
-        bf16 image rows."""
+        bf16 image rows; with processors.want_logprobs (ids, pred_z, logprobs): per sequence the fp32 log-probabilities of its ids."""
         self._tail(x0.contiguous())
         for s in range(self.max_new_tokens):
             self._step()
@@ -1715,7 +1843,10 @@ class GreedyLoopGraph:
         if not bool(st[3].all()):                               # pragma: no cover - max_new_tokens steps finish every sequence by construction
             raise RuntimeError(f"greedy loop: sequences still live after {self.steps} steps (state {st.tolist()})")
         n_tok, n_z = st[4].tolist(), st[5].tolist()
-        return ([self.tok_log[b, :n_tok[b]].clone() for b in range(len(n_tok))], [self.z_log[b, :n_z[b]].clone() for b in range(len(n_z))])
+        out = ([self.tok_log[b, :n_tok[b]].clone() for b in range(len(n_tok))], [self.z_log[b, :n_z[b]].clone() for b in range(len(n_z))])
+        if self.processors is not None and self.processors.want_logprobs:
+            out += ([self.logp_log[b, :n_tok[b]].clone() for b in range(len(n_tok))],)
+        return out
 
 
 class GeluFn(Function):

@@ -550,7 +550,8 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
     def greedy_decode(self, position_ids, attention_mask, inputs_embeds, start_image_token_id=DEFAULT_IMAGE_START_ID,
                       end_image_token_id=DEFAULT_IMAGE_END_ID, eos_token_id=(128001, 128009), do_sample=None,
                       temperature=None, top_p=None, num_beams=None, max_new_tokens=1024, use_cache=None, output_image=False,
-                      top_k=None, seed=None, stream_ids=None, num_return_sequences=None):
+                      top_k=None, seed=None, stream_ids=None, num_return_sequences=None, repetition_penalty=None, min_new_tokens=None,
+                      suppress_tokens=None, output_logprobs=False, repetition_penalty_ids=None):
         """Token mode / continuous 'image mode' greedy loop.  use_cache=False re-runs the prefix every step exactly like
         the reference (which forces use_cache=False, O(L^2)); the default keeps a KV cache and feeds one row per step
         through the decode-shape kernels -- same state machine, same outputs.
@@ -570,8 +571,29 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         once for all continuations (mm355_attn_decode_shared; functional.set_variant("shared_prefix_attn", False), or a head shape that
         kernel does not take: the prompt's cache rows are copied to every sequence and the step is the batch's).  Refused by name: n > 1
         without an active sampler (n greedy continuations are n copies), with more than one prompt, or with use_cache=False.  None or 1:
-        as without the argument."""
+        as without the argument.
+        Logits processors, applied on the device between the head and the pick in HF's order (mm355_logits_process_rows_f32, inside the
+        captured step; any of them sends one sequence through the device loop as well): repetition_penalty (None / 1: off) divides the
+        positive and multiplies the negative logits of the ids the sequence has GENERATED so far -- what HF does when it is handed
+        inputs_embeds, as generate() hands them; repetition_penalty_ids (one id list, or one list per sequence; one list for all
+        continuations of num_return_sequences) marks ids before the first step for callers who want HF's prompt-included behaviour, and
+        generate() does not pass it.  min_new_tokens (None / 0: off) keeps the eos ids at -inf while the sequence's count of outputs is
+        below it; the count is the loop's total_out, so image rows count as outputs.  suppress_tokens (None / empty: off) keeps its ids
+        at -inf throughout (128256, <im_start>, asks for a text-only answer).  output_logprobs=True also returns, aligned with the ids,
+        the fp32 log-probability of every emitted id under the PROCESSED logits -- after the three processors, before temperature, top-k
+        and top-p; with no processor active the model's own log-softmax (mm355_token_note_rows_f32): (ids, logprobs), or (ids, image rows,
+        logprobs) with output_image=True, `logprobs` a list of fp32 tensors in the batch shapes, also for one sequence.  All of it works
+        with batches, left padding, the sampler and num_return_sequences.  Refused by name before any device work: a penalty that is not
+        finite or <= 0; min_new_tokens negative, non-integer or above max_new_tokens; an id outside [0, vocabulary) in suppress_tokens or
+        repetition_penalty_ids (strip the -200 image sentinel first); repetition_penalty_ids without an active penalty or with the
+        wrong number of lists; any of the options with use_cache=False (NotImplementedError)."""
         copies = self._copies_of(num_return_sequences)
+        V = self.w8_lm_head[0].shape[0] if self.w8_lm_head is not None else self.lm_head.weight.shape[0]
+        processors = self._processors_of(repetition_penalty, min_new_tokens, suppress_tokens, output_logprobs, repetition_penalty_ids,
+                                         max_new_tokens, V, inputs_embeds.shape[0])
+        if processors is not None and not (use_cache is None or use_cache):
+            raise NotImplementedError("greedy_decode(repetition_penalty / min_new_tokens / suppress_tokens / output_logprobs, use_cache=False): "
+                                      "the logits processors run in the device loop on the KV cache (use_cache=True)")
         if copies > 1:
             if not (use_cache is None or use_cache):
                 raise ValueError(f"greedy_decode(num_return_sequences={copies}, use_cache=False): the continuations share the prompt's KV "
@@ -583,15 +605,15 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
                 raise ValueError(f"greedy_decode(num_return_sequences={copies}) needs an active sampler (do_sample=True and temperature > "
                                  "0): greedy continuations of one prompt are all the same sequence")
             return self._greedy_decode_loop(inputs_embeds, attention_mask, start_image_token_id, end_image_token_id, eos_token_id,
-                                            max_new_tokens, output_image, sampler=sampler, copies=copies)
+                                            max_new_tokens, output_image, sampler=sampler, copies=copies, processors=processors)
         sampler = self._sampler_of(do_sample, temperature, top_k, top_p, num_beams, seed, stream_ids, inputs_embeds.shape[0])
         if sampler is not None and not (use_cache is None or use_cache):
             raise NotImplementedError("greedy_decode(do_sample=True, use_cache=False): sampling runs in the device loop on the KV cache "
                                       "(use_cache=True)")
         if use_cache is None or use_cache:
-            if inputs_embeds.shape[0] != 1 or F.VARIANTS["greedy_loop_b1"] or sampler is not None:
+            if inputs_embeds.shape[0] != 1 or F.VARIANTS["greedy_loop_b1"] or sampler is not None or processors is not None:
                 return self._greedy_decode_loop(inputs_embeds, attention_mask, start_image_token_id, end_image_token_id, eos_token_id,
-                                                max_new_tokens, output_image, sampler=sampler)
+                                                max_new_tokens, output_image, sampler=sampler, processors=processors)
             return self._greedy_decode_cached(inputs_embeds, start_image_token_id, end_image_token_id, eos_token_id,
                                               max_new_tokens, output_image)
         if inputs_embeds.shape[0] != 1:
@@ -902,14 +924,60 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
             raise ValueError(f"greedy_decode: stream_ids = {stream_ids}: one id in [0, 2^31) per sequence ({B})")
         return (inv_t, int(top_k), top_p, int(seed) & 0xFFFFFFFFFFFFFFFF, stream_ids)
 
+    @staticmethod
+    def _processors_of(repetition_penalty, min_new_tokens, suppress_tokens, output_logprobs, repetition_penalty_ids, max_new_tokens, V, B):
+        """greedy_decode's logits-processor arguments -> a dict of plain values for functional.LogitsProcessors (the suppressed ids still a
+        host list), or None when every option is off.  Refuses bad values by name before any device work.  V: the width of the logits;
+        B: the number of prompts."""
+        def ids_of(name, ids):
+            try:
+                out = [operator.index(i) for i in ids]
+            except TypeError:
+                raise ValueError(f"greedy_decode: {name} = {ids!r} must be a list of integer ids") from None
+            bad = [i for i in out if not 0 <= i < V]
+            if bad:
+                raise ValueError(f"greedy_decode: {name} holds ids outside [0, {V}): {bad[:4]} (strip sentinels such as the image index first)")
+            return out
+        penalty = 1.0 if repetition_penalty is None else float(repetition_penalty)
+        if not (math.isfinite(penalty) and penalty > 0):
+            raise ValueError(f"greedy_decode: repetition_penalty = {repetition_penalty} must be finite and > 0 (1: off)")
+        min_new = 0 if min_new_tokens is None else min_new_tokens
+        try:
+            if isinstance(min_new, bool):
+                raise TypeError
+            min_new = int(min_new) if isinstance(min_new, float) and min_new.is_integer() else operator.index(min_new)
+        except TypeError:
+            min_new = -1
+        if min_new < 0 or min_new > int(max_new_tokens):
+            raise ValueError(f"greedy_decode: min_new_tokens = {min_new_tokens!r} must be an integer in [0, max_new_tokens = {max_new_tokens}] "
+                             "(0: off)")
+        suppress = [] if suppress_tokens is None else ids_of("suppress_tokens", suppress_tokens)
+        marks = None
+        if repetition_penalty_ids is not None:
+            if penalty == 1.0:
+                raise ValueError("greedy_decode: repetition_penalty_ids without an active repetition_penalty: nothing would read the marks")
+            lists = list(repetition_penalty_ids)
+            if lists and isinstance(lists[0], (list, tuple, torch.Tensor)):
+                if len(lists) != B:
+                    raise ValueError(f"greedy_decode: repetition_penalty_ids holds {len(lists)} lists for {B} sequences (one list for all, "
+                                     "or one per sequence)")
+                marks = [ids_of("repetition_penalty_ids", [int(i) for i in l]) for l in lists]
+            else:
+                marks = [ids_of("repetition_penalty_ids", lists)] * B
+        if penalty == 1.0 and min_new == 0 and not suppress and not output_logprobs:
+            return None
+        return dict(repetition_penalty=penalty, min_new_tokens=min_new, suppress=sorted(set(suppress)), want_logprobs=bool(output_logprobs),
+                    marks=marks)
+
     def _greedy_decode_loop(self, inputs_embeds, attention_mask, start_image_token_id, end_image_token_id, eos_token_id, max_new_tokens,
-                            output_image, sampler=None, copies=1):
+                            output_image, sampler=None, copies=1, processors=None):
         """greedy_decode of B sequences: the prompt pass of _prefill_batch (same-length prompts as one batch, ragged ones one after the
         other), then functional.GreedyLoopGraph -- one pass over the weights per step for all sequences, head, argmax and the reference's
         mode state machine on the device.  The host reads the live counter every config.mm355_greedy_poll_steps steps (default 8: at most
         7 wasted steps per call against one synchronisation per 8 tokens; a judgement, tools/bench_greedy_batch.py gives the numbers).
         copies > 1 (one prompt): `copies` continuations of it, the prompt pass of _prefill_shared; sampler=None then walks the greedy loop
-        `copies` times over (tests)."""
+        `copies` times over (tests).  processors: _processors_of's dict (its marks one list per prompt: a prompt's list marks every one of
+        its continuations); with want_logprobs the log-probabilities are returned last."""
         if inputs_embeds.dtype != BF16:
             raise TypeError(f"inputs_embeds must be bf16, got {inputs_embeds.dtype}")
         dev = inputs_embeds.device
@@ -928,14 +996,23 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
             x0 = torch.stack([o[-1] for o in outs], 0)
         embed = self.model.embed_tokens.weight.data
         V = self.w8_lm_head[0].shape[0] if self.w8_lm_head is not None else self.lm_head.weight.shape[0]
+        proc = None
+        if processors is not None:
+            sup = processors["suppress"]
+            marks = processors["marks"]
+            proc = F.LogitsProcessors(processors["repetition_penalty"], processors["min_new_tokens"],
+                                      torch.tensor(sup, dtype=torch.int32).to(dev) if sup else None, processors["want_logprobs"],
+                                      None if marks is None else [marks[b // copies] for b in range(B * copies)])
         loop = F.GreedyLoopGraph(self.model.layers, cache.meta, cache.kv, cache.meta.cos, cache.meta.sin, h, dev, self._head_rows_device,
                                  embed, V, self._vision_head_out, start_image_token_id, end_image_token_id,
                                  self.get_model().vision_tower.image_token_len, max_new_tokens, set(eos_token_id),
-                                 poll=getattr(self.config, "mm355_greedy_poll_steps", 8), sampler=sampler)
+                                 poll=getattr(self.config, "mm355_greedy_poll_steps", 8), sampler=sampler, processors=proc)
         self._greedy_loop = loop                              # (tools / tests: steps, host_reads, the static logits of the last step)
-        ids, embs = loop.run(x0)
+        ids, embs, *logp = loop.run(x0)
         if B == 1 and copies == 1:                            # one sequence: the return shapes of _greedy_decode_cached
             embs = embs[0] if embs[0].shape[0] else torch.tensor([], dtype=torch.float32, device=dev)
+        if logp:
+            return (ids, embs, logp[0]) if output_image else (ids, logp[0])
         return (ids, embs) if output_image else ids
 
     # ------------------------------------------------------------------ HF generate() on the decode kernels (reference :711-738)

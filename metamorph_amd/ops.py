@@ -1401,6 +1401,60 @@ def greedy_advance(tok, C, state, live, embed, fed, pred_z, x_in, tok_log, z_log
                f"mm355_greedy_advance B={B} C={C} eos={len(eos)}")
 
 
+# ------------------------------------------------------------------------------------------------ logits processors, log-probabilities (csrc/logits.hip)
+
+def seen_words(C):
+    """32-bit words per row of the bitmap of seen ids over C logits: bit (i & 31) of word (i >> 5) is id i"""
+    return (int(C) + 31) // 32
+
+
+def _chk_seen(seen, R, C):
+    """a bitmap of R rows: 32-bit words (torch.int32 or torch.uint32 storage of the same bits), contiguous -> words per row"""
+    assert seen.dtype in (torch.int32, torch.uint32) and seen.dim() == 2 and seen.is_contiguous() and seen.shape[0] == R
+    assert seen.shape[1] >= seen_words(C), f"{seen.shape[1]} bitmap words per row for {C} logits"
+    return seen.shape[1]
+
+
+def logits_process_rows(x2d, penalty=1.0, seen=None, total_out=None, min_new_tokens=0, eos_ids=(), suppress_ids=None):
+    """Edits the contiguous fp32 logits x2d [R, C] in place (mm355_logits_process_rows_f32; the model of it, bit for bit, is
+    functional.logits_process_host), per row in HF's order: ids marked in seen [R, >= seen_words(C)] times / over `penalty` (1: off), the
+    eos ids -inf while total_out[r] (int32 [R]) < min_new_tokens (0: off), the ids of suppress_ids (int32 device tensor) -inf."""
+    _chk_dev(x2d, seen, total_out, suppress_ids)
+    assert x2d.dim() == 2 and x2d.is_contiguous() and x2d.dtype == torch.float32
+    R, C = x2d.shape
+    words = _chk_seen(seen, R, C) if seen is not None else 0
+    assert total_out is None or (total_out.dtype == torch.int32 and total_out.is_contiguous() and total_out.numel() == R)
+    assert suppress_ids is None or (suppress_ids.dtype == torch.int32 and suppress_ids.is_contiguous() and suppress_ids.dim() == 1)
+    eos = [int(e) for e in eos_ids]
+    arr = (_lib.ctypes.c_int32 * max(len(eos), 1))(*eos)
+    n_sup = 0 if suppress_ids is None else suppress_ids.numel()
+    _lib.check(_L().mm355_logits_process_rows_f32(x2d.data_ptr(), R, C, float(penalty), _p(seen), words, _p(total_out), int(min_new_tokens),
+                                                  _lib.ctypes.addressof(arr), len(eos), _p(suppress_ids) if n_sup else 0, n_sup, _stream()),
+               f"mm355_logits_process_rows_f32 R={R} C={C} penalty={penalty} min_new_tokens={min_new_tokens} eos={len(eos)} suppress={n_sup}")
+    return x2d
+
+
+def token_note_rows(x2d, tok, state, num_image_tokens, token_cap=None, seen=None, logp_log=None):
+    """After the pick and before greedy_advance (mm355_token_note_rows_f32; functional.token_note_host): for every row that is about to log
+    tok[r] -- state: the int32 [6, R] rows of greedy_advance -- sets the id's bit in seen [R, >= seen_words(C)] and writes its
+    log-probability under the fp32 logits x2d [R, C] as they stand to logp_log[r, n_tokens[r]] (fp32 [R, token_cap])."""
+    _chk_dev(x2d, tok, state, seen, logp_log)
+    assert x2d.dim() == 2 and x2d.is_contiguous() and x2d.dtype == torch.float32
+    R, C = x2d.shape
+    assert tok.dtype == torch.int32 and tok.is_contiguous() and tok.numel() == R
+    assert state.dtype == torch.int32 and tuple(state.shape) == (6, R) and state.is_contiguous()
+    words = _chk_seen(seen, R, C) if seen is not None else 0
+    if logp_log is not None:
+        assert logp_log.dtype == torch.float32 and logp_log.is_contiguous() and logp_log.dim() == 2 and logp_log.shape[0] == R
+        assert token_cap is None or int(token_cap) == logp_log.shape[1]
+        token_cap = logp_log.shape[1]
+    assert token_cap is not None, "token_cap: the rows of the token log (taken from logp_log where that is given)"
+    in_image, n_img, _, done, n_tokens, _ = (state[i].data_ptr() for i in range(6))
+    _lib.check(_L().mm355_token_note_rows_f32(x2d.data_ptr(), R, C, tok.data_ptr(), in_image, n_img, done, n_tokens, int(num_image_tokens),
+                                              int(token_cap), _p(seen), words, _p(logp_log), _stream()),
+               f"mm355_token_note_rows_f32 R={R} C={C} token_cap={token_cap}")
+
+
 def rows_scatter_add_(dst2d, src2d, idx_i32):
     _chk_dev(dst2d, src2d, idx_i32)
     ps, R, h, lds = _rows2d(src2d)
