@@ -585,6 +585,37 @@ int mm355_attn_decode_shared_f8(const mm355_bf16* q, int64_t ld_q, const uint8_t
                                 int64_t d, float scale, float* workspace, int64_t workspace_floats, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The same attention with INDEXED own rows: the beams of one prompt (HF GenerationMixin._beam_search, generation/utils.py; the reference
+ * reaches it through generate(use_customize_greedy=False, num_beams=K), metamorph_llama.py:711-717, where every step reorders the whole
+ * cache).  After a beam step query b continues the hypothesis of some parent beam, so its own rows are scattered over the B blocks; no row
+ * moves, a table says where each one lives.
+ *   attn_decode_shared_idx / _idx_f8: the arguments of mm355_attn_decode_shared / _f8 plus own_block, a device table of uint8 [B][ld_own_block]
+ *         (one byte names a block: B <= 255): for query b, key j >= shared_len is row j of the own block of sequence
+ *         own_block[b][j - shared_len]; keys below shared_len are the shared rows.  A NULL table is the identity: mm355_attn_decode_shared's
+ *         kernel, bit for bit, and so is the table own_block[b][*] = b.  An entry is the caller's promise; the kernel clamps it into [0, B)
+ *         and its column into [0, ld_own_block), so a wrong entry (or a wrong kv_lens[b]) still reads inside the cache and the table.  Never
+ *         read: table entries at or beyond min(kv_lens[b], max_kv_len) - shared_len, and everything mm355_attn_decode_shared never reads --
+ *         in particular the own rows of blocks the table does not point to.  The e4m3 form follows the table for bytes and scales alike and
+ *         equals the bf16 form on the dequantised cache bit for bit.  The shared part, the key split, the merge launch, the workspace
+ *         (mm355_attn_decode_shared_ws_floats) and all refusals are mm355_attn_decode_shared's; in addition a table with B > 255 or
+ *         ld_own_block < 1 is MM355_EINVAL.  The own workgroup loads the table entries of the tile after next together with the rows of
+ *         the next tile, so the dependent load is off the critical path.
+ * ------------------------------------------------------------------------------------------------ */
+int mm355_attn_decode_shared_idx(const mm355_bf16* q, int64_t ld_q, const mm355_bf16* k_shared, const mm355_bf16* v_shared,
+                                 int64_t ld_shared, const mm355_bf16* k_cache, const mm355_bf16* v_cache, int64_t ld_kv,
+                                 int64_t batch_stride_kv, const int32_t* kv_lens, const uint8_t* own_block, int64_t ld_own_block,
+                                 int64_t shared_len, int64_t max_kv_len, mm355_bf16* o, int64_t ld_o, int64_t B, int64_t Hq, int64_t Hkv,
+                                 int64_t d, float scale, float* workspace, int64_t workspace_floats, void* stream);
+int mm355_attn_decode_shared_idx_f8(const mm355_bf16* q, int64_t ld_q, const uint8_t* k_shared, const uint8_t* v_shared,
+                                    int64_t ld_shared_bytes, const float* k_shared_scale, const float* v_shared_scale,
+                                    int64_t ld_shared_scale, const uint8_t* k_cache, const uint8_t* v_cache, int64_t ld_kv_bytes,
+                                    int64_t batch_stride_kv_bytes, const float* k_scale, const float* v_scale, int64_t ld_scale,
+                                    int64_t batch_stride_scale, int fmt, const int32_t* kv_lens, const uint8_t* own_block,
+                                    int64_t ld_own_block, int64_t shared_len, int64_t max_kv_len, mm355_bf16* o, int64_t ld_o, int64_t B,
+                                    int64_t Hq, int64_t Hkv, int64_t d, float scale, float* workspace, int64_t workspace_floats,
+                                    void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Elementwise: SwiGLU (HF LlamaMLP; K12), GELU (projector / vision_head), scaling helpers.
  * gu = [M][2I] with gate in columns [0,I) and up in [I,2I).
  * ------------------------------------------------------------------------------------------------ */
@@ -807,6 +838,57 @@ int mm355_logits_process_rows_f32(float* x, int64_t R, int64_t C, float penalty,
 int mm355_token_note_rows_f32(const float* x, int64_t R, int64_t C, const int32_t* tok, const int32_t* in_image, const int32_t* n_img,
                               const int32_t* done, const int32_t* n_tokens, int num_image_tokens, int64_t token_cap, uint32_t* seen,
                               int64_t seen_words, float* logp_log, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Beam search in the same loop (functional.BeamLoopGraph; csrc/beam.hip): HF's GenerationMixin._beam_search (transformers
+ * generation/utils.py, which the reference reaches through generate(use_customize_greedy=False, num_beams=K), metamorph_llama.py:711-717)
+ * for ONE prompt, do_sample=False, no logits processors.  K <= MM355_BEAM_MAX beams, V logits, M = max(2, 1 + eos ids) * K candidates.
+ * Both entry points read no host value at run time (they can be captured), use no floating-point atomics and are bit-reproducible
+ * functions of their inputs; all arithmetic is fp32 with HF's literal -1e9.
+ * beam_select_rows_f32: x [K, V] contiguous fp32 logits, running [K] the beams' scores (no NaN).  Writes
+ *           stats [K, 2] = (row maximum m, lse = ln sum_i exp(x_i - m)), computed as token_note_rows_f32 computes them (v_exp_f32, the same
+ *                 fixed-order tree; within 1e-4 + 2^-22 |value| of fp64); a NaN in the row, m = +inf or m = -inf: lse = NaN
+ *           cand_val [M], cand_idx [M]: the M best of acc[b * V + i] = ((x[b,i] - m_b) - lse_b) + running[b], the operations in exactly
+ *                 that fp32 order, sorted by value descending, a NaN after every number (a row whose lse is NaN has NaN scores
+ *                 throughout), among equals the lower flat index first
+ *         One workgroup per row finds the row's min(M, V) best (the M best of all lie among them): the min(M, V)-th largest of the 1024
+ *         per-thread maxima bounds them from below, what reaches the bound goes through an exact radix select on (order-preserving value
+ *         key, index) pairs with integer LDS histograms; a second launch of one workgroup ranks the K * min(M, V) partial candidates.
+ *         workspace: mm355_beam_select_rows_ws_bytes(K, V, M) bytes, 4-byte aligned.  MM355_EINVAL before any launch: a null pointer, K
+ *         outside [1, MM355_BEAM_MAX], M outside [K, 9 K] or > K V, V < 1 or beyond argmax_rows_f32's bound, a workspace too small.
+ *         The host model: functional.beam_select_host.
+ * beam_advance: one launch runs HF's step on the M sorted candidates (candidate c: parent = idx / V, id = idx % V; an idx outside [0, K V)
+ *         is clamped into it) and device-resident state: running [K] fp32 (start: 0, -1e9, ...), fin_score [K] fp32 (start: -1e9),
+ *         fin_flag [K] int32 (0), fin_end [K, 3] int32, scal [2] int32 = (heuristic unsatisfied: 1, generated length n: 0), live [1] (1).
+ *           hit[c] = id among the eos ids, or n + 1 >= max_new_tokens
+ *           running beams: the K best of val + hit * -1e9 -> running, tok [K], parent [K], row n of tok_log / parent_log [log_cap, K]
+ *           pool: the K best of (old pool, val / len_pow[n] - 1e9 [pool full and early_stopping == 1] - 1e9 [heuristic satisfied]
+ *                 - 1e9 [not (hit and c < K)]), three successive additions; flags travel with the scores and fin_end of an entry says
+ *                 where its hypothesis ended: (step n, the parent's slot, id) -- the host rebuilds the ids from the back-pointer logs
+ *           n += 1; unsatisfied &= any_k(running[0] / len_pow[L - 1] > (fin_flag[k] ? min(fin_score) : -1e9)), L = max_new_tokens if
+ *                 early_stopping == 2 ("never") and length_penalty > 0, else n
+ *           live[0] = 0 unless unsatisfied and not (all flags and early_stopping == 1) and not all M candidates hit
+ *           own_block (nullable, uint8 [K, ld_own_block], the table of mm355_attn_decode_shared_idx): column t < n of slot i becomes that
+ *                 of slot parent[i] (a column is read whole before it is written: in place), column n becomes i -- the row slot i
+ *                 itself appends in the next decode step, in its own block
+ *           x_in (nullable together with embed): row i = embed[tok[i]]
+ *         Ties in the three selections go to the lower index (torch.topk leaves them open), a NaN sorts last.  len_pow: DEVICE fp32
+ *         [max_new_tokens], len_pow[t - 1] = (float)(t ** length_penalty), made on the host: the device calls no pow.  With live[0] == 0
+ *         the launch writes nothing, so a finished search rides along as finished sequences do in greedy_advance; n outside [0,
+ *         max_new_tokens) sets live[0] = 0 and writes nothing else.  eos_ids: HOST memory, n_eos <= MM355_GREEDY_MAX_EOS.  MM355_EINVAL:
+ *         a null pointer (own_block and the embed / x_in pair excepted), K, M, V as above, max_new_tokens < 1, log_cap or ld_own_block <
+ *         max_new_tokens, early_stopping outside {0, 1, 2}, a NaN length_penalty, V > embed_rows, rows that are not 16-byte vectors.
+ *         The host model: functional.beam_step_host.
+ * ------------------------------------------------------------------------------------------------ */
+#define MM355_BEAM_MAX 8
+int64_t mm355_beam_select_rows_ws_bytes(int64_t K, int64_t V, int64_t M);
+int mm355_beam_select_rows_f32(const float* x, int64_t K, int64_t V, const float* running, int64_t M, float* stats, float* cand_val,
+                               int32_t* cand_idx, void* workspace, int64_t workspace_bytes, void* stream);
+int mm355_beam_advance(const float* cand_val, const int32_t* cand_idx, int64_t K, int64_t M, int64_t V, float* running, float* fin_score,
+                       int32_t* fin_flag, int32_t* fin_end, int32_t* scal, int32_t* live, int32_t* tok, int32_t* parent, int32_t* tok_log,
+                       int32_t* parent_log, int64_t log_cap, uint8_t* own_block, int64_t ld_own_block, const mm355_bf16* embed,
+                       int64_t ld_embed, int64_t embed_rows, mm355_bf16* x_in, int64_t ld_x, int64_t h, const float* len_pow,
+                       int max_new_tokens, float length_penalty, int early_stopping, const int32_t* eos_ids, int n_eos, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * ZeRO-2 shard update (replaces DeepSpeed zero2.json + HF adamw_torch, train.py:82): AdamW on the

@@ -10,6 +10,9 @@
 // shared_merge_kernel, the second launch, folds the nsplit + 1 partials of a row.  The key split depends on the launch arguments alone.
 // The e4m3 form differs in the tile mover alone (attn_tile.h), so it equals the bf16 form on the dequantised cache bit for bit.
 // Never read: rows [0, shared_len) of a sequence's own block, shared rows >= shared_len, own rows >= min(kv_lens[b], max_kv_len).
+// The indexed form (IDX; the beams of a beam search, functional.BeamLoopGraph): own row j of query b is row j of the block own_block[b][j -
+// shared_len], one byte per row.  The own workgroup fetches the entries of the tile after next with the rows of the next tile, so the
+// dependent load in front of a row's address has a tile's compute to arrive; everything else is the same code.
 #include "attn_tile.h"
 #include <algorithm>
 
@@ -23,6 +26,7 @@ struct SArgs {
     const unsigned char* k; const unsigned char* v; int64_t ld_kv, bs_kv;       // own blocks, BYTES per row / per sequence
     const float* ks; const float* vs; int64_t ld_sc, bs_sc;                     // e4m3 form: scales [B][rows][Hkv]
     const int32_t* kv_lens; uint16_t* o; int64_t ld_o; float* ws;
+    const uint8_t* own_block; int64_t ld_ob;                                    // indexed form: block of own row t of query b at [b * ld_ob + t]
     int B, Hkv, d, G, R, nqt, nsplit, tps, shared_len, max_kv; int64_t rpad;
     float scale;
 };
@@ -49,7 +53,7 @@ Plan make_plan(int64_t B, int64_t Hq, int64_t Hkv, int64_t shared_len) {
     return p;
 }
 
-template <int DP, bool F8>
+template <int DP, bool F8, bool IDX>
 __global__ __launch_bounds__(NT) void shared_kernel(SArgs a) {
     using G_ = Geo<DP>;
     constexpr int KS = G_::KS, NF = G_::NF;
@@ -75,9 +79,10 @@ __global__ __launch_bounds__(NT) void shared_kernel(SArgs a) {
         k_lo = a.shared_len;
         k_end = min(a.kv_lens[b], a.max_kv);                 // the host bound keeps a wrong kv_lens[] inside the cache
         r0 = b * G; nrow = G; slot = a.nsplit;
-        kbase = a.k + (int64_t)b * a.bs_kv + (int64_t)hk * d * EB;
-        vbase = a.v + (int64_t)b * a.bs_kv + (int64_t)hk * d * EB;
-        if (F8) { ksb = a.ks + (int64_t)b * a.bs_sc + hk; vsb = a.vs + (int64_t)b * a.bs_sc + hk; }
+        const int64_t blk0 = IDX ? 0 : b;                    // (indexed: the block comes per row, from the table)
+        kbase = a.k + blk0 * a.bs_kv + (int64_t)hk * d * EB;
+        vbase = a.v + blk0 * a.bs_kv + (int64_t)hk * d * EB;
+        if (F8) { ksb = a.ks + blk0 * a.bs_sc + hk; vsb = a.vs + blk0 * a.bs_sc + hk; }
         ld = a.ld_kv; ld_sc = a.ld_sc;
     } else {
         const int qt = blockIdx.x / a.nsplit, split = blockIdx.x % a.nsplit;
@@ -112,18 +117,34 @@ __global__ __launch_bounds__(NT) void shared_kernel(SArgs a) {
 
     if (ntiles > 0) {
         Stage<NV, F8> rk, rv;
-        load_tile<DP, NV, F8>(rk, kbase, ksb, ld, ld_sc, k_lo, k_end, d, tid);
-        load_tile<DP, NV, F8>(rv, vbase, vsb, ld, ld_sc, k_lo, k_end, d, tid);
+        int blk[NV];                                         // indexed own rows: the blocks of the tile `fetch` moves next
+        const uint8_t* tbl = nullptr;
+        if constexpr (IDX) {
+            if (own) {
+                tbl = a.own_block + (int64_t)((int)blockIdx.x - nshared) * a.ld_ob;
+                load_blocks<DP, NV>(blk, tbl, (int)a.ld_ob, a.B, a.shared_len, k_lo, k_end, tid);
+            }
+        }
+        auto fetch = [&](int row0) {                         // the K and V tiles at row0 -> registers
+            if constexpr (IDX) {
+                if (own) {
+                    load_tile_idx<DP, NV, F8>(rk, kbase, ksb, ld, ld_sc, a.bs_kv, a.bs_sc, blk, row0, k_end, d, tid);
+                    load_tile_idx<DP, NV, F8>(rv, vbase, vsb, ld, ld_sc, a.bs_kv, a.bs_sc, blk, row0, k_end, d, tid);
+                    load_blocks<DP, NV>(blk, tbl, (int)a.ld_ob, a.B, a.shared_len, row0 + 64, k_end, tid);
+                    return;
+                }
+            }
+            load_tile<DP, NV, F8>(rk, kbase, ksb, ld, ld_sc, row0, k_end, d, tid);
+            load_tile<DP, NV, F8>(rv, vbase, vsb, ld, ld_sc, row0, k_end, d, tid);
+        };
+        fetch(k_lo);
         store_tile<DP, NV, F8>(rk, sK, tid);
         store_tile<DP, NV, F8>(rv, sV, tid);
         __syncthreads();
         for (int t = 0; t < ntiles; ++t) {
             const int kv0 = k_lo + t * 64;
             const bool more = t + 1 < ntiles;
-            if (more) {
-                load_tile<DP, NV, F8>(rk, kbase, ksb, ld, ld_sc, kv0 + 64, k_end, d, tid);
-                load_tile<DP, NV, F8>(rv, vbase, vsb, ld, ld_sc, kv0 + 64, k_end, d, tid);
-            }
+            if (more) fetch(kv0 + 64);
             if (wave_on) softmax_tile<DP>(sK, sV, qf, ot, m_run, l_run, kv0, kv0 + 64 > k_end, k_end - 1, sl2, fr, fq);
             __syncthreads();                                 // every wave is done reading this tile
             if (more) {
@@ -161,14 +182,17 @@ __global__ __launch_bounds__(NT) void shared_merge_kernel(SArgs a) {
     *(u32x2*)(a.o + (int64_t)b * a.ld_o + (int64_t)(hk * a.G + g) * a.d + c) = w;
 }
 
-template <int DP, bool F8>
-int launch(const SArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL((shared_kernel<DP, F8>), dim3((unsigned)(a.nqt * a.nsplit + a.B), (unsigned)a.Hkv), dim3(NT), 0, s, a);
+template <int DP, bool F8, bool IDX>
+int launch_k(const SArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL((shared_kernel<DP, F8, IDX>), dim3((unsigned)(a.nqt * a.nsplit + a.B), (unsigned)a.Hkv), dim3(NT), 0, s, a);
     if (mm_launch_status() != MM355_OK) return MM355_ELAUNCH;
     const unsigned gx = (unsigned)(((int64_t)a.R * (DP / 4) + NT - 1) / NT);
     hipLaunchKernelGGL((shared_merge_kernel<DP>), dim3(gx, (unsigned)a.Hkv), dim3(NT), 0, s, a);
     return mm_launch_status();
 }
+
+template <int DP, bool F8>
+int launch(const SArgs& a, hipStream_t s) { return a.own_block ? launch_k<DP, F8, true>(a, s) : launch_k<DP, F8, false>(a, s); }
 
 int pick_dp(int64_t d) { return d <= 64 ? 64 : (d <= 96 ? 96 : 128); }
 
@@ -177,11 +201,13 @@ int64_t ws_floats(const Plan& p, int64_t Hkv, int64_t d) { return Hkv * (p.nspli
 // eb = bytes per cached element (2: bf16, 1: e4m3); the row and sequence strides arrive in BYTES
 int shared_impl(const mm355_bf16* q, int64_t ld_q, const void* ksh, const void* vsh, int64_t ld_sh, const float* kssh, const float* vssh,
                 int64_t ld_scsh, const void* k, const void* v, int64_t ld_kv, int64_t bs_kv, int eb, const float* ks, const float* vs,
-                int64_t ld_sc, int64_t bs_sc, const int32_t* kv_lens, int64_t shared_len, int64_t max_kv_len, mm355_bf16* o, int64_t ld_o,
-                int64_t B, int64_t Hq, int64_t Hkv, int64_t d, float scale, float* ws, int64_t ws_fl, void* stream) {
+                int64_t ld_sc, int64_t bs_sc, const int32_t* kv_lens, const uint8_t* own_block, int64_t ld_ob, int64_t shared_len,
+                int64_t max_kv_len, mm355_bf16* o, int64_t ld_o, int64_t B, int64_t Hq, int64_t Hkv, int64_t d, float scale, float* ws,
+                int64_t ws_fl, void* stream) {
     if (!q || !ksh || !vsh || !k || !v || !kv_lens || !o || B <= 0 || Hq <= 0 || Hkv <= 0 || (Hq % Hkv) || d <= 0 || max_kv_len <= 0 ||
         shared_len < 0 || shared_len > max_kv_len || max_kv_len > 0x7fffffc0ll || B * (Hq / Hkv) > 0x7fffffc0ll || B > 0x7ffffffll || Hkv > 65535)
         return MM355_EINVAL;
+    if (own_block && (B > 255 || ld_ob < 1 || ld_ob > 0x7fffffffll)) return MM355_EINVAL;      // one byte names a block
     if ((d & 7) || d > 128) return MM355_EUNSUPPORTED;
     const uintptr_t amask = eb == 2 ? 15u : 7u;              // one 16-byte (bf16) or 8-byte (e4m3) load per 8 columns
     if (!mm_aligned16(q) || !mm_aligned16(o) || (ld_q & 7) || (ld_o & 7) || ld_q < Hq * d || ld_o < Hq * d ||
@@ -196,7 +222,7 @@ int shared_impl(const mm355_bf16* q, int64_t ld_q, const void* ksh, const void* 
     if ((int64_t)p.nqt * p.nsplit + B > 0x7fffffffll) return MM355_EINVAL;
     if (!ws || (((uintptr_t)ws) & 15u) || ws_fl < ws_floats(p, Hkv, d)) return MM355_EINVAL;
     SArgs a{q, ld_q, (const unsigned char*)ksh, (const unsigned char*)vsh, ld_sh, kssh, vssh, ld_scsh, (const unsigned char*)k,
-            (const unsigned char*)v, ld_kv, bs_kv, ks, vs, ld_sc, bs_sc, kv_lens, o, ld_o, ws, (int)B, (int)Hkv, (int)d, p.G, p.R, p.nqt,
+            (const unsigned char*)v, ld_kv, bs_kv, ks, vs, ld_sc, bs_sc, kv_lens, o, ld_o, ws, own_block, ld_ob, (int)B, (int)Hkv, (int)d, p.G, p.R, p.nqt,
             p.nsplit, p.tps, (int)shared_len, (int)max_kv_len, p.rpad, scale};
     hipStream_t s = (hipStream_t)stream;
     const int dp = pick_dp(d);
@@ -228,7 +254,18 @@ extern "C" int mm355_attn_decode_shared(const mm355_bf16* q, int64_t ld_q, const
                                         int64_t workspace_floats, void* stream) {
     (void)hipGetLastError();
     return shared_impl(q, ld_q, k_shared, v_shared, ld_shared * 2, nullptr, nullptr, 0, k_cache, v_cache, ld_kv * 2, batch_stride_kv * 2, 2, nullptr,
-                       nullptr, 0, 0, kv_lens, shared_len, max_kv_len, o, ld_o, B, Hq, Hkv, d, scale, workspace, workspace_floats, stream);
+                       nullptr, 0, 0, kv_lens, nullptr, 0, shared_len, max_kv_len, o, ld_o, B, Hq, Hkv, d, scale, workspace, workspace_floats, stream);
+}
+
+extern "C" int mm355_attn_decode_shared_idx(const mm355_bf16* q, int64_t ld_q, const mm355_bf16* k_shared, const mm355_bf16* v_shared,
+                                            int64_t ld_shared, const mm355_bf16* k_cache, const mm355_bf16* v_cache, int64_t ld_kv,
+                                            int64_t batch_stride_kv, const int32_t* kv_lens, const uint8_t* own_block, int64_t ld_own_block,
+                                            int64_t shared_len, int64_t max_kv_len, mm355_bf16* o, int64_t ld_o, int64_t B, int64_t Hq,
+                                            int64_t Hkv, int64_t d, float scale, float* workspace, int64_t workspace_floats, void* stream) {
+    (void)hipGetLastError();
+    return shared_impl(q, ld_q, k_shared, v_shared, ld_shared * 2, nullptr, nullptr, 0, k_cache, v_cache, ld_kv * 2, batch_stride_kv * 2, 2, nullptr,
+                       nullptr, 0, 0, kv_lens, own_block, ld_own_block, shared_len, max_kv_len, o, ld_o, B, Hq, Hkv, d, scale, workspace,
+                       workspace_floats, stream);
 }
 
 extern "C" int mm355_attn_decode_shared_f8(const mm355_bf16* q, int64_t ld_q, const uint8_t* k_shared, const uint8_t* v_shared,
@@ -241,6 +278,21 @@ extern "C" int mm355_attn_decode_shared_f8(const mm355_bf16* q, int64_t ld_q, co
     (void)hipGetLastError();
     if (fmt != MM355_KV8_E4M3 || !k_scale || !v_scale || !k_shared_scale || !v_shared_scale) return MM355_EINVAL;
     return shared_impl(q, ld_q, k_shared, v_shared, ld_shared_bytes, k_shared_scale, v_shared_scale, ld_shared_scale, k_cache, v_cache, ld_kv_bytes,
-                       batch_stride_kv_bytes, 1, k_scale, v_scale, ld_scale, batch_stride_scale, kv_lens, shared_len, max_kv_len, o, ld_o, B, Hq,
-                       Hkv, d, scale, workspace, workspace_floats, stream);
+                       batch_stride_kv_bytes, 1, k_scale, v_scale, ld_scale, batch_stride_scale, kv_lens, nullptr, 0, shared_len, max_kv_len, o,
+                       ld_o, B, Hq, Hkv, d, scale, workspace, workspace_floats, stream);
+}
+
+extern "C" int mm355_attn_decode_shared_idx_f8(const mm355_bf16* q, int64_t ld_q, const uint8_t* k_shared, const uint8_t* v_shared,
+                                               int64_t ld_shared_bytes, const float* k_shared_scale, const float* v_shared_scale,
+                                               int64_t ld_shared_scale, const uint8_t* k_cache, const uint8_t* v_cache, int64_t ld_kv_bytes,
+                                               int64_t batch_stride_kv_bytes, const float* k_scale, const float* v_scale, int64_t ld_scale,
+                                               int64_t batch_stride_scale, int fmt, const int32_t* kv_lens, const uint8_t* own_block,
+                                               int64_t ld_own_block, int64_t shared_len, int64_t max_kv_len, mm355_bf16* o, int64_t ld_o,
+                                               int64_t B, int64_t Hq, int64_t Hkv, int64_t d, float scale, float* workspace,
+                                               int64_t workspace_floats, void* stream) {
+    (void)hipGetLastError();
+    if (fmt != MM355_KV8_E4M3 || !k_scale || !v_scale || !k_shared_scale || !v_shared_scale) return MM355_EINVAL;
+    return shared_impl(q, ld_q, k_shared, v_shared, ld_shared_bytes, k_shared_scale, v_shared_scale, ld_shared_scale, k_cache, v_cache, ld_kv_bytes,
+                       batch_stride_kv_bytes, 1, k_scale, v_scale, ld_scale, batch_stride_scale, kv_lens, own_block, ld_own_block, shared_len,
+                       max_kv_len, o, ld_o, B, Hq, Hkv, d, scale, workspace, workspace_floats, stream);
 }

@@ -26,6 +26,38 @@ MM_DEV void load_tile(Stage<NV, F8>& st, const unsigned char* base, const float*
         }
     }
 }
+// The block numbers of the rows load_tile_idx is about to move: blk[i] = tbl[row - first] of this thread's i-th vector, clamped into [0, nblk)
+// (an entry is the caller's promise; a wrong one still names a block of the cache) and the column into [0, cols).  Rows are clamped as
+// load_tile clamps them, so no entry at or beyond end - first is read; a tile that starts at or beyond `end` reads nothing.
+template <int DP, int NV>
+MM_DEV void load_blocks(int (&blk)[NV], const uint8_t* tbl, int cols, int nblk, int first, int row0, int end, int tid) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int v = tid + i * NT, row = v / (DP / 8);
+        const bool on = v < Geo<DP>::V64 && row0 < end;
+        const int col = min(min(row0 + row, end - 1) - first, cols - 1);
+        blk[i] = on ? min((int)tbl[col], nblk - 1) : 0;
+    }
+}
+// load_tile where row r of the tile lives in block blk[] of a [blocks][rows] cache (block strides bs BYTES / bs_sc scales): the same
+// loads from other addresses, so the tile in LDS -- and everything computed from it -- is load_tile's on the gathered rows
+template <int DP, int NV, bool F8>
+MM_DEV void load_tile_idx(Stage<NV, F8>& st, const unsigned char* base, const float* sbase, int64_t ld, int64_t ld_sc, int64_t bs, int64_t bs_sc,
+                          const int (&blk)[NV], int row0, int end, int d, int tid) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int v = tid + i * NT, row = v / (DP / 8), c = v % (DP / 8);
+        const bool on = v < Geo<DP>::V64 && c * 8 < d;
+        const int rr = min(row0 + row, end - 1);
+        const unsigned char* p = base + blk[i] * bs + (int64_t)rr * ld;
+        if constexpr (F8) {
+            st.r[i] = on ? *(const u32x2*)(p + c * 8) : u32x2{0u, 0u};
+            st.s[i] = on ? sbase[blk[i] * bs_sc + (int64_t)rr * ld_sc] : 0.f;
+        } else {
+            st.r[i] = on ? *(const u32x4*)(p + c * 16) : u32x4{0u, 0u, 0u, 0u};
+        }
+    }
+}
 template <int DP, int NV, bool F8>
 MM_DEV void store_tile(const Stage<NV, F8>& st, unsigned char* s, int tid) {
 #pragma unroll

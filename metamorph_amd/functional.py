@@ -786,6 +786,7 @@ class KVCache:
         self.Hq, self.d = Hq, d
         self.shared_len = 0                                                      # > 0: rows [0, shared_len) of sequence 0 are every sequence's first rows
         self.shared_ws = None
+        self.own_block = None                                                    # uint8 [batch, own rows]: the block each own row lives in (beams)
         self.ws = None
         if Hq is not None:                                                       # (sized for the whole batch: beyond 16 rows one attention launch serves all of them)
             self.ws = torch.zeros(int(ops._L().mm355_attn_decode_ws_floats(batch, Hq, d, max_len)), device=device,
@@ -798,14 +799,25 @@ class KVCache:
 
     @property
     def shared(self):
-        """(shared_len, workspace of mm355_attn_decode_shared) while the first rows are shared, else None"""
-        return (self.shared_len, self.shared_ws) if self.shared_len > 0 else None
+        """(shared_len, workspace of mm355_attn_decode_shared) while the first rows are shared, else None; with a table of own rows
+        (set_shared(n, own_rows=...)) it rides along as a third entry"""
+        if self.shared_len <= 0:
+            return None
+        return (self.shared_len, self.shared_ws) if self.own_block is None else (self.shared_len, self.shared_ws, self.own_block)
 
-    def set_shared(self, n):
+    def set_shared(self, n, own_rows=None):
         """Declare rows [0, n) of sequence 0 the first n rows of EVERY sequence (n continuations of one prompt: the prompt's rows are stored
         and read once; rows [0, n) of the other sequences' blocks are never read again).  Every sequence must hold at least n rows
-        (set_lengths first); n = 0 ends the sharing.  The decode step then attends through mm355_attn_decode_shared."""
+        (set_lengths first); n = 0 ends the sharing.  The decode step then attends through mm355_attn_decode_shared.
+        own_rows = r (the beams of a beam search): also allocates own_block, uint8 [batch, r], the block in which own row t of sequence b
+        lives -- the identity at the start; the step then attends through mm355_attn_decode_shared_idx and whoever permutes the
+        sequences (mm355_beam_advance) rewrites the table instead of moving rows."""
         n = int(n)
+        self.own_block = None
+        if own_rows is not None:
+            if n <= 0 or int(own_rows) < 1 or self.batch > 255:
+                raise ValueError(f"a table of own rows needs a shared prefix (got {n} rows), at least one column (got {own_rows}) and at "
+                                 f"most 255 sequences (got {self.batch}): one byte names a block")
         if n < 0 or n > min(self.lengths):
             raise ValueError(f"shared prefix of {n} rows on sequences of {self.lengths} rows: every sequence must hold the shared rows")
         if n > 0:
@@ -816,6 +828,8 @@ class KVCache:
             if n_ws <= 0:
                 raise ValueError(f"mm355_attn_decode_shared has no workspace for batch={self.batch} Hq={self.Hq} Hkv={Hkv} d={self.d}")
             self.shared_ws = torch.empty(n_ws, device=self.k.device, dtype=torch.float32)
+            if own_rows is not None:
+                self.own_block = torch.arange(self.batch, dtype=torch.uint8).view(-1, 1).repeat(1, int(own_rows)).to(self.k.device)
         else:
             self.shared_ws = None
         self.shared_len = n
@@ -1256,14 +1270,16 @@ def _proj(on8, rec, name, weights, w8_op, bf16_op, x, *args, **kw):
 def _attend_decode(q, i, meta, k, v, kv8, len_dev, ws, kv_bound, shared=None):
     """Attention of the step's new rows (one per sequence, already appended) over layer i of the cache: every sequence over its own rows
     (mm355_attn_decode / _f8), or, on a cache whose first rows are shared (KVCache.shared: (shared_len, workspace)), over rows [0,
-    shared_len) of sequence 0 and then its own rows (mm355_attn_decode_shared / _f8)."""
+    shared_len) of sequence 0 and then its own rows (mm355_attn_decode_shared / _f8); a third entry of `shared` is the table that says in
+    which block each own row lives (mm355_attn_decode_shared_idx / _idx_f8)."""
     H = (meta.Hq, meta.Hkv, meta.d, meta.scale)
     if shared is not None:
-        P, sws = shared
+        P, sws, *tbl = shared
+        tbl = {"own_block": tbl[0]} if tbl else {}
         if kv8 is not None:
             return ops.attn_decode_shared_f8(q, k[i, 0], v[i, 0], kv8[0][i, 0], kv8[1][i, 0], k[i], v[i], kv8[0][i], kv8[1][i], len_dev, P,
-                                             kv_bound, *H, workspace=sws)
-        return ops.attn_decode_shared(q, k[i, 0], v[i, 0], k[i], v[i], len_dev, P, kv_bound, *H, workspace=sws)
+                                             kv_bound, *H, workspace=sws, **tbl)
+        return ops.attn_decode_shared(q, k[i, 0], v[i, 0], k[i], v[i], len_dev, P, kv_bound, *H, workspace=sws, **tbl)
     if kv8 is not None:
         return ops.attn_decode_f8(q, k[i], v[i], kv8[0][i], kv8[1][i], len_dev, kv_bound, *H, workspace=ws)
     return ops.attn_decode(q, k[i], v[i], len_dev, kv_bound, *H, workspace=ws)
@@ -1526,6 +1542,168 @@ def greedy_advance_host(state, tok, start_id, end_id, num_image_tokens, max_new_
     if tok in eos_ids or s["total_out"] > max_new_tokens:
         s["done"] = 1
     return ("z", "fed") if image_row else ("tok", "embed")
+
+
+BEAM_MAX = 8                                                 # MM355_BEAM_MAX
+BEAM_EARLY_STOPPING = {False: 0, True: 1, "never": 2}        # mm355_beam_advance's early_stopping
+
+
+def beam_candidates(num_beams, n_eos):
+    """M: the candidates HF's beam search keeps per step (`beams_to_keep`), max(2, 1 + eos ids) * K"""
+    return max(2, 1 + int(n_eos)) * int(num_beams)
+
+
+def beam_len_pow(max_new_tokens, length_penalty):
+    """float32(t ** length_penalty), t = 1 .. max_new_tokens: the divisors of HF's length penalty as it forms them (a Python int to a
+    Python power, rounded to fp32 where it meets the fp32 scores).  The device reads this table and calls no pow."""
+    import numpy as np
+    out = np.empty(int(max_new_tokens), dtype=np.float32)
+    with np.errstate(over="ignore"):
+        for t in range(1, int(max_new_tokens) + 1):
+            try:
+                out[t - 1] = np.float32(t ** length_penalty)
+            except OverflowError:
+                out[t - 1] = np.float32(np.inf)
+    return out
+
+
+def _beam_order(vals):
+    """indices of `vals` in the candidates' order: value descending, a NaN after every number, among equals the lower index first
+    (torch.topk leaves ties open; this is the rule of cand_beats in csrc/beam.hip)"""
+    import numpy as np
+    v = np.asarray(vals, dtype=np.float32)
+    nan = np.isnan(v)
+    return np.lexsort((np.arange(v.shape[0]), np.where(nan, np.float32(0), -v), nan))
+
+
+def beam_logprob_rows_host(x, stats):
+    """(x[b, i] - m_b) - lse_b in fp32, in that order: the log-probabilities mm355_beam_select_rows_f32 forms from its own statistics
+    stats [K, 2] = (m, lse); a row whose lse is NaN (a NaN in the row, m = +-inf) is NaN throughout."""
+    import numpy as np
+    x = np.asarray(x, dtype=np.float32)
+    st = np.asarray(stats, dtype=np.float32)
+    with np.errstate(all="ignore"):
+        lp = (x - st[:, :1]) - st[:, 1:2]
+    lp[np.isnan(st[:, 1])] = np.float32("nan")
+    return lp
+
+
+def beam_select_host(lp, running, M):
+    """Step 1 of HF's beam step: the M best of acc[b * V + i] = lp[b, i] + running[b] (fp32) -> (values [M] fp32, flat indices [M] int32),
+    sorted in _beam_order.  The specification of the candidate list of mm355_beam_select_rows_f32 (given beam_logprob_rows_host of its
+    statistics)."""
+    import numpy as np
+    lp = np.asarray(lp, dtype=np.float32)
+    with np.errstate(all="ignore"):
+        acc = (lp + np.asarray(running, dtype=np.float32)[:, None]).reshape(-1)
+    order = _beam_order(acc)[:int(M)]
+    return acc[order], order.astype(np.int32)
+
+
+def beam_state_host(num_beams, max_new_tokens):
+    """The state of a beam search before its first step (HF _beam_search, section 3): a dict of NumPy arrays, the layout of the device
+    state of BeamLoopGraph.  own_block is the table of mm355_attn_decode_shared_idx, the identity at the start."""
+    import numpy as np
+    K, cap = int(num_beams), int(max_new_tokens) + 1
+    running = np.full(K, -1e9, dtype=np.float32)
+    running[0] = 0
+    return dict(running=running, fin_score=np.full(K, -1e9, dtype=np.float32), fin_flag=np.zeros(K, dtype=np.int32),
+                fin_end=np.full((K, 3), -1, dtype=np.int32), scal=np.array([1, 0], dtype=np.int32), live=np.array([1], dtype=np.int32),
+                tok=np.zeros(K, dtype=np.int32), parent=np.zeros(K, dtype=np.int32), tok_log=np.zeros((cap, K), dtype=np.int32),
+                parent_log=np.zeros((cap, K), dtype=np.int32), own_block=np.repeat(np.arange(K, dtype=np.uint8)[:, None], cap, 1))
+
+
+def beam_step_host(state, cand_val, cand_idx, V, eos_ids, max_new_tokens, len_pow, length_penalty=1.0, early_stopping=False):
+    """Steps 2 - 6 of one iteration of HF's GenerationMixin._beam_search (transformers 5.15, generation/utils.py: stopping criteria,
+    _get_running_beams_for_next_iteration, _update_finished_beams, _check_early_stop_heuristic, _beam_search_has_unfinished_sequences)
+    for ONE prompt on the M sorted candidates of step 1, in fp32 with HF's literal -1e9: the specification of mm355_beam_advance.
+    state: beam_state_host's dict, updated in place (a search whose live flag is 0 changes nothing); len_pow: beam_len_pow.
+    Besides HF's state it keeps what the device keeps instead of id sequences: row n of the back-pointer logs tok_log / parent_log, for
+    every pool entry where its hypothesis ended (fin_end: step, the parent's slot, id), and the table own_block: after the step whose
+    generated length was n, own rows [0, n) of slot i are those of its parent and row n is the row slot i appends next, in block i."""
+    import numpy as np
+    s = state
+    if not s["live"][0]:
+        return
+    f32, NEG = np.float32, np.float32(-1e9)
+    K, M = s["running"].shape[0], len(cand_val)
+    unsat, n = int(s["scal"][0]), int(s["scal"][1])
+    if not 0 <= n < int(max_new_tokens):
+        s["live"][0] = 0
+        return
+    val = np.asarray(cand_val, dtype=np.float32)
+    idx = np.clip(np.asarray(cand_idx, dtype=np.int64), 0, K * int(V) - 1)
+    par, ids = (idx // V).astype(np.int32), (idx % V).astype(np.int32)
+    eos = set(int(e) for e in eos_ids)
+    hit = np.array([int(i) in eos or n + 1 >= max_new_tokens for i in ids])
+    with np.errstate(all="ignore"):
+        # 3. running beams
+        run = val + hit.astype(np.float32) * NEG
+        pick = _beam_order(run)[:K]
+        s["running"][:] = run[pick]
+        s["tok"][:], s["parent"][:] = ids[pick], par[pick]
+        s["tok_log"][n], s["parent_log"][n] = ids[pick], par[pick]
+        # 4. finished pool
+        full = bool(s["fin_flag"].all())
+        fin_now = hit & (np.arange(M) < K)
+        fin = val / f32(len_pow[n])
+        fin = fin + f32(full and early_stopping is True) * NEG
+        fin = fin + f32(not unsat) * NEG
+        fin = fin + (~fin_now).astype(np.float32) * NEG
+        scores = np.concatenate([s["fin_score"], fin.astype(np.float32)])
+        flags = np.concatenate([s["fin_flag"], fin_now.astype(np.int32)])
+        ends = np.concatenate([s["fin_end"], np.stack([np.full(M, n, dtype=np.int32), par, ids], 1)])
+        keep = _beam_order(scores)[:K]
+        s["fin_score"][:], s["fin_flag"][:], s["fin_end"][:] = scores[keep], flags[keep], ends[keep]
+        # 5. the heuristic
+        n1 = n + 1
+        fixed = early_stopping == "never" and length_penalty > 0.0
+        best = s["running"][0] / f32(len_pow[(int(max_new_tokens) if fixed else n1) - 1])
+        worst = np.where(s["fin_flag"] != 0, np.min(s["fin_score"]), NEG)
+        unsat = int(bool(unsat) and bool(np.any(best > worst)))
+    s["scal"][:] = (unsat, n1)
+    # 6. go on?
+    if not (unsat and not (bool(s["fin_flag"].all()) and early_stopping is True) and not bool(hit.all())):
+        s["live"][0] = 0
+    # the table of own rows
+    tbl = s["own_block"]
+    tbl[:, :n] = tbl[s["parent"], :n]
+    tbl[:, n] = np.arange(K, dtype=np.uint8)
+
+
+def beam_hypotheses_host(state):
+    """The pool of a finished search -> (ids, scores, flags): per pool entry, best first, its generated ids (int32; rebuilt from the
+    back-pointer logs: the entry ended at step t with `id` on the beam that sat in slot p after step t - 1), its fp32 score and whether
+    it is a finished hypothesis (an unfinished entry has no ids and HF's -1e9)."""
+    import numpy as np
+    out = []
+    for (t, p, tok), flag in zip(state["fin_end"].tolist(), state["fin_flag"].tolist()):
+        ids = []
+        if flag:
+            ids = [tok]
+            for u in range(t - 1, -1, -1):
+                ids.append(int(state["tok_log"][u][p]))
+                p = int(state["parent_log"][u][p])
+        out.append(np.array(ids[::-1], dtype=np.int32))
+    return out, np.array(state["fin_score"], dtype=np.float32), np.array(state["fin_flag"], dtype=np.int32)
+
+
+def beam_search_host(logprob_rows_fn, num_beams, V, eos_ids, max_new_tokens, length_penalty=1.0, early_stopping=False):
+    """HF's beam search for one prompt, driven by logprob_rows_fn(t, state) -> the [K, V] fp32 log-probability rows of the running beams
+    at step t (state["tok"] / state["parent"] say which beams those are).  Returns (ids, scores, flags, steps): beam_hypotheses_host of
+    the final pool and the number of steps run."""
+    import numpy as np
+    if early_stopping not in (False, True, "never") or isinstance(early_stopping, (int, float)) and not isinstance(early_stopping, bool):
+        raise ValueError(f"early_stopping = {early_stopping!r}: one of False, True, 'never'")
+    state = beam_state_host(num_beams, max_new_tokens)
+    len_pow = beam_len_pow(max_new_tokens, length_penalty)
+    M = beam_candidates(num_beams, len(set(eos_ids)))
+    t = 0
+    while state["live"][0]:
+        val, idx = beam_select_host(np.asarray(logprob_rows_fn(t, state), dtype=np.float32), state["running"], M)
+        beam_step_host(state, val, idx, V, eos_ids, max_new_tokens, len_pow, length_penalty, early_stopping)
+        t += 1
+    return (*beam_hypotheses_host(state), t)
 
 
 def philox4x32_10(counter4, key2):
@@ -1847,6 +2025,134 @@ class GreedyLoopGraph:
         if self.processors is not None and self.processors.want_logprobs:
             out += ([self.logp_log[b, :n_tok[b]].clone() for b in range(len(n_tok))],)
         return out
+
+
+BEAM_STATE = ("running", "fin_score", "fin_flag", "fin_end", "scal", "live", "tok", "parent", "tok_log", "parent_log", "own_block")
+
+
+class BeamLoopGraph:
+    """HF's beam search (GenerationMixin._beam_search: one prompt, do_sample=False, no logits processors, tokens only) with the token loop
+    on the device: GreedyLoopGraph's sibling.  The K beams are the K sequences of a cache whose prompt rows are stored once
+    (KVCache.set_shared(L, own_rows=max_new_tokens + 1)); a beam's own rows stay where they were appended and the cache's table own_block
+    says in which block each one lives, so no cache row is ever reordered.  One step is decoder_decode_row (attention through
+    mm355_attn_decode_shared_idx) -> `head` (final norm and lm_head into the static fp32 `logits`; no image head) ->
+    mm355_beam_select_rows_f32 (log-softmax statistics and the M best of the K * V accumulated scores) -> mm355_beam_advance (HF's
+    bookkeeping, the back-pointer logs, the new table and the next input rows: beam_step_host).  The step reads no host value: ONE hipGraph
+    per attention bound, replayed per token; set_variant("decode_graph", False) runs the same launches eagerly.  The host replays at most
+    max_new_tokens - 1 steps and reads `live` every `poll` steps (`host_reads` counts them, the final read of the results included).  A
+    finished search rides along: mm355_beam_advance writes nothing for it, so the result does not depend on `poll`.
+    head(x [K, h], logits_out f32 [K, C]).  run(x0) returns beam_hypotheses_host of the final pool."""
+
+    def __init__(self, layers, meta, cache, cos, sin, h, device, head, embed, C, max_new_tokens, eos_ids, length_penalty=1.0,
+                 early_stopping=False, poll=8):
+        eos = sorted(set(int(e) for e in eos_ids))
+        if len(eos) > ops.GREEDY_MAX_EOS:
+            raise ValueError(f"{len(eos)} eos ids: the device loop takes up to {ops.GREEDY_MAX_EOS}")
+        K = cache.batch
+        if not 1 <= K <= BEAM_MAX:
+            raise ValueError(f"{K} beams: the device beam loop takes 1 .. {BEAM_MAX}")
+        if C > embed.shape[0]:
+            raise ValueError(f"{C} logits over an embedding of {embed.shape[0]} rows: a candidate id would be no row of it")
+        if int(poll) < 1:
+            raise ValueError(f"mm355_greedy_poll_steps = {poll}: the live counter is read every poll >= 1 steps")
+        if early_stopping not in BEAM_EARLY_STOPPING or (isinstance(early_stopping, (int, float)) and not isinstance(early_stopping, bool)):
+            raise ValueError(f"early_stopping = {early_stopping!r}: one of False, True, 'never'")
+        self.max_new_tokens, self.poll, self.C = int(max_new_tokens), int(poll), int(C)
+        self.M = beam_candidates(K, len(eos))
+        if self.max_new_tokens < 1 or self.M > K * self.C:
+            raise ValueError(f"max_new_tokens = {max_new_tokens} must be >= 1 and {K} x {C} logits must hold the {self.M} candidates of a step")
+        if cache.own_block is None or cache.own_block.shape[1] < self.max_new_tokens:
+            raise ValueError("the beam loop runs on a cache with a table of own rows: KVCache.set_shared(L, own_rows=max_new_tokens + 1)")
+        self.args = (layers, meta, cache, cos, sin)
+        self.cache, self.head, self.embed = cache, head, embed
+        self.eos, self.length_penalty, self.early_stopping = eos, float(length_penalty), BEAM_EARLY_STOPPING[early_stopping]
+        host = beam_state_host(K, self.max_new_tokens)
+        self.state = {n: (cache.own_block if n == "own_block" else torch.from_numpy(host[n]).to(device)) for n in BEAM_STATE}
+        self.len_pow = torch.from_numpy(beam_len_pow(self.max_new_tokens, float(length_penalty))).to(device)
+        self.x_in = torch.zeros((K, h), device=device, dtype=BF16)
+        self.logits = torch.empty((K, self.C), device=device, dtype=torch.float32)
+        self.stats = torch.zeros((K, 2), device=device, dtype=torch.float32)
+        self.cand_val = torch.zeros(self.M, device=device, dtype=torch.float32)
+        self.cand_idx = torch.zeros(self.M, device=device, dtype=torch.int32)
+        self.sel_ws = ops.beam_select_rows_ws(K, self.C, self.M, device)
+        self.graphs = {}                                     # kv bound -> graph
+        self.capture_ok = VARIANTS["decode_graph"]
+        self.host_reads = 0
+        self.steps = 0
+        self.on_tail = None                                  # (tests: called after every tail with the loop)
+
+    @property
+    def live(self):
+        return self.state["live"]
+
+    def _tail(self, x):
+        self.head(x, self.logits)
+        ops.beam_select_rows(self.logits, self.state["running"], self.M, self.stats, self.cand_val, self.cand_idx, self.sel_ws)
+        ops.beam_advance(self.cand_val, self.cand_idx, self.C, self.state, self.len_pow, self.max_new_tokens, self.length_penalty,
+                         self.early_stopping, self.eos, embed=self.embed, x_in=self.x_in)
+
+    def _launches(self, bound=None):
+        self._tail(decoder_decode_row(self.x_in, *self.args, kv_bound=bound))
+
+    def _capture(self, bound):
+        cache = self.cache
+        keep = list(cache.lengths)
+        live = self.live.clone()
+        try:
+            self.live.fill_(0)                                   # the warm-up runs for real: a search that is not live logs and feeds nothing
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self._launches(bound)
+            torch.cuda.current_stream().wait_stream(side)
+            cache.set_lengths(keep)                              # (the warm-up's scratch cache row is overwritten by the next real step)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._launches(bound)
+            cache.lengths = keep                                 # capture records, it does not run: host mirror unchanged
+            self.graphs[bound] = g
+        except Exception as e:                                   # pragma: no cover - depends on the runtime
+            import warnings
+            warnings.warn(f"hipGraph capture of the beam step failed ({e!r}); using eager launches")
+            self.capture_ok = False
+            self.graphs = {}
+            cache.set_lengths(keep)
+        self.live.copy_(live)
+
+    def _step(self):
+        if self.capture_ok:
+            bound = decode_kv_bound(self.cache)
+            if bound not in self.graphs:
+                self._capture(bound)
+        if not self.capture_ok:
+            return self._launches()
+        if self.cache.length >= self.cache.max_len:
+            raise ValueError(f"KV cache full ({self.cache.max_len} rows)")
+        self.graphs[bound].replay()
+        self.cache.lengths = [n + 1 for n in self.cache.lengths]
+
+    def run(self, x0):
+        """x0 [K, h]: the prompt pass's last hidden row, K times (pre final norm): HF's step 0, whose running scores (0, -1e9, ...) let
+        only the first beam through.  Then up to max_new_tokens - 1 steps.  Returns (ids, scores, flags): per pool entry, best first,
+        its generated int32 ids (NumPy), and the fp32 scores and finished flags of the pool."""
+        self._tail(x0.contiguous())
+        if self.on_tail is not None:
+            self.on_tail(self)
+        for s in range(self.max_new_tokens - 1):
+            self._step()
+            self.steps += 1
+            if self.on_tail is not None:
+                self.on_tail(self)
+            if self.steps % self.poll == 0 and s + 2 < self.max_new_tokens:
+                self.host_reads += 1
+                if int(self.live.item()) == 0:
+                    break
+        self.host_reads += 1
+        host = {n: t.cpu().numpy() for n, t in self.state.items()}
+        if host["live"][0]:                                      # pragma: no cover - the step that generates id max_new_tokens ends every search
+            raise RuntimeError(f"beam loop: the search is still live after {self.steps} steps (scal {host['scal'].tolist()})")
+        self.final = host
+        return beam_hypotheses_host(host)
 
 
 class GeluFn(Function):

@@ -1015,6 +1015,95 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
             return (ids, embs, logp[0]) if output_image else (ids, logp[0])
         return (ids, embs) if output_image else ids
 
+    # ------------------------------------------------------------------ beam search, token loop on the device
+    def _head_text_rows(self, x, logits_out):
+        """final norm + lm_head -> fp32 logits into `logits_out`: the text-only head of the beam loop (no image head is run)"""
+        self._lm_head_into(self.model.norm(x).contiguous(), logits_out)
+
+    @torch.no_grad()
+    def beam_decode(self, position_ids, attention_mask, inputs_embeds, num_beams, eos_token_id=(128001, 128009), max_new_tokens=1024,
+                    length_penalty=1.0, early_stopping=False, num_return_sequences=None, output_scores=False, do_sample=None,
+                    use_cache=None, output_image=False, repetition_penalty=None, min_new_tokens=None, suppress_tokens=None,
+                    output_logprobs=False):
+        """HF's beam search (GenerationMixin._beam_search with do_sample=False and no logits processors: the hypotheses of
+        generate(use_customize_greedy=False, num_beams=K)) for ONE prompt with the token loop on the device (functional.BeamLoopGraph).
+        The prompt (inputs_embeds [1, L, h] bf16; an attention_mask may left-pad it) runs through the decoder once and its cache rows are
+        stored and read once for all K = num_beams beams (mm355_attn_decode_shared_idx); a beam's own rows are never moved, a table says
+        where they live.  Per token: one captured step, one pass over the weights, no host read (config.mm355_greedy_poll_steps as for
+        greedy_decode).  Tokens only: <im_start> is an ordinary id.  Returns the num_return_sequences (default 1) best hypotheses, best
+        first, as int32 id tensors -- the generated ids up to and including the eos id that ended them, unpadded; with output_scores=True
+        (ids, scores), scores the fp32 `sequences_scores` (sum of log-probabilities / length ** length_penalty).  length_penalty and
+        early_stopping (False, True or "never") are HF's.  w8 / w4 weights and the FP8 cache work as in greedy_decode.
+        Refused by name before any device work -- ValueError: num_beams no integer in [2, 8], more than one prompt, num_return_sequences
+        > num_beams, more eos ids than the device loop takes, a length_penalty that is not finite, another early_stopping,
+        max_new_tokens < 1, fewer logits than a step keeps candidates; NotImplementedError: use_cache=False, do_sample, any logits
+        processor (repetition_penalty, min_new_tokens, suppress_tokens, output_logprobs), output_image=True, and a head shape
+        mm355_attn_decode_shared does not take or set_variant("shared_prefix_attn", False) -- there is no fan-out fallback: use the HF
+        path, generate(use_customize_greedy=False, num_beams=K)."""
+        try:
+            K = -1 if isinstance(num_beams, bool) else operator.index(num_beams)
+        except TypeError:
+            K = -1
+        if not 2 <= K <= F.BEAM_MAX:
+            raise ValueError(f"beam_decode: num_beams = {num_beams!r} must be an integer in [2, {F.BEAM_MAX}] (1 beam is greedy_decode)")
+        if inputs_embeds.shape[0] != 1:
+            raise ValueError(f"beam_decode takes one prompt, got {inputs_embeds.shape[0]}")
+        n_ret = self._copies_of(num_return_sequences)
+        if n_ret > K:
+            raise ValueError(f"beam_decode: num_return_sequences = {n_ret} exceeds num_beams = {K}: the pool holds num_beams hypotheses")
+        eos = sorted(set(int(e) for e in ([] if eos_token_id is None else
+                                          [eos_token_id] if isinstance(eos_token_id, int) else eos_token_id)))
+        if len(eos) > ops.GREEDY_MAX_EOS:
+            raise ValueError(f"beam_decode: {len(eos)} eos ids: the device loop takes up to {ops.GREEDY_MAX_EOS}")
+        try:
+            length_penalty = float(length_penalty)
+        except (TypeError, ValueError):
+            length_penalty = float("nan")
+        if not math.isfinite(length_penalty):
+            raise ValueError("beam_decode: length_penalty must be a finite number")
+        if early_stopping not in (False, True, "never") or (isinstance(early_stopping, (int, float)) and not isinstance(early_stopping, bool)):
+            raise ValueError(f"beam_decode: early_stopping = {early_stopping!r} must be False, True or 'never'")
+        if isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int) or max_new_tokens < 1:
+            raise ValueError(f"beam_decode: max_new_tokens = {max_new_tokens!r} must be an integer >= 1")
+        V = self.w8_lm_head[0].shape[0] if self.w8_lm_head is not None else self.lm_head.weight.shape[0]
+        M = F.beam_candidates(K, len(eos))
+        if V < M:
+            raise ValueError(f"beam_decode: {V} logits are fewer than the {M} candidates a step of {K} beams with {len(eos)} eos ids keeps")
+        if not (use_cache is None or use_cache):
+            raise NotImplementedError("beam_decode(use_cache=False): the beams live in the KV cache (use_cache=True)")
+        if do_sample:
+            raise NotImplementedError("beam_decode(do_sample=True): beam sampling is not part of the device beam loop")
+        if (repetition_penalty not in (None, 1, 1.0) or min_new_tokens not in (None, 0) or (suppress_tokens is not None and len(suppress_tokens))
+                or output_logprobs):
+            raise NotImplementedError("beam_decode(repetition_penalty / min_new_tokens / suppress_tokens / output_logprobs): logits "
+                                      "processors are not part of the device beam loop (HF applies them after the log-softmax)")
+        if output_image:
+            raise NotImplementedError("beam_decode(output_image=True): the beam loop is token-only, image rows are not generated under beams")
+        cfg = self.config
+        hf_path = "use the HF path: generate(use_customize_greedy=False, num_beams=K)"
+        if not ops.attn_decode_shared_supported(cfg.num_attention_heads, cfg.num_key_value_heads, _head_dim(cfg)):
+            raise NotImplementedError(f"beam_decode: mm355_attn_decode_shared does not take the head shape Hq={cfg.num_attention_heads} "
+                                      f"Hkv={cfg.num_key_value_heads} d={_head_dim(cfg)} and there is no fan-out fallback; {hf_path}")
+        if not F.VARIANTS["shared_prefix_attn"]:
+            raise NotImplementedError(f'beam_decode with set_variant("shared_prefix_attn", False): the beams share the prompt\'s cache rows '
+                                      f"and there is no fan-out fallback; {hf_path}")
+        if inputs_embeds.dtype != BF16:
+            raise TypeError(f"inputs_embeds must be bf16, got {inputs_embeds.dtype}")
+        dev = inputs_embeds.device
+        _, n, h = inputs_embeds.shape
+        pads = self._left_pads(attention_mask, 1, n)
+        F.params_ready(None)
+        x2d = inputs_embeds[0, pads[0]:].reshape(n - pads[0], h)
+        cache = HipKVCache(capacity=x2d.shape[0] + max_new_tokens + 2)
+        x0 = self._prefill_shared(x2d, cache, K, chunk=self._prefill_chunk_rows(), own_rows=max_new_tokens + 1)
+        loop = F.BeamLoopGraph(self.model.layers, cache.meta, cache.kv, cache.meta.cos, cache.meta.sin, h, dev, self._head_text_rows,
+                               self.model.embed_tokens.weight.data, V, max_new_tokens, eos, length_penalty, early_stopping,
+                               poll=getattr(self.config, "mm355_greedy_poll_steps", 8))
+        self._beam_loop = loop                                # (tools / tests: steps, host_reads, the final state)
+        ids, scores, _ = loop.run(x0)
+        out = [torch.from_numpy(i).to(dev) for i in ids[:n_ret]]
+        return (out, torch.from_numpy(scores[:n_ret].copy()).to(dev)) if output_scores else out
+
     # ------------------------------------------------------------------ HF generate() on the decode kernels (reference :711-738)
     def _prefill_batch(self, seqs, cache, stepper=True, chunk=None):
         """Prompt pass of a batch: seqs = one [L_b, h] tensor of prompt rows per sequence (padding already stripped) -> their hidden rows
@@ -1053,12 +1142,13 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
             cache.stepper = F.DecodeStepGraph(self.model.layers, meta, cache.kv, cos, sin, h, dev)
         return out
 
-    def _prefill_shared(self, x2d, cache, n, chunk=None):
+    def _prefill_shared(self, x2d, cache, n, chunk=None, own_rows=None):
         """Prompt pass of n continuations of ONE prompt x2d [L, h]: the prompt runs once into sequence 0 of a cache of n sequences; returns
         the prompt's last hidden row (pre final norm) n times, [n, h].  Afterwards every sequence holds L rows and, on the shared route
         (functional.VARIANTS["shared_prefix_attn"] and a head shape mm355_attn_decode_shared takes), rows [0, L) of sequence 0 are every
         sequence's first rows (KVCache.set_shared); else they are copied into every sequence's block (KVCache.copy_prefix) and the step
-        runs on the batch's attention."""
+        runs on the batch's attention.  own_rows (beam_decode, which has checked that the shared route applies): the columns of the
+        table of own rows, KVCache.set_shared(L, own_rows=...)."""
         dev = x2d.device
         L, h = int(x2d.shape[0]), x2d.shape[1]
         cap = cache.capacity if cache.capacity is not None else L + 1024 + 2
@@ -1078,8 +1168,9 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
             rows = F.decoder_prefill_chunked(x2d.contiguous(), self.model.layers, mb, kv, chunk, row=0)
         if F.VARIANTS["shared_prefix_attn"] and ops.attn_decode_shared_supported(meta.Hq, meta.Hkv, meta.d):
             kv.set_lengths([L] * n)
-            kv.set_shared(L)
+            kv.set_shared(L, own_rows=own_rows)
         else:
+            assert own_rows is None
             kv.copy_prefix(L)
             kv.set_lengths([L] * n)
         return rows[-1:].expand(n, h).contiguous()
@@ -1199,11 +1290,16 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
                  image_embeds=None, **kwargs):
         position_ids = kwargs.pop("position_ids", None)
         attention_mask = kwargs.pop("attention_mask", None)
+        device_beam_search = kwargs.pop("device_beam_search", False)
         if images is not None or image_embeds is not None:
             (_, position_ids, attention_mask, _, inputs_embeds, _, _, _) = self.prepare_inputs_labels_for_multimodal(
                 inputs, position_ids, attention_mask, None, None, images, image_sizes=image_sizes, image_embeds=image_embeds)
         else:
             inputs_embeds = self.get_model().embed_tokens(inputs)
+        if device_beam_search:
+            # beam search with the token loop on the device (beam_decode): HF's hypotheses without HF's per-token host loop and cache reorder
+            return self.beam_decode(position_ids=position_ids, attention_mask=attention_mask, inputs_embeds=inputs_embeds,
+                                    output_image=output_image, **kwargs)
         if not use_customize_greedy:
             # reference :711-717: `super().generate(position_ids=..., attention_mask=..., inputs_embeds=..., **kwargs)` -- HF's sampling
             # / greedy search driving forward() with a cache.  Here the cache is a HipKVCache (decode kernels + hipGraph replay).

@@ -777,18 +777,35 @@ def _shared_args(q, kv_lens, shared_len, max_kv_len, shared_rows, rows, Hq, Hkv,
     return B, pq, ldq, out, po, ldo, ws, (0 if ws is None else ws.numel())
 
 
-def attn_decode_shared(q, k_shared, v_shared, k_cache, v_cache, kv_lens, shared_len, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None):
+def _own_block(own_block, B):
+    """the table of mm355_attn_decode_shared_idx: uint8 [>= B, columns] on the device, rows contiguous -> (pointer, row stride)"""
+    assert own_block.dtype == torch.uint8 and own_block.dim() == 2 and own_block.stride(1) == 1 and own_block.shape[0] >= B and B <= 255
+    assert own_block.shape[1] >= 1
+    return own_block.data_ptr(), own_block.stride(0)
+
+
+def attn_decode_shared(q, k_shared, v_shared, k_cache, v_cache, kv_lens, shared_len, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None,
+                       own_block=None):
     """The decode step's attention for B sequences whose first shared_len cached rows are the same rows, stored once
     (mm355_attn_decode_shared): q [B, Hq*d] bf16, already rotated (may be a column block of a wider tensor); k_shared / v_shared [>= shared_len,
     Hkv*d] bf16; k_cache / v_cache [B, rows, Hkv*d] bf16 whose rows [shared_len, kv_lens[b]) are sequence b's own; kv_lens int32 [B] on the
-    device, kv_lens[b] >= shared_len; shared_len and max_kv_len host bounds.  Rows [0, shared_len) of the own blocks are never read."""
-    _chk_dev(q, k_shared, v_shared, k_cache, v_cache, kv_lens, out)
+    device, kv_lens[b] >= shared_len; shared_len and max_kv_len host bounds.  Rows [0, shared_len) of the own blocks are never read.
+    own_block (uint8 [B, columns] on the device; the beams of a beam search): own row j of query b is row j of block own_block[b, j -
+    shared_len] (mm355_attn_decode_shared_idx); None is the identity."""
+    _chk_dev(q, k_shared, v_shared, k_cache, v_cache, kv_lens, out, own_block)
     assert k_cache.dim() == 3 and k_cache.dtype == BF16 and k_cache.shape == v_cache.shape and k_cache.stride(2) == 1
     assert v_cache.stride() == k_cache.stride() and k_cache.shape[2] == Hkv * d and k_cache.shape[0] >= kv_lens.shape[0]
     assert k_shared.dim() == 2 and k_shared.dtype == BF16 and k_shared.shape == v_shared.shape and k_shared.stride() == v_shared.stride()
     assert k_shared.stride(1) == 1 and k_shared.shape[1] == Hkv * d
     B, pq, ldq, out, po, ldo, ws, n_ws = _shared_args(q, kv_lens, shared_len, max_kv_len, k_shared.shape[0], k_cache.shape[1], Hq, Hkv, d, out,
                                                       workspace)
+    if own_block is not None:
+        pt, ldt = _own_block(own_block, B)
+        _lib.check(_L().mm355_attn_decode_shared_idx(pq, ldq, k_shared.data_ptr(), v_shared.data_ptr(), k_shared.stride(0), k_cache.data_ptr(),
+                                                     v_cache.data_ptr(), k_cache.stride(1), k_cache.stride(0), kv_lens.data_ptr(), pt, ldt,
+                                                     shared_len, max_kv_len, po, ldo, B, Hq, Hkv, d, scale, _p(ws), n_ws, _stream()),
+                   f"mm355_attn_decode_shared_idx B={B} Hq={Hq} Hkv={Hkv} d={d} shared_len={shared_len}")
+        return out
     _lib.check(_L().mm355_attn_decode_shared(pq, ldq, k_shared.data_ptr(), v_shared.data_ptr(), k_shared.stride(0), k_cache.data_ptr(),
                                              v_cache.data_ptr(), k_cache.stride(1), k_cache.stride(0), kv_lens.data_ptr(), shared_len, max_kv_len,
                                              po, ldo, B, Hq, Hkv, d, scale, _p(ws), n_ws, _stream()),
@@ -797,11 +814,11 @@ def attn_decode_shared(q, k_shared, v_shared, k_cache, v_cache, kv_lens, shared_
 
 
 def attn_decode_shared_f8(q, k_shared, v_shared, k_shared_scale, v_shared_scale, k8, v8, k_scale, v_scale, kv_lens, shared_len, max_kv_len, Hq,
-                          Hkv, d, scale, out=None, workspace=None):
+                          Hkv, d, scale, out=None, workspace=None, own_block=None):
     """attn_decode_shared() over e4m3 bytes: k_shared / v_shared [>= shared_len, Hkv*d] uint8 with scales [>= shared_len, Hkv] f32, k8 / v8 [B,
     rows, Hkv*d] uint8 with k_scale / v_scale [B, rows, Hkv] f32 (mm355_attn_decode_shared_f8): equal to attn_decode_shared() on dequant_kv8()
-    of the same bytes bit for bit."""
-    _chk_dev(q, k_shared, v_shared, k_shared_scale, v_shared_scale, k8, v8, k_scale, v_scale, kv_lens, out)
+    of the same bytes bit for bit.  own_block: as for attn_decode_shared (mm355_attn_decode_shared_idx_f8), bytes and scales follow it."""
+    _chk_dev(q, k_shared, v_shared, k_shared_scale, v_shared_scale, k8, v8, k_scale, v_scale, kv_lens, out, own_block)
     assert k8.shape == v8.shape and k8.stride() == v8.stride() and k_scale.stride() == v_scale.stride() and k8.shape[0] >= kv_lens.shape[0]
     ldb, bsb, ldsc, bssc = _kv8_cache(k8, k_scale, Hkv, d)
     _kv8_cache(v8, v_scale, Hkv, d)
@@ -810,6 +827,15 @@ def attn_decode_shared_f8(q, k_shared, v_shared, k_shared_scale, v_shared_scale,
     assert k_shared_scale.dtype == torch.float32 and tuple(k_shared_scale.shape) == (k_shared.shape[0], Hkv) and k_shared_scale.stride(1) == 1
     assert v_shared_scale.dtype == torch.float32 and v_shared_scale.shape == k_shared_scale.shape and v_shared_scale.stride() == k_shared_scale.stride()
     B, pq, ldq, out, po, ldo, ws, n_ws = _shared_args(q, kv_lens, shared_len, max_kv_len, k_shared.shape[0], k8.shape[1], Hq, Hkv, d, out, workspace)
+    if own_block is not None:
+        pt, ldt = _own_block(own_block, B)
+        _lib.check(_L().mm355_attn_decode_shared_idx_f8(pq, ldq, k_shared.data_ptr(), v_shared.data_ptr(), k_shared.stride(0),
+                                                        k_shared_scale.data_ptr(), v_shared_scale.data_ptr(), k_shared_scale.stride(0),
+                                                        k8.data_ptr(), v8.data_ptr(), ldb, bsb, k_scale.data_ptr(), v_scale.data_ptr(), ldsc,
+                                                        bssc, KV8_E4M3, kv_lens.data_ptr(), pt, ldt, shared_len, max_kv_len, po, ldo, B, Hq,
+                                                        Hkv, d, scale, _p(ws), n_ws, _stream()),
+                   f"mm355_attn_decode_shared_idx_f8 B={B} Hq={Hq} Hkv={Hkv} d={d} shared_len={shared_len}")
+        return out
     _lib.check(_L().mm355_attn_decode_shared_f8(pq, ldq, k_shared.data_ptr(), v_shared.data_ptr(), k_shared.stride(0), k_shared_scale.data_ptr(),
                                                 v_shared_scale.data_ptr(), k_shared_scale.stride(0), k8.data_ptr(), v8.data_ptr(), ldb, bsb,
                                                 k_scale.data_ptr(), v_scale.data_ptr(), ldsc, bssc, KV8_E4M3, kv_lens.data_ptr(), shared_len,
@@ -1399,6 +1425,80 @@ def greedy_advance(tok, C, state, live, embed, fed, pred_z, x_in, tok_log, z_log
                                          tok_log.data_ptr(), tok_log.shape[1], z_log.data_ptr(), z_log.shape[1], int(start_id), int(end_id),
                                          int(num_image_tokens), int(max_new_tokens), _lib.ctypes.addressof(arr), len(eos), _stream()),
                f"mm355_greedy_advance B={B} C={C} eos={len(eos)}")
+
+
+# ------------------------------------------------------------------------------------------------ beam search in the device loop (csrc/beam.hip)
+
+BEAM_MAX = 8                                                 # MM355_BEAM_MAX
+
+
+def beam_select_rows_ws(K, V, M, device):
+    """the workspace of beam_select_rows (mm355_beam_select_rows_ws_bytes)"""
+    return torch.empty(int(_L().mm355_beam_select_rows_ws_bytes(K, V, M)), device=device, dtype=torch.uint8)
+
+
+def beam_select_rows(x2d, running, M, stats=None, cand_val=None, cand_idx=None, ws=None):
+    """Step 1 of a beam step on the contiguous fp32 logits x2d [K, V] and the beams' scores running [K] (mm355_beam_select_rows_f32; the
+    model of it is functional.beam_select_host on beam_logprob_rows_host of the statistics): -> (stats [K, 2] = (row maximum, ln sum
+    exp(x - maximum)), cand_val [M] fp32, cand_idx [M] int32): the M best of ((x - m) - lse) + running over all K * V entries, sorted by
+    value descending, then flat index ascending."""
+    _chk_dev(x2d, running, stats, cand_val, cand_idx, ws)
+    assert x2d.dim() == 2 and x2d.is_contiguous() and x2d.dtype == torch.float32
+    K, V = x2d.shape
+    M = int(M)
+    dev = x2d.device
+    assert running.dtype == torch.float32 and running.is_contiguous() and running.numel() == K
+    stats = torch.empty((K, 2), device=dev, dtype=torch.float32) if stats is None else stats
+    cand_val = torch.empty(M, device=dev, dtype=torch.float32) if cand_val is None else cand_val
+    cand_idx = torch.empty(M, device=dev, dtype=torch.int32) if cand_idx is None else cand_idx
+    ws = beam_select_rows_ws(K, V, M, dev) if ws is None else ws
+    assert stats.dtype == torch.float32 and stats.is_contiguous() and tuple(stats.shape) == (K, 2)
+    assert cand_val.dtype == torch.float32 and cand_val.is_contiguous() and cand_val.numel() == M
+    assert cand_idx.dtype == torch.int32 and cand_idx.is_contiguous() and cand_idx.numel() == M
+    _lib.check(_L().mm355_beam_select_rows_f32(x2d.data_ptr(), K, V, running.data_ptr(), M, stats.data_ptr(), cand_val.data_ptr(),
+                                               cand_idx.data_ptr(), _p(ws) if ws.numel() else 0, ws.numel() * ws.element_size(), _stream()),
+               f"mm355_beam_select_rows_f32 K={K} V={V} M={M}")
+    return stats, cand_val, cand_idx
+
+
+def beam_advance(cand_val, cand_idx, V, state, len_pow, max_new_tokens, length_penalty, early_stopping, eos_ids, embed=None, x_in=None):
+    """Steps 2 - 6 of a beam step for the M sorted candidates on device-resident state (mm355_beam_advance; the model of it, bit for bit,
+    is functional.beam_step_host).  state: a dict of device tensors in functional.beam_state_host's layout (running, fin_score fp32 [K];
+    fin_flag [K], fin_end [K, 3], scal [2], live [1], tok, parent [K], tok_log, parent_log [cap, K] int32; own_block uint8 [K, columns] or
+    None); len_pow fp32 [max_new_tokens] on the device (functional.beam_len_pow); early_stopping 0 / 1 / 2 (False / True / "never");
+    embed [rows >= V, h] and x_in [K, h]: the next input rows, or both None."""
+    s = state
+    tbl = s.get("own_block")
+    _chk_dev(cand_val, cand_idx, len_pow, embed, x_in, *[t for t in s.values() if t is not None])
+    K, M = s["running"].numel(), cand_val.numel()
+    assert cand_val.dtype == torch.float32 and cand_idx.dtype == torch.int32 and cand_idx.numel() == M
+    assert cand_val.is_contiguous() and cand_idx.is_contiguous()
+    for n, dt, shape in (("running", torch.float32, (K,)), ("fin_score", torch.float32, (K,)), ("fin_flag", torch.int32, (K,)),
+                         ("fin_end", torch.int32, (K, 3)), ("scal", torch.int32, (2,)), ("live", torch.int32, (1,)),
+                         ("tok", torch.int32, (K,)), ("parent", torch.int32, (K,))):
+        assert s[n].dtype == dt and tuple(s[n].shape) == shape and s[n].is_contiguous(), n
+    cap = s["tok_log"].shape[0]
+    for n in ("tok_log", "parent_log"):
+        assert s[n].dtype == torch.int32 and tuple(s[n].shape) == (cap, K) and s[n].is_contiguous(), n
+    assert len_pow.dtype == torch.float32 and len_pow.is_contiguous() and len_pow.numel() >= int(max_new_tokens)
+    pt, ldt = (0, 0)
+    if tbl is not None:
+        assert tbl.dtype == torch.uint8 and tbl.dim() == 2 and tbl.stride(1) == 1 and tbl.shape[0] == K
+        pt, ldt = tbl.data_ptr(), tbl.stride(0)
+        assert tbl.shape[1] >= int(max_new_tokens)
+    pe = lde = rows = px = ldx = h = 0
+    if x_in is not None:
+        pe, rows, h, lde = _rows2d(embed)
+        px, Kx, hx, ldx = _rows2d(x_in)
+        assert (Kx, hx) == (K, h) and embed.dtype == BF16 and x_in.dtype == BF16
+    eos = [int(e) for e in eos_ids]
+    arr = (_lib.ctypes.c_int32 * max(len(eos), 1))(*eos)
+    _lib.check(_L().mm355_beam_advance(cand_val.data_ptr(), cand_idx.data_ptr(), K, M, int(V), s["running"].data_ptr(), s["fin_score"].data_ptr(),
+                                       s["fin_flag"].data_ptr(), s["fin_end"].data_ptr(), s["scal"].data_ptr(), s["live"].data_ptr(),
+                                       s["tok"].data_ptr(), s["parent"].data_ptr(), s["tok_log"].data_ptr(), s["parent_log"].data_ptr(), cap,
+                                       pt, ldt, pe, lde, rows, px, ldx, h, len_pow.data_ptr(), int(max_new_tokens), float(length_penalty),
+                                       int(early_stopping), _lib.ctypes.addressof(arr), len(eos), _stream()),
+               f"mm355_beam_advance K={K} M={M} V={V} eos={len(eos)}")
 
 
 # ------------------------------------------------------------------------------------------------ logits processors, log-probabilities (csrc/logits.hip)
