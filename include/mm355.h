@@ -616,6 +616,40 @@ int mm355_attn_decode_shared_idx_f8(const mm355_bf16* q, int64_t ld_q, const uin
                                     void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Extending by n rows per sequence a cache of B sequences whose first shared_len rows are the SAME rows, stored once
+ * (csrc/attn_extend_shared.hip): B different questions over one context -- the pass between the prefix and the decode loop.  The union of
+ * mm355_attn_extend and mm355_attn_decode_shared.
+ *   attn_extend_shared: q [B*n][Hq*d] (ld_q), ALREADY rotated, row (b, i) at b * n + i; k_shared / v_shared [shared_len][Hkv*d] (row stride
+ *         ld_shared), one copy; k_cache / v_cache [B][rows][Hkv*d] as mm355_attn_decode takes them; past[B] int32 on the device; o
+ *         [B*n][Hq*d] (ld_o).  The own block of sequence b already holds the new rows at past[b] .. past[b] + n - 1 (the append comes first);
+ *         past[b] >= shared_len is the caller's promise.  Row (b, i) attends the keys j in [0, shared_len) from the shared copy and then the
+ *         keys j in [shared_len, past[b] + i] from row j of block b (the own rows keep their absolute index).  o = softmax(scale * q K^T) V
+ *         with the softmax in fp32 and the scale applied on the fp32 side.  Right for n == 1 (mm355_attn_decode_shared's case with kv_lens =
+ *         past + 1), shared_len == 0 (mm355_attn_extend's case) and past[b] == shared_len (no earlier own rows).  Never read, whatever past[]
+ *         says: rows [0, shared_len) of any own block, shared rows >= shared_len, own rows >= min(past[b] + n, max_kv_len).  shared_len, n and
+ *         max_kv_len (shared_len <= max_kv_len <= rows) are host launch parameters.  Shared rows: mm355_attn_decode_shared's shared part with
+ *         packed row (b * n + i) * G + g (G = Hq / Hkv), so a shared K / V tile is read once per KV head and 64 / G query rows of any
+ *         sequence, the key tiles dealt to several workgroups; own rows: workgroups per (sequence, KV head, 64 packed rows of that
+ *         sequence) in the same launch, with mm355_attn_extend's per-row key limit; a second launch merges the partials.  The split is a
+ *         function of (B, n, Hq, Hkv, shared_len) alone: the same arguments give the same bits.  The workspace
+ *         (mm355_attn_extend_shared_ws_floats floats, 16-byte aligned, never 0 for valid arguments) is always needed.
+ *   attn_extend_shared_f8: the same over e4m3 bytes and scales for both parts (as mm355_attn_decode_shared_f8 takes them), widened to bf16 on
+ *         the way into LDS: equal to mm355_attn_extend_shared on the dequantised cache bit for bit.
+ *   Before any launch: what mm355_attn_decode_shared refuses, with the same codes, and n <= 0 or n > max_kv_len: MM355_EINVAL.
+ * ------------------------------------------------------------------------------------------------ */
+int64_t mm355_attn_extend_shared_ws_floats(int64_t B, int64_t n, int64_t Hq, int64_t Hkv, int64_t d, int64_t shared_len, int64_t max_kv_len);
+int mm355_attn_extend_shared(const mm355_bf16* q, int64_t ld_q, const mm355_bf16* k_shared, const mm355_bf16* v_shared, int64_t ld_shared,
+                             const mm355_bf16* k_cache, const mm355_bf16* v_cache, int64_t ld_kv, int64_t batch_stride_kv,
+                             const int32_t* past, int64_t n, int64_t shared_len, int64_t max_kv_len, mm355_bf16* o, int64_t ld_o, int64_t B,
+                             int64_t Hq, int64_t Hkv, int64_t d, float scale, float* workspace, int64_t workspace_floats, void* stream);
+int mm355_attn_extend_shared_f8(const mm355_bf16* q, int64_t ld_q, const uint8_t* k_shared, const uint8_t* v_shared, int64_t ld_shared_bytes,
+                                const float* k_shared_scale, const float* v_shared_scale, int64_t ld_shared_scale, const uint8_t* k_cache,
+                                const uint8_t* v_cache, int64_t ld_kv_bytes, int64_t batch_stride_kv_bytes, const float* k_scale,
+                                const float* v_scale, int64_t ld_scale, int64_t batch_stride_scale, int fmt, const int32_t* past, int64_t n,
+                                int64_t shared_len, int64_t max_kv_len, mm355_bf16* o, int64_t ld_o, int64_t B, int64_t Hq, int64_t Hkv,
+                                int64_t d, float scale, float* workspace, int64_t workspace_floats, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Elementwise: SwiGLU (HF LlamaMLP; K12), GELU (projector / vision_head), scaling helpers.
  * gu = [M][2I] with gate in columns [0,I) and up in [I,2I).
  * ------------------------------------------------------------------------------------------------ */

@@ -40,12 +40,7 @@ Plan make_plan(int64_t B, int64_t n, int64_t Hq, int64_t Hkv, int64_t max_kv_len
     p.nqt = (p.R + 63) / 64;
     p.rpad = (int64_t)p.nqt * 64;
     const int64_t nwg = B * Hkv * p.nqt;
-    const int ktiles = (int)((max_kv_len + 63) / 64);
-    int ns = 1;
-    if (nwg < 128) ns = (int)std::min<int64_t>(std::max(1, ktiles / 4), (256 + nwg - 1) / nwg);
-    ns = std::min(ns, 64);
-    p.tps = (ktiles + ns - 1) / ns;
-    p.nsplit = (ktiles + p.tps - 1) / p.tps;
+    key_runs(nwg, (int)((max_kv_len + 63) / 64), p.nsplit, p.tps);
     return p;
 }
 

@@ -1,10 +1,22 @@
-// What attn_extend.hip and attn_decode_shared.hip share on top of attn2.h: the K / V tile mover (bf16 and e4m3 cache), one 64-key step of the
-// "swapped" online softmax (S^T = K Q^T, O^T += V^T P^T, log2 domain, deferred rescale) and the fold of per-key-run partials.
+// What attn_extend.hip, attn_decode_shared.hip and attn_extend_shared.hip share on top of attn2.h: the K / V tile mover (bf16 and e4m3 cache),
+// one 64-key step of the "swapped" online softmax (S^T = K Q^T, O^T += V^T P^T, log2 domain, deferred rescale), the fold of per-key-run
+// partials and the host rule that deals the key tiles to runs.
 #pragma once
 #include "attn2.h"
+#include <algorithm>
 
 namespace attn_tile {
 using namespace attn2;
+
+// The key runs of a launch (host): `ktiles` 64-key tiles are dealt to nsplit workgroups in contiguous runs of tps tiles.  One run while the
+// nwg workgroups without a split give every other CU one; else enough runs of >= 4 tiles to reach about one workgroup per CU.
+inline void key_runs(int64_t nwg, int ktiles, int& nsplit, int& tps) {
+    int ns = 1;
+    if (nwg < 128) ns = (int)std::min<int64_t>(std::max(1, ktiles / 4), (256 + nwg - 1) / nwg);
+    ns = std::min(ns, 64);
+    tps = (ktiles + ns - 1) / ns;
+    nsplit = (ktiles + tps - 1) / tps;
+}
 
 template <int NV, bool F8> struct Stage;
 template <int NV> struct Stage<NV, false> { u32x4 r[NV]; };

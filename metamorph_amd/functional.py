@@ -55,7 +55,12 @@ VARIANTS = {"fuse_swiglu": True, "fuse_rope": True, "fuse_swiglu_bwd": True, "de
             # n continuations of one prompt (greedy_decode(num_return_sequences=n)): the prompt's cache rows stored once in sequence 0 and read
             # once per KV head and step by mm355_attn_decode_shared (KVCache.set_shared); off, or where that kernel does not take the shape:
             # the rows are copied into every sequence's block and the step runs on mm355_attn_decode.  The prompt runs once either way.
-            "shared_prefix_attn": True}
+            "shared_prefix_attn": True,
+            # B prompts that begin alike (greedy_decode(shared_prefix_rows="auto")): the smallest common prefix, in rows, that is worth the
+            # shared route (the prefix once + one decoder_extend_shared pass); below it the ordinary batch.  512: the smallest measured prefix
+            # from which no cell of profiles/shared_prefix_batch.md loses -- at 1 / 16 / 128 shared rows two passes over the weights cost
+            # more than the one batched prompt pass of prompts of equal length (0.56 - 0.90 x); an int S is taken at its word
+            "shared_prefix_min_rows": 512}
 
 
 def set_variant(name, value):
@@ -1071,6 +1076,125 @@ def decoder_extend(x, layers, meta, cache, row=0):
             x = mm(act, mlp.down_proj.weight, residual=x2)
     cache.set_length(past + n, row)
     return x
+
+
+def _append_rows_batch(qkv, cache, i, past, n, ident, meta):
+    """_append_rows for B sequences of n rows each: rows (b, *) of qkv -> rows past[b] .. past[b] + n - 1 of block b.  One launch per tensor
+    where all sequences start at the same row, else sequence by sequence."""
+    nq, nk = meta.Hq * meta.d, meta.Hkv * meta.d
+    B = len(past)
+    if len(set(past)) > 1:
+        for b in range(B):
+            _append_rows(qkv[b * n:(b + 1) * n], cache, i, b, past[b], ident, meta)
+    elif cache.kv8 is not None:
+        ops.kv_quant_f8(qkv[:, nq:nq + nk], meta.Hkv, meta.d, cache.k[i], cache.k_scale[i], row0=past[0], rows_per_seq=n)
+        ops.kv_quant_f8(qkv[:, nq + nk:], meta.Hkv, meta.d, cache.v[i], cache.v_scale[i], row0=past[0], rows_per_seq=n)
+    else:
+        cache.k[i, :, past[0]:past[0] + n].copy_(qkv[:, nq:nq + nk].view(B, n, nk))
+        cache.v[i, :, past[0]:past[0] + n].copy_(qkv[:, nq + nk:].view(B, n, nk))
+
+
+def _attend_extend_shared(q, cache, i, past_dev, n, bound, meta, ws):
+    """attention of the n new rows of every sequence over layer i of a cache with a shared prefix, which already holds them: the shared rows
+    are rows [0, shared_len) of sequence 0, as _attend_decode picks them"""
+    H = (meta.Hq, meta.Hkv, meta.d, meta.scale)
+    k, v, P = cache.k, cache.v, cache.shared_len
+    if cache.kv8 is not None:
+        ks, vs = cache.kv8
+        return ops.attn_extend_shared_f8(q, k[i, 0], v[i, 0], ks[i, 0], vs[i, 0], k[i], v[i], ks[i], vs[i], past_dev, n, P, bound, *H, workspace=ws)
+    return ops.attn_extend_shared(q, k[i, 0], v[i, 0], k[i], v[i], past_dev, n, P, bound, *H, workspace=ws)
+
+
+def decoder_extend_shared(x, layers, meta, cache, past=None):
+    """n new rows of EACH of the B = cache.batch sequences of a cache with a shared prefix (KVCache.set_shared) in ONE pass over the weights:
+    x [B, n, h] -> hidden rows [B, n, h] (pre final norm).  Row (b, i) sits at position past[b] + i (past: a list of B ints, default
+    cache.lengths; past[b] >= cache.shared_len) and attends the shared rows and then rows [shared_len, past[b] + i] of block b; afterwards
+    cache.lengths[b] == past[b] + n.  B different questions over one context: the pass between the prefix and the decode loop.
+    decoder_extend's two routes and its projection routing (w8_route, W8Scratch, the split-K limits, on the row count B * n) with three
+    differences: the positions are per row (mm355_rope_qk_pos with B sequences of n rows); the append goes into block b per sequence, so
+    q|k|v is always the plain split projection + rotation + append that decoder_extend takes on an fp8_e4m3 cache (the fused reduce launch
+    cannot name a block per row); attention is mm355_attn_extend_shared.  An fp8_e4m3 cache is read back quantised, as decoder_extend reads it.
+    Sequences of unequal length: right-pad x with zero rows to the longest and set_lengths afterwards.  Rows are independent outside
+    attention and attention is causal over the own rows, so a valid row never sees a padding row; the padding rows' K / V land at own rows
+    beyond the sequence's length, where no kernel reads them before a later append overwrites them."""
+    if x.dim() != 3 or x.shape[0] != cache.batch:
+        raise ValueError(f"decoder_extend_shared takes x [batch, n, h] with batch = {cache.batch} sequences, got {tuple(x.shape)}")
+    B, n, h = x.shape
+    S = cache.shared_len
+    if S <= 0:
+        raise ValueError("decoder_extend_shared needs a cache with a shared prefix (KVCache.set_shared); without one the pass is decoder_extend")
+    past = [int(p) for p in (cache.lengths if past is None else past)]
+    if len(past) != B or min(past) < S:
+        raise ValueError(f"decoder_extend_shared: new rows at {past} on a shared prefix of {S} rows: every sequence's own rows begin at or "
+                         "after the shared rows")
+    if max(past) + n > cache.max_len:
+        raise ValueError(f"KV cache capacity of {cache.max_len} rows is too small for {max(past)} cached + {n} new rows")
+    if torch.is_grad_enabled():
+        raise RuntimeError("decoder_extend_shared is an inference pass (torch.no_grad())")
+    R = B * n
+    x = x.reshape(R, h)
+    nq = meta.Hq * meta.d
+    bound = max(past) + n
+    ident = torch.arange(n, device=x.device, dtype=torch.int32)
+    past_dev = torch.tensor(past, dtype=torch.int32).to(x.device)
+    n_ws = int(ops._L().mm355_attn_extend_shared_ws_floats(B, n, meta.Hq, meta.Hkv, meta.d, S, bound))
+    ws = torch.empty(max(n_ws, 4), device=x.device, dtype=torch.float32)
+
+    def append_attend(qkv, i):
+        ops.rope_qk_(qkv, B, n, meta.Hq, meta.Hkv, meta.d, meta.cos, meta.sin, pos_offset=past_dev)
+        _append_rows_batch(qkv, cache, i, past, n, ident, meta)
+        return _attend_extend_shared(qkv[:, :nq], cache, i, past_dev, n, bound, meta, ws)
+
+    splitk = VARIANTS["prefill_splitk"] and R <= 4096
+    wq_shape = ((meta.Hq + 2 * meta.Hkv) * meta.d, h)
+    if splitk and VARIANTS["prefill_fused"] and meta.d % 16 == 0 and ops.gemm_splitk_splits(R, *wq_shape):
+        n1 = None
+        for i, layer in enumerate(layers):
+            params_ready(layer)
+            rec = getattr(layer, "w8", None)
+            on8 = w8_route(layer, R, gu_rows=PROMPT_GU_SPLITK_ROWS)
+            att, mlp = layer.self_attn, layer.mlp
+            if n1 is None:
+                n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
+            qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), "gemm", ops.gemm_splitk, n1)
+            o = append_attend(qkv, i)
+            x2, n2 = _proj(on8, rec, "o", (att.o_proj.weight,), "gemm_norm", ops.gemm_splitk_norm, o,
+                           layer.post_attention_layernorm.weight, meta.eps, residual=x)
+            if "gu" in on8:
+                act = rec.gemm_swiglu(n2, *rec.gu, meta.I)
+            else:
+                wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
+                if VARIANTS["fuse_swiglu"] and ops.gemm_swiglu_supported(n2, wgu, meta.I):
+                    _, act = ops.gemm_swiglu(n2, wgu, meta.I)
+                elif R <= PROMPT_GU_SPLITK_ROWS:
+                    act = ops.gemm_splitk_swiglu(n2, wgu, meta.I)
+                else:
+                    act = ops.swiglu_fwd(ops.gemm(n2, wgu), meta.I)
+            if i + 1 < len(layers):
+                params_ready(layers[i + 1])
+                x, n1 = _proj(on8, rec, "down", (mlp.down_proj.weight,), "gemm_norm", ops.gemm_splitk_norm, act,
+                              layers[i + 1].input_layernorm.weight, meta.eps, residual=x2)
+            else:
+                x = _proj(on8, rec, "down", (mlp.down_proj.weight,), "gemm", ops.gemm_splitk, act, residual=x2)
+    else:
+        mm = ops.gemm_splitk if splitk else ops.gemm
+        for i, layer in enumerate(layers):
+            params_ready(layer)
+            w8_materialize(layer)                             # (a quantised layer: the scratch route, as decoder_extend's plain pass)
+            att, mlp = layer.self_attn, layer.mlp
+            wqkv = fused_weight([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight])
+            wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
+            o = append_attend(mm(ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps), wqkv), i)
+            x2 = mm(o, att.o_proj.weight, residual=x)
+            n2 = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
+            if VARIANTS["fuse_swiglu"] and ops.gemm_swiglu_supported(n2, wgu, meta.I):
+                _, act = ops.gemm_swiglu(n2, wgu, meta.I)
+            else:
+                gu = ops.gemm_splitk(n2, wgu) if (splitk and R <= PROMPT_GU_SPLITK_ROWS) else ops.gemm(n2, wgu)
+                act = ops.swiglu_fwd(gu, meta.I)
+            x = mm(act, mlp.down_proj.weight, residual=x2)
+    cache.set_lengths([p + n for p in past])
+    return x.view(B, n, h)
 
 
 def decoder_prefill_chunked(x, layers, meta, cache, chunk, row=0):

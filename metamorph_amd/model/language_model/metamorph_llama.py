@@ -551,7 +551,7 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
                       end_image_token_id=DEFAULT_IMAGE_END_ID, eos_token_id=(128001, 128009), do_sample=None,
                       temperature=None, top_p=None, num_beams=None, max_new_tokens=1024, use_cache=None, output_image=False,
                       top_k=None, seed=None, stream_ids=None, num_return_sequences=None, repetition_penalty=None, min_new_tokens=None,
-                      suppress_tokens=None, output_logprobs=False, repetition_penalty_ids=None):
+                      suppress_tokens=None, output_logprobs=False, repetition_penalty_ids=None, shared_prefix_rows=None):
         """Token mode / continuous 'image mode' greedy loop.  use_cache=False re-runs the prefix every step exactly like
         the reference (which forces use_cache=False, O(L^2)); the default keeps a KV cache and feeds one row per step
         through the decode-shape kernels -- same state machine, same outputs.
@@ -586,8 +586,32 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         with batches, left padding, the sampler and num_return_sequences.  Refused by name before any device work: a penalty that is not
         finite or <= 0; min_new_tokens negative, non-integer or above max_new_tokens; an id outside [0, vocabulary) in suppress_tokens or
         repetition_penalty_ids (strip the -200 image sentinel first); repetition_penalty_ids without an active penalty or with the
-        wrong number of lists; any of the options with use_cache=False (NotImplementedError)."""
+        wrong number of lists; any of the options with use_cache=False (NotImplementedError).
+        shared_prefix_rows = S (a batch of B > 1 prompts that begin alike: one image asked B questions, a system prompt in front of B
+        items): an int S promises that, once left padding is stripped, rows [0, S) of every sequence are the same rows; "auto" takes the
+        longest common prefix of the stripped rows, capped so that every sequence keeps one own row, and is the ordinary batch below
+        functional.VARIANTS["shared_prefix_min_rows"] rows.  The promise is checked on the device before any decoder work (one comparison,
+        one synchronisation); a break raises ValueError naming the first sequence and row that differ.  The S rows then run through the
+        decoder ONCE into sequence 0 of the cache, the B sequences' own rows -- right-padded with zero rows to the longest -- in ONE more
+        pass over the weights (functional.decoder_extend_shared, mm355_attn_extend_shared), and every step of the device loop reads the
+        prefix once for all sequences (mm355_attn_decode_shared).  functional.set_variant("shared_prefix_attn", False), or a head shape
+        the kernels do not take: the prefix still runs once, its cache rows are copied to every sequence, the own rows go through
+        decoder_extend one sequence after the other and the step is the batch's.  The sampler, the logits processors, log-probabilities,
+        quantised weights and the fp8 cache work as without it.  One prompt: the argument is validated and the call is the one without
+        it.  Refused by name before any device work: use_cache=False, num_return_sequences > 1, an S that is negative, no integer and not
+        "auto", or above min L_b - 1 (every sequence keeps at least one own row).  None (the default): as without the argument."""
         copies = self._copies_of(num_return_sequences)
+        shared_rows = None
+        if shared_prefix_rows is not None:
+            want = self._shared_prefix_arg(shared_prefix_rows)
+            if not (use_cache is None or use_cache):
+                raise ValueError(f"greedy_decode(shared_prefix_rows={shared_prefix_rows!r}, use_cache=False): the sequences share the prefix's "
+                                 "KV cache rows (use_cache=True)")
+            if copies > 1:
+                raise ValueError(f"greedy_decode(shared_prefix_rows={shared_prefix_rows!r}, num_return_sequences={copies}): continuations of "
+                                 "several prompts over one prefix are not built; repeat the prompts instead")
+            B0, n0 = inputs_embeds.shape[:2]
+            shared_rows = self._shared_prefix_of(want, inputs_embeds, self._left_pads(attention_mask, B0, n0))
         V = self.w8_lm_head[0].shape[0] if self.w8_lm_head is not None else self.lm_head.weight.shape[0]
         processors = self._processors_of(repetition_penalty, min_new_tokens, suppress_tokens, output_logprobs, repetition_penalty_ids,
                                          max_new_tokens, V, inputs_embeds.shape[0])
@@ -613,7 +637,7 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         if use_cache is None or use_cache:
             if inputs_embeds.shape[0] != 1 or F.VARIANTS["greedy_loop_b1"] or sampler is not None or processors is not None:
                 return self._greedy_decode_loop(inputs_embeds, attention_mask, start_image_token_id, end_image_token_id, eos_token_id,
-                                                max_new_tokens, output_image, sampler=sampler, processors=processors)
+                                                max_new_tokens, output_image, sampler=sampler, processors=processors, shared_rows=shared_rows)
             return self._greedy_decode_cached(inputs_embeds, start_image_token_id, end_image_token_id, eos_token_id,
                                               max_new_tokens, output_image)
         if inputs_embeds.shape[0] != 1:
@@ -893,6 +917,61 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         return n
 
     @staticmethod
+    def _shared_prefix_arg(shared_prefix_rows):
+        """greedy_decode's shared_prefix_rows -> "auto" or a non-negative int; anything else is refused by name."""
+        if isinstance(shared_prefix_rows, str) and shared_prefix_rows == "auto":
+            return "auto"
+        try:
+            if isinstance(shared_prefix_rows, (bool, str)):
+                raise TypeError
+            S = operator.index(shared_prefix_rows)
+        except TypeError:
+            S = -1
+        if S < 0:
+            raise ValueError(f"greedy_decode: shared_prefix_rows = {shared_prefix_rows!r} must be a non-negative integer or \"auto\"")
+        return S
+
+    @staticmethod
+    def _first_differing_rows(inputs_embeds, pads, rows):
+        """For every sequence of a left-padded [B, n, h] batch the first of its stripped rows [0, rows) that is not sequence 0's row, `rows`
+        where there is none: one comparison where the batch lives and one copy to the host.  rows <= min(n - pads[b])."""
+        B, n, h = inputs_embeds.shape
+        if rows <= 0 or B == 1:
+            return [max(rows, 0)] * B
+        if len(set(pads)) == 1:                                  # (no ragged padding: a view)
+            x = inputs_embeds[:, pads[0]:pads[0] + rows]
+        else:
+            idx = torch.tensor(pads, dtype=torch.int64).view(B, 1) + torch.arange(rows, dtype=torch.int64).view(1, rows)
+            x = inputs_embeds.gather(1, idx.to(inputs_embeds.device).view(B, rows, 1).expand(B, rows, h))  # the stripped rows [B, rows, h]
+        differs = (x != x[:1]).any(-1)                                                                         # [B, rows]
+        first = torch.where(differs.any(1), differs.to(torch.int32).argmax(1), rows)
+        return [int(i) for i in first.cpu()]
+
+    @classmethod
+    def _shared_prefix_of(cls, want, inputs_embeds, pads):
+        """The rows the batch's shared-prefix route shares: `want` is _shared_prefix_arg's value, pads the left padding of every sequence.
+        None: the ordinary batch (one prompt, nothing shared, or "auto" below functional.VARIANTS["shared_prefix_min_rows"]).  An int
+        above min L_b - 1, or one whose promise does not hold, is refused by name."""
+        B, n, _ = inputs_embeds.shape
+        cap = n - max(pads) - 1                                 # every sequence keeps at least one own row
+        if want == "auto":
+            if B == 1:
+                return None
+            S = min(cls._first_differing_rows(inputs_embeds, pads, cap))
+            return S if S >= max(1, int(F.VARIANTS["shared_prefix_min_rows"])) else None
+        if want > cap:
+            raise ValueError(f"greedy_decode: shared_prefix_rows = {want} leaves a sequence of {cap + 1} rows no row of its own (at most "
+                             f"{cap}: the shortest sequence minus one)")
+        if B == 1 or want == 0:
+            return None
+        first = cls._first_differing_rows(inputs_embeds, pads, want)
+        bad = [b for b in range(B) if first[b] < want]
+        if bad:
+            raise ValueError(f"greedy_decode: shared_prefix_rows = {want}, but sequence {bad[0]} differs from sequence 0 at row {first[bad[0]]} "
+                             "(rows counted after left padding is stripped)")
+        return want
+
+    @staticmethod
     def _sampler_of(do_sample, temperature, top_k, top_p, num_beams, seed, stream_ids, B):
         """greedy_decode's sampling arguments -> GreedyLoopGraph's `sampler` tuple, or None for the greedy loop (do_sample falsy, or
         temperature None / 0).  Refuses bad values by name before any device work."""
@@ -970,14 +1049,15 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
                     marks=marks)
 
     def _greedy_decode_loop(self, inputs_embeds, attention_mask, start_image_token_id, end_image_token_id, eos_token_id, max_new_tokens,
-                            output_image, sampler=None, copies=1, processors=None):
+                            output_image, sampler=None, copies=1, processors=None, shared_rows=None):
         """greedy_decode of B sequences: the prompt pass of _prefill_batch (same-length prompts as one batch, ragged ones one after the
         other), then functional.GreedyLoopGraph -- one pass over the weights per step for all sequences, head, argmax and the reference's
         mode state machine on the device.  The host reads the live counter every config.mm355_greedy_poll_steps steps (default 8: at most
         7 wasted steps per call against one synchronisation per 8 tokens; a judgement, tools/bench_greedy_batch.py gives the numbers).
         copies > 1 (one prompt): `copies` continuations of it, the prompt pass of _prefill_shared; sampler=None then walks the greedy loop
         `copies` times over (tests).  processors: _processors_of's dict (its marks one list per prompt: a prompt's list marks every one of
-        its continuations); with want_logprobs the log-probabilities are returned last."""
+        its continuations); with want_logprobs the log-probabilities are returned last.  shared_rows = S (_shared_prefix_of: B > 1 prompts
+        whose first S stripped rows are the same rows): the prompt pass of _prefill_shared_batch."""
         if inputs_embeds.dtype != BF16:
             raise TypeError(f"inputs_embeds must be bf16, got {inputs_embeds.dtype}")
         dev = inputs_embeds.device
@@ -991,6 +1071,8 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
             if B != 1:
                 raise ValueError(f"{copies} continuations take one prompt, got {B}")
             x0 = self._prefill_shared(seqs[0], cache, copies, chunk=self._prefill_chunk_rows())
+        elif shared_rows:
+            x0 = self._prefill_shared_batch(seqs, cache, shared_rows, chunk=self._prefill_chunk_rows())
         else:
             outs = self._prefill_batch(seqs, cache, stepper=False, chunk=self._prefill_chunk_rows())
             x0 = torch.stack([o[-1] for o in outs], 0)
@@ -1175,6 +1257,50 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
             kv.set_lengths([L] * n)
         return rows[-1:].expand(n, h).contiguous()
 
+    def _prefill_shared_batch(self, seqs, cache, S, chunk=None):
+        """Prompt pass of B prompts whose first S rows are the same rows: seqs = one [L_b, h] tensor per sequence (padding stripped, 1 <= S
+        <= min L_b - 1) -> the last hidden row (pre final norm) of every prompt, [B, h].  The S rows run once into sequence 0 of a cache of
+        B sequences.  On the shared route (functional.VARIANTS["shared_prefix_attn"] and a head shape mm355_attn_extend_shared takes) they
+        become every sequence's first rows (KVCache.set_shared) and the own rows n_b = L_b - S of all sequences run as ONE
+        functional.decoder_extend_shared pass on [B, max n_b, h], right-padded with zero rows.  The padding is safe: rows are independent
+        outside attention and attention is causal over the own rows, so a valid row never sees a padding row; the padding rows' K / V land
+        at own rows >= L_b, which the loop's kv_lens[b] keeps unread until its appends have overwritten them from row L_b on.  Else
+        (fan-out) the rows are copied into every sequence's block (KVCache.copy_prefix), the own rows go through decoder_extend one
+        sequence after the other and the step runs on the batch's attention.  Afterwards sequence b holds L_b rows."""
+        dev = seqs[0].device
+        B, h = len(seqs), seqs[0].shape[1]
+        lens = [int(x.shape[0]) for x in seqs]
+        L0 = max(lens)
+        assert B > 1 and 1 <= S <= min(lens) - 1, (B, S, lens)
+        cap = cache.capacity if cache.capacity is not None else L0 + 1024 + 2
+        if cap < L0 + 1:
+            raise ValueError(f"HipKVCache capacity {cap} is smaller than the prompt ({L0} rows)")
+        cos, sin = self.model.rope_tables(cap, dev)
+        _, meta = self._decode_meta(L0)
+        meta.cos, meta.sin = cos, sin
+        kv = cache.kv = F.KVCache(len(self.model.layers), cap, meta.Hkv * meta.d, dev, Hq=meta.Hq, d=meta.d, batch=B,
+                                  fmt=self._kv_cache_format(cache.kv_format))
+        cache.meta = meta
+        _, mb = self._decode_meta(S)
+        mb.cos, mb.sin = cos, sin
+        prefix = seqs[0][:S].contiguous()
+        if chunk is None:
+            F.decoder_prefill(prefix, self.model.layers, mb, kv, row=0)
+        else:
+            F.decoder_prefill_chunked(prefix, self.model.layers, mb, kv, chunk, row=0)
+        if F.VARIANTS["shared_prefix_attn"] and ops.attn_extend_shared_supported(meta.Hq, meta.Hkv, meta.d):
+            kv.set_lengths([S] * B)
+            kv.set_shared(S)
+            own = torch.zeros((B, L0 - S, h), device=dev, dtype=seqs[0].dtype)
+            for b, x2d in enumerate(seqs):
+                own[b, :lens[b] - S] = x2d[S:]
+            rows = F.decoder_extend_shared(own, self.model.layers, meta, kv)
+            kv.set_lengths(lens)
+            return torch.stack([rows[b, lens[b] - S - 1] for b in range(B)], 0)
+        kv.copy_prefix(S)
+        kv.set_lengths([S] * B)
+        return torch.stack([F.decoder_extend(x2d[S:].contiguous(), self.model.layers, meta, kv, row=b)[-1] for b, x2d in enumerate(seqs)], 0)
+
     def _decode_batch(self, x, cache):
         """New rows x [B, n, h] (the hook of n = 1: one row per sequence and step) appended against the batch's cache, every position in ONE
         pass for all B sequences -> their hidden rows [B, n, h] (pre final norm)."""
@@ -1291,6 +1417,13 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         position_ids = kwargs.pop("position_ids", None)
         attention_mask = kwargs.pop("attention_mask", None)
         device_beam_search = kwargs.pop("device_beam_search", False)
+        if kwargs.get("shared_prefix_rows") is None:
+            kwargs.pop("shared_prefix_rows", None)               # (None is the call without the argument, on every route)
+        elif device_beam_search or not use_customize_greedy:
+            # (before the prompt is embedded: the shared-prefix batch is a route of greedy_decode's device loop only)
+            raise ValueError(f"generate(shared_prefix_rows={kwargs['shared_prefix_rows']!r}) runs in greedy_decode's device loop: not with "
+                             + ("device_beam_search=True (the beams of one prompt share its rows already)" if device_beam_search else
+                                "use_customize_greedy=False (HF's generate path drives forward() and knows no shared prefix)"))
         if images is not None or image_embeds is not None:
             (_, position_ids, attention_mask, _, inputs_embeds, _, _, _) = self.prepare_inputs_labels_for_multimodal(
                 inputs, position_ids, attention_mask, None, None, images, image_sizes=image_sizes, image_embeds=image_embeds)

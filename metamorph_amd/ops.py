@@ -844,6 +844,72 @@ def attn_decode_shared_f8(q, k_shared, v_shared, k_shared_scale, v_shared_scale,
     return out
 
 
+# ------------------------------------------------------------------------------------------------ extending a shared-prefix cache by n rows
+
+def attn_extend_shared_supported(Hq, Hkv, d):
+    """the head shapes mm355_attn_extend_shared takes (else MM355_EUNSUPPORTED): those of mm355_attn_decode_shared"""
+    return attn_decode_shared_supported(Hq, Hkv, d)
+
+
+def _extend_shared_args(q, past, n, shared_len, max_kv_len, shared_rows, rows, Hq, Hkv, d, out, workspace):
+    B = past.shape[0]
+    pq, R, W, ldq = _rows2d(q)
+    assert q.dtype == BF16 and R == B * n and W == Hq * d, (q.shape, B, n, Hq, d)
+    assert past.dtype == torch.int32 and n <= max_kv_len and 0 <= shared_len <= max_kv_len <= rows and shared_len <= shared_rows, \
+        (n, shared_len, max_kv_len, rows)
+    out = torch.empty((B * n, Hq * d), device=q.device, dtype=BF16) if out is None else out
+    po, Ro, Wo, ldo = _rows2d(out)
+    assert out.dtype == BF16 and (Ro, Wo) == (R, W)
+    n_ws = int(_L().mm355_attn_extend_shared_ws_floats(B, n, Hq, Hkv, d, shared_len, max_kv_len))
+    ws = workspace
+    if n_ws and (ws is None or ws.numel() < n_ws):
+        ws = torch.empty(n_ws, device=q.device, dtype=torch.float32)
+    return B, pq, ldq, out, po, ldo, ws, (0 if ws is None else ws.numel())
+
+
+def attn_extend_shared(q, k_shared, v_shared, k_cache, v_cache, past, n, shared_len, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None):
+    """n new rows per sequence for B sequences whose first shared_len cached rows are the same rows, stored once (mm355_attn_extend_shared):
+    q [B*n, Hq*d] bf16, already rotated, row (b, i) at b*n + i (may be a column block of a wider tensor); k_shared / v_shared [>= shared_len,
+    Hkv*d] bf16; k_cache / v_cache [B, rows, Hkv*d] bf16 already holding sequence b's new rows at past[b] .. past[b]+n-1; past int32 [B] on the
+    device, past[b] >= shared_len; n, shared_len and max_kv_len host bounds.  Row (b, i) attends the shared rows and then rows [shared_len,
+    past[b] + i] of block b.  Rows [0, shared_len) of the own blocks are never read."""
+    _chk_dev(q, k_shared, v_shared, k_cache, v_cache, past, out)
+    assert k_cache.dim() == 3 and k_cache.dtype == BF16 and k_cache.shape == v_cache.shape and k_cache.stride(2) == 1
+    assert v_cache.stride() == k_cache.stride() and k_cache.shape[2] == Hkv * d and k_cache.shape[0] >= past.shape[0]
+    assert k_shared.dim() == 2 and k_shared.dtype == BF16 and k_shared.shape == v_shared.shape and k_shared.stride() == v_shared.stride()
+    assert k_shared.stride(1) == 1 and k_shared.shape[1] == Hkv * d
+    B, pq, ldq, out, po, ldo, ws, n_ws = _extend_shared_args(q, past, n, shared_len, max_kv_len, k_shared.shape[0], k_cache.shape[1], Hq, Hkv, d,
+                                                             out, workspace)
+    _lib.check(_L().mm355_attn_extend_shared(pq, ldq, k_shared.data_ptr(), v_shared.data_ptr(), k_shared.stride(0), k_cache.data_ptr(),
+                                             v_cache.data_ptr(), k_cache.stride(1), k_cache.stride(0), past.data_ptr(), n, shared_len,
+                                             max_kv_len, po, ldo, B, Hq, Hkv, d, scale, _p(ws), n_ws, _stream()),
+               f"mm355_attn_extend_shared B={B} n={n} Hq={Hq} Hkv={Hkv} d={d} shared_len={shared_len}")
+    return out
+
+
+def attn_extend_shared_f8(q, k_shared, v_shared, k_shared_scale, v_shared_scale, k8, v8, k_scale, v_scale, past, n, shared_len, max_kv_len, Hq,
+                          Hkv, d, scale, out=None, workspace=None):
+    """attn_extend_shared() over e4m3 bytes: k_shared / v_shared [>= shared_len, Hkv*d] uint8 with scales [>= shared_len, Hkv] f32, k8 / v8 [B,
+    rows, Hkv*d] uint8 with k_scale / v_scale [B, rows, Hkv] f32 (mm355_attn_extend_shared_f8): equal to attn_extend_shared() on dequant_kv8()
+    of the same bytes bit for bit."""
+    _chk_dev(q, k_shared, v_shared, k_shared_scale, v_shared_scale, k8, v8, k_scale, v_scale, past, out)
+    assert k8.shape == v8.shape and k8.stride() == v8.stride() and k_scale.stride() == v_scale.stride() and k8.shape[0] >= past.shape[0]
+    ldb, bsb, ldsc, bssc = _kv8_cache(k8, k_scale, Hkv, d)
+    _kv8_cache(v8, v_scale, Hkv, d)
+    assert k_shared.dtype == torch.uint8 and k_shared.dim() == 2 and k_shared.shape == v_shared.shape and k_shared.stride() == v_shared.stride()
+    assert k_shared.stride(1) == 1 and k_shared.shape[1] == Hkv * d
+    assert k_shared_scale.dtype == torch.float32 and tuple(k_shared_scale.shape) == (k_shared.shape[0], Hkv) and k_shared_scale.stride(1) == 1
+    assert v_shared_scale.dtype == torch.float32 and v_shared_scale.shape == k_shared_scale.shape and v_shared_scale.stride() == k_shared_scale.stride()
+    B, pq, ldq, out, po, ldo, ws, n_ws = _extend_shared_args(q, past, n, shared_len, max_kv_len, k_shared.shape[0], k8.shape[1], Hq, Hkv, d, out,
+                                                             workspace)
+    _lib.check(_L().mm355_attn_extend_shared_f8(pq, ldq, k_shared.data_ptr(), v_shared.data_ptr(), k_shared.stride(0), k_shared_scale.data_ptr(),
+                                                v_shared_scale.data_ptr(), k_shared_scale.stride(0), k8.data_ptr(), v8.data_ptr(), ldb, bsb,
+                                                k_scale.data_ptr(), v_scale.data_ptr(), ldsc, bssc, KV8_E4M3, past.data_ptr(), n, shared_len,
+                                                max_kv_len, po, ldo, B, Hq, Hkv, d, scale, _p(ws), n_ws, _stream()),
+               f"mm355_attn_extend_shared_f8 B={B} n={n} Hq={Hq} Hkv={Hkv} d={d} shared_len={shared_len}")
+    return out
+
+
 def transpose(x, out=None, ld_out=None):
     """out[c, r] = x[r, c]"""
     _chk_dev(x, out)
