@@ -388,3 +388,31 @@ def test_hf_generate_of_20_prompts_gives_the_same_tokens_on_either_route(split_m
         on = a.generate(**kw)
         off = _without_w4_gemm(lambda: a.generate(**kw))
     assert on.shape[0] == 20 and on.shape[1] >= 6 and on.tolist() == off.tolist()
+
+
+# ------------------------------------------------------------------ h. the single-slice store on a ragged window
+@pytest.mark.parametrize("M", [19, 70])
+def test_gemm_w4_single_slice_store_on_a_ragged_window(ops, M):
+    """N = 523 into the first columns of an [M, 528] buffer, residual rows 528 apart: gemm_epilogue's 16-byte body on columns [0, 520) and its
+    scalar body on the last three, from the 32-row tile (M = 19) and the 64-row tile (M = 70), for bf16 and fp32 output, with and without
+    the residual.  N % 8 != 0 is never split (the workspace query says so), so the store under test is the one that ran.  Against the fp64
+    product of the dequantised weight under the derived bound of tests/gemm_epilogue_refs.py; the allocation is prefilled with a canary NaN:
+    every element of the window is written, nothing outside it."""
+    import gemm_epilogue_refs as E
+    from metamorph_amd import lib
+    N, K = 523, 256
+    assert int(lib.load().mm355_gemm_w4_ws_floats(M, N, K)) == 0
+    geo = E.Geometry("w4", M, N, 528, 0, 0, 528)
+    q, s, wd = quantised(N, K, 31)
+    qd, sd, wd = q.to(DEV), s.to(DEV), wd.to(DEV)
+    x, r = rnd(M, K, seed=1, scale=0.5).to(DEV), rnd(M, N, seed=4).to(DEV)
+    accb = E.accumulation_bound(x, wd)
+    for with_res in (False, True):
+        ref = x.double() @ wd.t() + (r.double() if with_res else 0.0)
+        for out_f32 in (False, True):
+            what = f"gemm_w4 {M}x{N}x{K} {'fp32' if out_f32 else 'bf16'}{' residual' if with_res else ''}"
+            alloc, view = E.canary_out(geo, torch.float32 if out_f32 else torch.bfloat16, DEV)
+            ops.gemm_w4(x, qd, sd, residual=E.residual_view(r, geo) if with_res else None, out=view)
+            E.check_untouched(alloc, geo, what)
+            worst = E.check(view, ref, E.epilogue_bound(ref, accb, None, out_f32), what, E.column_classes(geo, with_res))
+            print(f"{what}: largest |error| / bound {worst:.3f}")
