@@ -917,54 +917,105 @@ def decoder_prefill(x, layers, meta, cache, row=0):
     return x
 
 
-def _prefill_layers_fused(x, layers, meta, cache, row, ident):
-    """decoder_prefill for one sequence of a few hundred rows, with what follows a split projection in its reduce launch: q|k|v -> RoPE at the
-    row's position -> rotated k and v straight into the cache rows (mm355_gemm_splitk_rope_append_bf16 with a batch stride of 0: every row of
-    the call belongs to the same sequence), attention reads K / V from the cache rows, o / down + residual + the RMSNorm that follows
-    (mm355_gemm_splitk_norm_bf16).  The bits of decoder_layer_forward's prompt pass (rope_qk_ and rope_kv_append share their arithmetic)."""
-    L = x.shape[0]
-    nq = meta.Hq * meta.d
+def _seq_rows(t, n):
+    """Cache rows t [max_len, width] of ONE sequence as the [n, max_len, width] cache operand of a call with n rows: a batch stride of 0,
+    every row of the call belongs to this sequence."""
+    return t.as_strided((n, t.shape[0], t.shape[1]), (0, t.stride(0), 1))
+
+
+def _gate_up(on8, rec, mlp, n2, meta, prompt):
+    """gate|up + SwiGLU of a fused walk: on the record's bytes where w8_route put it there (a decode step of 17 - 32 rows too: the w8 GEMV has
+    no second row group), else the split-K form with SwiGLU in its reduce launch -- but for a prompt-side pass (prefill, extend,
+    extend_shared) the ping-pong GEMM with the SwiGLU epilogue where it takes the shape and two launches beyond PROMPT_GU_SPLITK_ROWS rows,
+    and for a decode step of up to 32 rows on wide weights the weight stream of the 16-row GEMV, a second x row group on its fragments."""
+    if "gu" in on8:
+        return rec.gemm_swiglu(n2, *rec.gu, meta.I)
+    wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
+    if prompt:
+        if VARIANTS["fuse_swiglu"] and ops.gemm_swiglu_supported(n2, wgu, meta.I):
+            return ops.gemm_swiglu(n2, wgu, meta.I)[1]
+        if n2.shape[0] > PROMPT_GU_SPLITK_ROWS:
+            return ops.swiglu_fwd(ops.gemm(n2, wgu), meta.I)
+    elif VARIANTS["decode_wide_gu_gemv"] and n2.shape[0] <= 32 and meta.I % 2 == 0 and ops.gemv_rows32_units(meta.I // 2):
+        return ops.gemv_swiglu(n2, wgu, meta.I)
+    return ops.gemm_splitk_swiglu(n2, wgu, meta.I)
+
+
+def _fused_walk(x, layers, meta, attend, prompt):
+    """x [rows, h] through every layer with what follows a split projection in its reduce launch: the input norm as a launch of its own
+    for the first layer only, o / down + residual + the RMSNorm that follows (mm355_gemm_splitk_norm_bf16; the last down: the plain split
+    projection).  The one step that differs between the passes is the caller's: attend(qkv, i) -> o, where qkv(w8_op, bf16_op, *args) is
+    layer i's q|k|v projection of the normed rows (_proj: the plain split projection or the one with RoPE + cache append) and what follows
+    it -- rotation, append, attention -- is up to the caller.  prompt: the prompt passes' gate|up rule and row limit, else the decode
+    step's.  A quantised layer: w8_route per layer, these projections on the w8 GEMM, the rest dequantised."""
     n1 = None
-    stage = None
-    if cache.kv8 is not None:
-        # fp8_e4m3 cache: the reduce launch writes the rotated k and the v rows into ONE pair of bf16 staging buffers shared by all layers,
-        # attention runs on them (the bits of the bf16-cache pass), then they are quantised into the cache rows
-        stage = torch.empty((2, L, meta.Hkv * meta.d), device=x.device, dtype=BF16)
     for i, layer in enumerate(layers):
         params_ready(layer)
         rec = getattr(layer, "w8", None)
-        on8 = w8_route(layer, L, gu_rows=PROMPT_GU_SPLITK_ROWS)   # (a quantised layer: these projections on the w8 GEMM, the rest dequantised)
+        on8 = w8_route(layer, x.shape[0], PROMPT_GU_SPLITK_ROWS if prompt else None)
         att, mlp = layer.self_attn, layer.mlp
         if n1 is None:
             n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
-        kc, vc = (stage[0], stage[1]) if stage is not None else (cache.k[i, row], cache.v[i, row])   # [max_len, width]
-        rows_k = kc.as_strided((L, kc.shape[0], kc.shape[1]), (0, kc.stride(0), 1))
-        rows_v = vc.as_strided((L, vc.shape[0], vc.shape[1]), (0, vc.stride(0), 1))
-        qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), "gemm_rope_append",
-                    ops.gemm_splitk_rope_append, n1, meta.Hq, meta.Hkv, meta.d, meta.cos, meta.sin, ident, rows_k, rows_v)
-        o, _ = ops.attn_fwd(qkv[:, :nq], kc[:L], vc[:L], 1, L, meta.Hq, meta.Hkv, meta.d, meta.scale, True, meta.seqlens)
-        if stage is not None:
-            ops.kv_quant_f8(stage[0], meta.Hkv, meta.d, cache.k[i, row:row + 1], cache.k_scale[i, row:row + 1])
-            ops.kv_quant_f8(stage[1], meta.Hkv, meta.d, cache.v[i, row:row + 1], cache.v_scale[i, row:row + 1])
+        o = attend(lambda w8_op, bf16_op, *args: _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight),
+                                                       w8_op, bf16_op, n1, *args), i)
         x2, n2 = _proj(on8, rec, "o", (att.o_proj.weight,), "gemm_norm", ops.gemm_splitk_norm, o,
                        layer.post_attention_layernorm.weight, meta.eps, residual=x)
-        if "gu" in on8:
-            act = rec.gemm_swiglu(n2, *rec.gu, meta.I)
-        else:
-            wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
-            if VARIANTS["fuse_swiglu"] and ops.gemm_swiglu_supported(n2, wgu, meta.I):
-                _, act = ops.gemm_swiglu(n2, wgu, meta.I)
-            elif L <= PROMPT_GU_SPLITK_ROWS:
-                act = ops.gemm_splitk_swiglu(n2, wgu, meta.I)
-            else:
-                act = ops.swiglu_fwd(ops.gemm(n2, wgu), meta.I)
+        act = _gate_up(on8, rec, mlp, n2, meta, prompt)
         if i + 1 < len(layers):
-            params_ready(layers[i + 1])
+            params_ready(layers[i + 1])                       # (its input norm weight is read by this layer's last launch)
             x, n1 = _proj(on8, rec, "down", (mlp.down_proj.weight,), "gemm_norm", ops.gemm_splitk_norm, act,
                           layers[i + 1].input_layernorm.weight, meta.eps, residual=x2)
         else:
             x = _proj(on8, rec, "down", (mlp.down_proj.weight,), "gemm", ops.gemm_splitk, act, residual=x2)
     return x
+
+
+def _plain_walk(x, layers, meta, splitk, append_attend):
+    """x [rows, h] through every layer on the plain route of decoder_extend / decoder_extend_shared: every norm, the rotation and SwiGLU
+    as launches of their own, the projections on the split-K GEMM (`splitk`) or the plain one; a quantised layer on the scratch route, as
+    decoder_prefill's plain pass.  append_attend(qkv, i) -> o is the caller's: rotation, append and attention of layer i."""
+    mm = ops.gemm_splitk if splitk else ops.gemm
+    for i, layer in enumerate(layers):
+        params_ready(layer)
+        w8_materialize(layer)
+        att, mlp = layer.self_attn, layer.mlp
+        wqkv = fused_weight([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight])
+        wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
+        o = append_attend(mm(ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps), wqkv), i)
+        x2 = mm(o, att.o_proj.weight, residual=x)
+        n2 = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
+        if VARIANTS["fuse_swiglu"] and ops.gemm_swiglu_supported(n2, wgu, meta.I):
+            _, act = ops.gemm_swiglu(n2, wgu, meta.I)
+        else:
+            gu = ops.gemm_splitk(n2, wgu) if (splitk and x.shape[0] <= PROMPT_GU_SPLITK_ROWS) else ops.gemm(n2, wgu)
+            act = ops.swiglu_fwd(gu, meta.I)
+        x = mm(act, mlp.down_proj.weight, residual=x2)
+    return x
+
+
+def _prefill_layers_fused(x, layers, meta, cache, row, ident):
+    """decoder_prefill for one sequence of a few hundred rows on _fused_walk: q|k|v -> RoPE at the row's position -> rotated k and v
+    straight into the cache rows (mm355_gemm_splitk_rope_append_bf16 on _seq_rows), attention reads K / V from the cache rows.  The bits of
+    decoder_layer_forward's prompt pass (rope_qk_ and rope_kv_append share their arithmetic)."""
+    L = x.shape[0]
+    nq = meta.Hq * meta.d
+    stage = None
+    if cache.kv8 is not None:
+        # fp8_e4m3 cache: the reduce launch writes the rotated k and the v rows into ONE pair of bf16 staging buffers shared by all layers,
+        # attention runs on them (the bits of the bf16-cache pass), then they are quantised into the cache rows
+        stage = torch.empty((2, L, meta.Hkv * meta.d), device=x.device, dtype=BF16)
+
+    def attend(qkv, i):
+        kc, vc = (stage[0], stage[1]) if stage is not None else (cache.k[i, row], cache.v[i, row])   # [max_len, width]
+        q = qkv("gemm_rope_append", ops.gemm_splitk_rope_append, meta.Hq, meta.Hkv, meta.d, meta.cos, meta.sin, ident,
+                _seq_rows(kc, L), _seq_rows(vc, L))
+        o, _ = ops.attn_fwd(q[:, :nq], kc[:L], vc[:L], 1, L, meta.Hq, meta.Hkv, meta.d, meta.scale, True, meta.seqlens)
+        if stage is not None:
+            ops.kv_quant_f8(stage[0], meta.Hkv, meta.d, cache.k[i, row:row + 1], cache.k_scale[i, row:row + 1])
+            ops.kv_quant_f8(stage[1], meta.Hkv, meta.d, cache.v[i, row:row + 1], cache.v_scale[i, row:row + 1])
+        return o
+
+    return _fused_walk(x, layers, meta, attend, prompt=True)
 
 
 def _attend_extend(q, cache, i, row, past_dev, n, bound, meta):
@@ -991,12 +1042,12 @@ def decoder_extend(x, layers, meta, cache, row=0):
     """n new rows of sequence `row` on its FILLED cache in one pass over the weights: x [n, h] -> hidden rows [n, h] (pre final norm); the rows
     sit at positions past .. past + n - 1 (past = cache.lengths[row] >= 1) and afterwards cache.lengths[row] == past + n.  A follow-up turn
     of a conversation, a slice of a prompt run in chunks, candidate tokens scored against a cache (then KVCache.set_length back).
-    _prefill_layers_fused with three differences: the positions are past + arange(n), attention is mm355_attn_extend over the cache rows
-    (the append comes first), and an fp8_e4m3 cache is read back quantised -- the new rows are rotated in the q|k|v activation, quantised
-    into the cache at row past and attended from there: the semantics of n decode steps (every row sees the quantised form of all rows, its
-    own included), not of the first prompt pass.  The projections take the prompt pass's routes (w8_route, W8Scratch, the split-K limits);
-    where _prefill_layers_fused does not apply (more than 4096 rows, q|k|v not split, d % 16 != 0) the plain decoder_layer_forward route
-    with mm355_rope_qk_pos and a row copy into the cache."""
+    _prefill_layers_fused's walk (_fused_walk) with three differences in its attention step: the positions are past + arange(n), attention
+    is mm355_attn_extend over the cache rows (the append comes first), and an fp8_e4m3 cache is read back quantised -- the new rows are
+    rotated in the q|k|v activation, quantised into the cache at row past and attended from there: the semantics of n decode steps (every
+    row sees the quantised form of all rows, its own included), not of the first prompt pass.  The projections take the prompt pass's
+    routes (w8_route, W8Scratch, the split-K limits); where the fused walk does not apply (more than 4096 rows, q|k|v not split,
+    d % 16 != 0) the plain route (_plain_walk) with mm355_rope_qk_pos and a row copy into the cache."""
     n, h = x.shape
     if cache.shared_len > 0:
         raise ValueError(f"decoder_extend on a cache with a shared prefix of {cache.shared_len} rows: sequences 1.. do not hold the prefix "
@@ -1014,66 +1065,23 @@ def decoder_extend(x, layers, meta, cache, row=0):
     pos = ident + past
     past_dev = pos[:1]
     splitk = VARIANTS["prefill_splitk"] and n <= 4096
-    wq_shape = ((meta.Hq + 2 * meta.Hkv) * meta.d, h)
-    if splitk and VARIANTS["prefill_fused"] and meta.d % 16 == 0 and ops.gemm_splitk_splits(n, *wq_shape):
-        n1 = None
-        for i, layer in enumerate(layers):
-            params_ready(layer)
-            rec = getattr(layer, "w8", None)
-            on8 = w8_route(layer, n, gu_rows=PROMPT_GU_SPLITK_ROWS)
-            att, mlp = layer.self_attn, layer.mlp
-            if n1 is None:
-                n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
-            wq = (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight)
-            if cache.kv8 is not None:                         # plain split projection, rotation in place, quantising append (no fused f8 form)
-                qkv = _proj(on8, rec, "qkv", wq, "gemm", ops.gemm_splitk, n1)
-                ops.rope_qk_(qkv, 1, n, meta.Hq, meta.Hkv, meta.d, meta.cos, meta.sin, pos_offset=past_dev)
-                _append_rows(qkv, cache, i, row, past, ident, meta)
-            else:
-                kc, vc = cache.k[i, row], cache.v[i, row]
-                rows_k = kc.as_strided((n, kc.shape[0], kc.shape[1]), (0, kc.stride(0), 1))
-                rows_v = vc.as_strided((n, vc.shape[0], vc.shape[1]), (0, vc.stride(0), 1))
-                qkv = _proj(on8, rec, "qkv", wq, "gemm_rope_append", ops.gemm_splitk_rope_append, n1, meta.Hq, meta.Hkv, meta.d,
-                            meta.cos, meta.sin, pos, rows_k, rows_v)
-            o = _attend_extend(qkv[:, :nq], cache, i, row, past_dev, n, bound, meta)
-            x2, n2 = _proj(on8, rec, "o", (att.o_proj.weight,), "gemm_norm", ops.gemm_splitk_norm, o,
-                           layer.post_attention_layernorm.weight, meta.eps, residual=x)
-            if "gu" in on8:
-                act = rec.gemm_swiglu(n2, *rec.gu, meta.I)
-            else:
-                wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
-                if VARIANTS["fuse_swiglu"] and ops.gemm_swiglu_supported(n2, wgu, meta.I):
-                    _, act = ops.gemm_swiglu(n2, wgu, meta.I)
-                elif n <= PROMPT_GU_SPLITK_ROWS:
-                    act = ops.gemm_splitk_swiglu(n2, wgu, meta.I)
-                else:
-                    act = ops.swiglu_fwd(ops.gemm(n2, wgu), meta.I)
-            if i + 1 < len(layers):
-                params_ready(layers[i + 1])
-                x, n1 = _proj(on8, rec, "down", (mlp.down_proj.weight,), "gemm_norm", ops.gemm_splitk_norm, act,
-                              layers[i + 1].input_layernorm.weight, meta.eps, residual=x2)
-            else:
-                x = _proj(on8, rec, "down", (mlp.down_proj.weight,), "gemm", ops.gemm_splitk, act, residual=x2)
+
+    def append_attend(qkv, i):                                # rotation in place, (quantising) append, attention over the cache rows
+        ops.rope_qk_(qkv, 1, n, meta.Hq, meta.Hkv, meta.d, meta.cos, meta.sin, pos_offset=past_dev)
+        _append_rows(qkv, cache, i, row, past, ident, meta)
+        return _attend_extend(qkv[:, :nq], cache, i, row, past_dev, n, bound, meta)
+
+    def attend(qkv, i):
+        if cache.kv8 is not None:                             # plain split projection, then as the plain route (no fused f8 form)
+            return append_attend(qkv("gemm", ops.gemm_splitk), i)
+        q = qkv("gemm_rope_append", ops.gemm_splitk_rope_append, meta.Hq, meta.Hkv, meta.d, meta.cos, meta.sin, pos,
+                _seq_rows(cache.k[i, row], n), _seq_rows(cache.v[i, row], n))
+        return _attend_extend(q[:, :nq], cache, i, row, past_dev, n, bound, meta)
+
+    if splitk and VARIANTS["prefill_fused"] and meta.d % 16 == 0 and ops.gemm_splitk_splits(n, (meta.Hq + 2 * meta.Hkv) * meta.d, h):
+        x = _fused_walk(x, layers, meta, attend, prompt=True)
     else:
-        mm = ops.gemm_splitk if splitk else ops.gemm
-        for i, layer in enumerate(layers):
-            params_ready(layer)
-            w8_materialize(layer)                             # (a quantised layer: the scratch route, as decoder_prefill's plain pass)
-            att, mlp = layer.self_attn, layer.mlp
-            wqkv = fused_weight([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight])
-            wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
-            qkv = mm(ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps), wqkv)
-            ops.rope_qk_(qkv, 1, n, meta.Hq, meta.Hkv, meta.d, meta.cos, meta.sin, pos_offset=past_dev)
-            _append_rows(qkv, cache, i, row, past, ident, meta)
-            o = _attend_extend(qkv[:, :nq], cache, i, row, past_dev, n, bound, meta)
-            x2 = mm(o, att.o_proj.weight, residual=x)
-            n2 = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
-            if VARIANTS["fuse_swiglu"] and ops.gemm_swiglu_supported(n2, wgu, meta.I):
-                _, act = ops.gemm_swiglu(n2, wgu, meta.I)
-            else:
-                gu = ops.gemm_splitk(n2, wgu) if (splitk and n <= PROMPT_GU_SPLITK_ROWS) else ops.gemm(n2, wgu)
-                act = ops.swiglu_fwd(gu, meta.I)
-            x = mm(act, mlp.down_proj.weight, residual=x2)
+        x = _plain_walk(x, layers, meta, splitk, append_attend)
     cache.set_length(past + n, row)
     return x
 
@@ -1146,53 +1154,10 @@ def decoder_extend_shared(x, layers, meta, cache, past=None):
         return _attend_extend_shared(qkv[:, :nq], cache, i, past_dev, n, bound, meta, ws)
 
     splitk = VARIANTS["prefill_splitk"] and R <= 4096
-    wq_shape = ((meta.Hq + 2 * meta.Hkv) * meta.d, h)
-    if splitk and VARIANTS["prefill_fused"] and meta.d % 16 == 0 and ops.gemm_splitk_splits(R, *wq_shape):
-        n1 = None
-        for i, layer in enumerate(layers):
-            params_ready(layer)
-            rec = getattr(layer, "w8", None)
-            on8 = w8_route(layer, R, gu_rows=PROMPT_GU_SPLITK_ROWS)
-            att, mlp = layer.self_attn, layer.mlp
-            if n1 is None:
-                n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
-            qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), "gemm", ops.gemm_splitk, n1)
-            o = append_attend(qkv, i)
-            x2, n2 = _proj(on8, rec, "o", (att.o_proj.weight,), "gemm_norm", ops.gemm_splitk_norm, o,
-                           layer.post_attention_layernorm.weight, meta.eps, residual=x)
-            if "gu" in on8:
-                act = rec.gemm_swiglu(n2, *rec.gu, meta.I)
-            else:
-                wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
-                if VARIANTS["fuse_swiglu"] and ops.gemm_swiglu_supported(n2, wgu, meta.I):
-                    _, act = ops.gemm_swiglu(n2, wgu, meta.I)
-                elif R <= PROMPT_GU_SPLITK_ROWS:
-                    act = ops.gemm_splitk_swiglu(n2, wgu, meta.I)
-                else:
-                    act = ops.swiglu_fwd(ops.gemm(n2, wgu), meta.I)
-            if i + 1 < len(layers):
-                params_ready(layers[i + 1])
-                x, n1 = _proj(on8, rec, "down", (mlp.down_proj.weight,), "gemm_norm", ops.gemm_splitk_norm, act,
-                              layers[i + 1].input_layernorm.weight, meta.eps, residual=x2)
-            else:
-                x = _proj(on8, rec, "down", (mlp.down_proj.weight,), "gemm", ops.gemm_splitk, act, residual=x2)
+    if splitk and VARIANTS["prefill_fused"] and meta.d % 16 == 0 and ops.gemm_splitk_splits(R, (meta.Hq + 2 * meta.Hkv) * meta.d, h):
+        x = _fused_walk(x, layers, meta, lambda qkv, i: append_attend(qkv("gemm", ops.gemm_splitk), i), prompt=True)
     else:
-        mm = ops.gemm_splitk if splitk else ops.gemm
-        for i, layer in enumerate(layers):
-            params_ready(layer)
-            w8_materialize(layer)                             # (a quantised layer: the scratch route, as decoder_extend's plain pass)
-            att, mlp = layer.self_attn, layer.mlp
-            wqkv = fused_weight([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight])
-            wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
-            o = append_attend(mm(ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps), wqkv), i)
-            x2 = mm(o, att.o_proj.weight, residual=x)
-            n2 = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
-            if VARIANTS["fuse_swiglu"] and ops.gemm_swiglu_supported(n2, wgu, meta.I):
-                _, act = ops.gemm_swiglu(n2, wgu, meta.I)
-            else:
-                gu = ops.gemm_splitk(n2, wgu) if (splitk and R <= PROMPT_GU_SPLITK_ROWS) else ops.gemm(n2, wgu)
-                act = ops.swiglu_fwd(gu, meta.I)
-            x = mm(act, mlp.down_proj.weight, residual=x2)
+        x = _plain_walk(x, layers, meta, splitk, append_attend)
     cache.set_lengths([p + n for p in past])
     return x.view(B, n, h)
 
@@ -1200,7 +1165,10 @@ def decoder_extend_shared(x, layers, meta, cache, past=None):
 def decoder_prefill_chunked(x, layers, meta, cache, chunk, row=0):
     """decoder_prefill of one sequence in slices of `chunk` rows: the first through decoder_prefill, every further one (the last may be short)
     through decoder_extend against the rows cached so far.  Bounds the live activations by the slice, and keeps a quantised decoder on the w8
-    split-K GEMM where the whole prompt would leave it (W8Scratch).  An fp8_e4m3 cache: the slices after the first read the cache quantised."""
+    split-K GEMM where the whole prompt would leave it (W8Scratch).  An fp8_e4m3 cache: the slices after the first read the cache quantised.
+    chunk None: not chunked, decoder_prefill as it is."""
+    if chunk is None:
+        return decoder_prefill(x, layers, meta, cache, row)
     L = x.shape[0]
     chunk = int(chunk)
     if chunk < 1:
@@ -1486,39 +1454,13 @@ def _decode_rows_gemm(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_
     nq = meta.Hq * meta.d
     if VARIANTS["decode_wide_fused"] and meta.d % 16 == 0:
         # what follows a split projection rides in its reduce launch (mm355_gemm_splitk_{rope_append,norm,swiglu}_bf16): 9 launches per layer
-        n1 = None
-        gu_gemv = VARIANTS["decode_wide_gu_gemv"] and x.shape[0] <= 32 and meta.I % 2 == 0 and ops.gemv_rows32_units(meta.I // 2)
-        for i, layer in enumerate(layers):
-            params_ready(layer)
-            rec = getattr(layer, "w8", None)
-            on8 = w8_route(layer, x.shape[0])                 # (a quantised layer: these projections on the w8 GEMM, the rest dequantised)
-            att, mlp = layer.self_attn, layer.mlp
-            if n1 is None:
-                n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
+        def attend(qkv, i):
             if kv8 is not None:                              # fp8_e4m3 cache: the plain split projection, then the quantising append (ten launches per layer)
-                qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), "gemm", ops.gemm_splitk, n1)
-                o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound, shared)
-            else:
-                qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), "gemm_rope_append",
-                            ops.gemm_splitk_rope_append, n1, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
-                o = _attend_decode(qkv[:, :nq], i, meta, k, v, None, len_dev, ws, kv_bound, shared)
-            x2, n2 = _proj(on8, rec, "o", (att.o_proj.weight,), "gemm_norm", ops.gemm_splitk_norm, o,
-                           layer.post_attention_layernorm.weight, meta.eps, residual=x)
-            if "gu" in on8:
-                act = rec.gemm_swiglu(n2, *rec.gu, meta.I)  # (17 - 32 rows too: the w8 GEMV has no second row group)
-            else:
-                wgu = fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight])
-                if gu_gemv:
-                    act = ops.gemv_swiglu(n2, wgu, meta.I)    # up to 32 rows: the weight stream of the 16-row kernel, a second x row group on its fragments
-                else:
-                    act = ops.gemm_splitk_swiglu(n2, wgu, meta.I)
-            if i + 1 < len(layers):
-                params_ready(layers[i + 1])                   # (its input norm weight is read by this layer's last launch)
-                x, n1 = _proj(on8, rec, "down", (mlp.down_proj.weight,), "gemm_norm", ops.gemm_splitk_norm, act,
-                              layers[i + 1].input_layernorm.weight, meta.eps, residual=x2)
-            else:
-                x = _proj(on8, rec, "down", (mlp.down_proj.weight,), "gemm", ops.gemm_splitk, act, residual=x2)
-        return x
+                return _append_attend_f8(qkv("gemm", ops.gemm_splitk), i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound, shared)
+            q = qkv("gemm_rope_append", ops.gemm_splitk_rope_append, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
+            return _attend_decode(q[:, :nq], i, meta, k, v, None, len_dev, ws, kv_bound, shared)
+
+        return _fused_walk(x, layers, meta, attend, prompt=False)
     for i, layer in enumerate(layers):
         params_ready(layer)
         rec = getattr(layer, "w8", None)
@@ -1575,19 +1517,104 @@ def decoder_decode_row(x, layers, meta, cache, cos, sin, kv_bound=None):
     return y
 
 
-class DecodeStepGraph:
-    """decoder_decode_row captured as a hipGraph (5 - 7 launches x layers per step collapse into one graph launch; the per-token step is
-    launch-bound otherwise) and replayed per token: copy the new rows (one per sequence) into `x_in`, replay, read `x_out`.  One capture
-    per attention bound (decode_kv_bound: the short, single-key-group form while every sequence holds <= 1024 rows, the general one
-    afterwards), made when first needed.  Falls back to eager launches if capture is not possible (functional.set_variant("decode_graph",
-    False) forces that)."""
+class _CapturedStep:
+    """One decode step over `cache` as a hipGraph per attention bound (decode_kv_bound: the short, single-key-group form while every
+    sequence holds <= 1024 rows, the general one afterwards), captured when the bound is first needed and replayed per token; eager
+    launches if capture is not possible (functional.set_variant("decode_graph", False) forces that).  A subclass owns the static input
+    rows `x_in` and supplies what follows decoder_decode_row in a step (_tail), the `label` of the warning and, where the warm-up must
+    leave no trace in its own state, _quiet().  The loops' run() share _poll_loop."""
+    label = "decode"
 
-    def __init__(self, layers, meta, cache, cos, sin, h, device):
+    def __init__(self, layers, meta, cache, cos, sin):
         self.args = (layers, meta, cache, cos, sin)
         self.cache = cache
-        self.x_in = torch.zeros((cache.batch, h), device=device, dtype=BF16)
-        self.graphs = {}                                     # kv bound -> (graph, x_out)
+        self.graphs = {}                                     # kv bound -> (graph, what _launches returned under capture)
         self.capture_ok = VARIANTS["decode_graph"]
+
+    def _launches(self, bound=None):
+        """one step on the rows in `x_in`, eager: decoder_decode_row, then the subclass's tail on its hidden rows"""
+        return self._tail(decoder_decode_row(self.x_in, *self.args, kv_bound=bound))
+
+    def _tail(self, x):
+        return x
+
+    def _quiet(self):
+        """(tensor, value) or None: the warm-up launches run for real, so the tensor is filled with the value around warm-up and capture
+        (a state in which the step logs and feeds nothing) and restored afterwards"""
+        return None
+
+    def _capture(self, bound):
+        cache = self.cache
+        keep = list(cache.lengths)
+        quiet = self._quiet()
+        saved = None if quiet is None else quiet[0].clone()
+        try:
+            if quiet is not None:
+                quiet[0].fill_(quiet[1])
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):                       # warm-up outside capture (writes a scratch cache row, overwritten by the next real step)
+                self._launches(bound)
+            torch.cuda.current_stream().wait_stream(side)
+            cache.set_lengths(keep)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                out = self._launches(bound)
+            cache.lengths = keep                                 # capture records, it does not run: host mirror unchanged
+            self.graphs[bound] = (g, out)
+        except Exception as e:                                   # pragma: no cover - depends on the runtime
+            import warnings
+            warnings.warn(f"hipGraph capture of the {self.label} step failed ({e!r}); using eager launches")
+            self.capture_ok = False
+            self.graphs = {}
+            cache.set_lengths(keep)
+        if quiet is not None:
+            quiet[0].copy_(saved)
+
+    def _captured(self):
+        """The (graph, output) of the next step's bound, captured now if the bound is new; None: eager launches.  Refuses a full cache."""
+        if self.capture_ok:
+            bound = decode_kv_bound(self.cache)
+            if bound not in self.graphs:
+                self._capture(bound)
+        if not self.capture_ok:
+            return None
+        if self.cache.length >= self.cache.max_len:
+            raise ValueError(f"KV cache full ({self.cache.max_len} rows)")
+        return self.graphs[bound]
+
+    def _replay(self, entry):
+        entry[0].replay()
+        self.cache.lengths = [n + 1 for n in self.cache.lengths]
+        return entry[1]
+
+    def _step(self):
+        entry = self._captured()
+        return self._launches() if entry is None else self._replay(entry)
+
+    def _poll_loop(self, n_steps, after_step=None):
+        """Up to n_steps steps, launched blind; the device's count of live sequences is read every `poll` steps -- never after the last
+        step, the results are read then anyway -- and the first 0 ends the loop.  `host_reads` counts the reads, the final one included."""
+        for s in range(n_steps):
+            self._step()
+            self.steps += 1
+            if after_step is not None:
+                after_step(self)
+            if self.steps % self.poll == 0 and s + 1 < n_steps:
+                self.host_reads += 1
+                if int(self.live.item()) == 0:
+                    break
+        self.host_reads += 1
+
+
+class DecodeStepGraph(_CapturedStep):
+    """decoder_decode_row captured as a hipGraph (5 - 7 launches x layers per step collapse into one graph launch; the per-token step is
+    launch-bound otherwise) and replayed per token: copy the new rows (one per sequence) into `x_in`, replay, read `x_out`.  One capture
+    per attention bound (_CapturedStep), the first one made here."""
+
+    def __init__(self, layers, meta, cache, cos, sin, h, device):
+        super().__init__(layers, meta, cache, cos, sin)
+        self.x_in = torch.zeros((cache.batch, h), device=device, dtype=BF16)
         if self.capture_ok:
             self._capture(decode_kv_bound(cache))
 
@@ -1595,43 +1622,13 @@ class DecodeStepGraph:
     def graph(self):                                         # (tools / tests: "is the step a graph?")
         return next(iter(self.graphs.values()))[0] if self.graphs else None
 
-    def _capture(self, bound):
-        cache = self.cache
-        keep = list(cache.lengths)
-        try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):                       # warm-up outside capture (writes a scratch row, undone below)
-                decoder_decode_row(self.x_in, *self.args, kv_bound=bound)
-            torch.cuda.current_stream().wait_stream(side)
-            cache.set_lengths(keep)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                x_out = decoder_decode_row(self.x_in, *self.args, kv_bound=bound)
-            cache.lengths = keep                                 # capture records, it does not run: host mirror unchanged
-            self.graphs[bound] = (g, x_out)
-        except Exception as e:                                   # pragma: no cover - depends on the runtime
-            import warnings
-            warnings.warn(f"hipGraph capture of the decode step failed ({e!r}); using eager launches")
-            self.capture_ok = False
-            self.graphs = {}
-            cache.set_lengths(keep)
-
     def step(self, rows):
         """rows [batch, h] (one new row per sequence) -> their hidden rows [batch, h] (pre final norm; overwritten by the next step)"""
-        if self.capture_ok:
-            bound = decode_kv_bound(self.cache)
-            if bound not in self.graphs:
-                self._capture(bound)
-        if not self.capture_ok:
+        entry = self._captured()
+        if entry is None:
             return decoder_decode_row(rows.contiguous().view(self.cache.batch, -1), *self.args)
-        if self.cache.length >= self.cache.max_len:
-            raise ValueError(f"KV cache full ({self.cache.max_len} rows)")
-        g, x_out = self.graphs[bound]
         self.x_in.copy_(rows.view(self.cache.batch, -1))
-        g.replay()
-        self.cache.lengths = [n + 1 for n in self.cache.lengths]
-        return x_out
+        return self._replay(entry)
 
 
 GREEDY_STATE = ("in_image", "n_img", "total_out", "done", "n_tokens", "n_z")     # rows of GreedyLoopGraph.state, arguments of mm355_greedy_advance
@@ -1980,7 +1977,7 @@ class LogitsProcessors:
         return self.edits or bool(self.want_logprobs)
 
 
-class GreedyLoopGraph:
+class GreedyLoopGraph(_CapturedStep):
     """The greedy text-and-image loop (reference metamorph_llama.py:502-597) of a batch with the token loop on the device.  One step is
     decoder_decode_row (all rows, whatever route the batch size takes) -> `head` (the model's final norm, image head for ALL rows, row select
     by the device-resident mode, lm_head into the static fp32 `logits`) -> mm355_argmax_rows_f32 -> mm355_greedy_advance, which runs the
@@ -2002,6 +1999,7 @@ class GreedyLoopGraph:
     uint32 words, ~16 KB per sequence at 128 256 logits), `logp_log` [B, cap] fp32 the log-probability of every logged id under the
     PROCESSED logits (before temperature, top-k and top-p; with no processor editing, the model's own log-softmax); run() then returns them
     as a third list.  processors None (or nothing active in it): none of this is allocated or launched."""
+    label = "greedy"
 
     def __init__(self, layers, meta, cache, cos, sin, h, device, head, embed, C, Dz, start_id, end_id, num_image_tokens, max_new_tokens,
                  eos_ids, poll=8, sampler=None, processors=None):
@@ -2011,9 +2009,9 @@ class GreedyLoopGraph:
             raise ValueError(f"{C} logits over an embedding of {embed.shape[0]} rows: an argmax id would be no row of it")
         if int(poll) < 1:
             raise ValueError(f"mm355_greedy_poll_steps = {poll}: the live counter is read every poll >= 1 steps")
+        super().__init__(layers, meta, cache, cos, sin)
         B = cache.batch
-        self.args = (layers, meta, cache, cos, sin)
-        self.cache, self.head, self.embed, self.C = cache, head, embed, int(C)
+        self.head, self.embed, self.C = head, embed, int(C)
         self.max_new_tokens, self.poll = int(max_new_tokens), int(poll)
         self.scalars = (int(start_id), int(end_id), int(num_image_tokens), self.max_new_tokens, sorted(int(e) for e in eos_ids))
         cap = self.max_new_tokens + 1                        # iterations of the loop: total_out > max_new_tokens ends it
@@ -2039,8 +2037,6 @@ class GreedyLoopGraph:
         self.processors = processors if processors is not None and processors.active else None
         if self.processors is not None:
             self._init_processors(B, cap, device)
-        self.graphs = {}                                     # kv bound -> graph
-        self.capture_ok = VARIANTS["decode_graph"]
         self.host_reads = 0
         self.steps = 0
 
@@ -2088,59 +2084,15 @@ class GreedyLoopGraph:
         ops.greedy_advance(self.tok, self.C, self.state, self.live, self.embed, fed, pred_z, self.x_in, self.tok_log, self.z_log,
                            *self.scalars)
 
-    def _launches(self, bound=None):
-        self._tail(decoder_decode_row(self.x_in, *self.args, kv_bound=bound))
-
-    def _capture(self, bound):
-        cache = self.cache
-        keep = list(cache.lengths)
-        done = self.state[3].clone()
-        try:
-            self.state[3].fill_(1)                               # the warm-up runs for real: with every sequence done it logs and feeds nothing
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._launches(bound)
-            torch.cuda.current_stream().wait_stream(side)
-            cache.set_lengths(keep)                              # (the warm-up's scratch cache row is overwritten by the next real step)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._launches(bound)
-            cache.lengths = keep                                 # capture records, it does not run: host mirror unchanged
-            self.graphs[bound] = g
-        except Exception as e:                                   # pragma: no cover - depends on the runtime
-            import warnings
-            warnings.warn(f"hipGraph capture of the greedy step failed ({e!r}); using eager launches")
-            self.capture_ok = False
-            self.graphs = {}
-            cache.set_lengths(keep)
-        self.state[3].copy_(done)
-
-    def _step(self):
-        if self.capture_ok:
-            bound = decode_kv_bound(self.cache)
-            if bound not in self.graphs:
-                self._capture(bound)
-        if not self.capture_ok:
-            return self._launches()
-        if self.cache.length >= self.cache.max_len:
-            raise ValueError(f"KV cache full ({self.cache.max_len} rows)")
-        self.graphs[bound].replay()
-        self.cache.lengths = [n + 1 for n in self.cache.lengths]
+    def _quiet(self):
+        return self.state[3], 1                              # with every sequence done the warm-up logs and feeds nothing
 
     def run(self, x0):
         """x0 [B, h]: the prompt pass's last hidden row of every sequence (pre final norm).  The first iteration's head and advance run on
         it without a decoder step; then up to max_new_tokens steps.  Returns (ids, pred_z): per sequence its int32 ids and its [n_b, Dz]
         bf16 image rows; with processors.want_logprobs (ids, pred_z, logprobs): per sequence the fp32 log-probabilities of its ids."""
         self._tail(x0.contiguous())
-        for s in range(self.max_new_tokens):
-            self._step()
-            self.steps += 1
-            if self.steps % self.poll == 0 and s + 1 < self.max_new_tokens:
-                self.host_reads += 1
-                if int(self.live.item()) == 0:
-                    break
-        self.host_reads += 1
+        self._poll_loop(self.max_new_tokens)
         st = self.state.cpu()
         if not bool(st[3].all()):                               # pragma: no cover - max_new_tokens steps finish every sequence by construction
             raise RuntimeError(f"greedy loop: sequences still live after {self.steps} steps (state {st.tolist()})")
@@ -2154,7 +2106,7 @@ class GreedyLoopGraph:
 BEAM_STATE = ("running", "fin_score", "fin_flag", "fin_end", "scal", "live", "tok", "parent", "tok_log", "parent_log", "own_block")
 
 
-class BeamLoopGraph:
+class BeamLoopGraph(_CapturedStep):
     """HF's beam search (GenerationMixin._beam_search: one prompt, do_sample=False, no logits processors, tokens only) with the token loop
     on the device: GreedyLoopGraph's sibling.  The K beams are the K sequences of a cache whose prompt rows are stored once
     (KVCache.set_shared(L, own_rows=max_new_tokens + 1)); a beam's own rows stay where they were appended and the cache's table own_block
@@ -2166,6 +2118,7 @@ class BeamLoopGraph:
     max_new_tokens - 1 steps and reads `live` every `poll` steps (`host_reads` counts them, the final read of the results included).  A
     finished search rides along: mm355_beam_advance writes nothing for it, so the result does not depend on `poll`.
     head(x [K, h], logits_out f32 [K, C]).  run(x0) returns beam_hypotheses_host of the final pool."""
+    label = "beam"
 
     def __init__(self, layers, meta, cache, cos, sin, h, device, head, embed, C, max_new_tokens, eos_ids, length_penalty=1.0,
                  early_stopping=False, poll=8):
@@ -2187,8 +2140,8 @@ class BeamLoopGraph:
             raise ValueError(f"max_new_tokens = {max_new_tokens} must be >= 1 and {K} x {C} logits must hold the {self.M} candidates of a step")
         if cache.own_block is None or cache.own_block.shape[1] < self.max_new_tokens:
             raise ValueError("the beam loop runs on a cache with a table of own rows: KVCache.set_shared(L, own_rows=max_new_tokens + 1)")
-        self.args = (layers, meta, cache, cos, sin)
-        self.cache, self.head, self.embed = cache, head, embed
+        super().__init__(layers, meta, cache, cos, sin)
+        self.head, self.embed = head, embed
         self.eos, self.length_penalty, self.early_stopping = eos, float(length_penalty), BEAM_EARLY_STOPPING[early_stopping]
         host = beam_state_host(K, self.max_new_tokens)
         self.state = {n: (cache.own_block if n == "own_block" else torch.from_numpy(host[n]).to(device)) for n in BEAM_STATE}
@@ -2199,8 +2152,6 @@ class BeamLoopGraph:
         self.cand_val = torch.zeros(self.M, device=device, dtype=torch.float32)
         self.cand_idx = torch.zeros(self.M, device=device, dtype=torch.int32)
         self.sel_ws = ops.beam_select_rows_ws(K, self.C, self.M, device)
-        self.graphs = {}                                     # kv bound -> graph
-        self.capture_ok = VARIANTS["decode_graph"]
         self.host_reads = 0
         self.steps = 0
         self.on_tail = None                                  # (tests: called after every tail with the loop)
@@ -2215,45 +2166,8 @@ class BeamLoopGraph:
         ops.beam_advance(self.cand_val, self.cand_idx, self.C, self.state, self.len_pow, self.max_new_tokens, self.length_penalty,
                          self.early_stopping, self.eos, embed=self.embed, x_in=self.x_in)
 
-    def _launches(self, bound=None):
-        self._tail(decoder_decode_row(self.x_in, *self.args, kv_bound=bound))
-
-    def _capture(self, bound):
-        cache = self.cache
-        keep = list(cache.lengths)
-        live = self.live.clone()
-        try:
-            self.live.fill_(0)                                   # the warm-up runs for real: a search that is not live logs and feeds nothing
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._launches(bound)
-            torch.cuda.current_stream().wait_stream(side)
-            cache.set_lengths(keep)                              # (the warm-up's scratch cache row is overwritten by the next real step)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._launches(bound)
-            cache.lengths = keep                                 # capture records, it does not run: host mirror unchanged
-            self.graphs[bound] = g
-        except Exception as e:                                   # pragma: no cover - depends on the runtime
-            import warnings
-            warnings.warn(f"hipGraph capture of the beam step failed ({e!r}); using eager launches")
-            self.capture_ok = False
-            self.graphs = {}
-            cache.set_lengths(keep)
-        self.live.copy_(live)
-
-    def _step(self):
-        if self.capture_ok:
-            bound = decode_kv_bound(self.cache)
-            if bound not in self.graphs:
-                self._capture(bound)
-        if not self.capture_ok:
-            return self._launches()
-        if self.cache.length >= self.cache.max_len:
-            raise ValueError(f"KV cache full ({self.cache.max_len} rows)")
-        self.graphs[bound].replay()
-        self.cache.lengths = [n + 1 for n in self.cache.lengths]
+    def _quiet(self):
+        return self.live, 0                                  # a search that is not live logs and feeds nothing
 
     def run(self, x0):
         """x0 [K, h]: the prompt pass's last hidden row, K times (pre final norm): HF's step 0, whose running scores (0, -1e9, ...) let
@@ -2262,16 +2176,7 @@ class BeamLoopGraph:
         self._tail(x0.contiguous())
         if self.on_tail is not None:
             self.on_tail(self)
-        for s in range(self.max_new_tokens - 1):
-            self._step()
-            self.steps += 1
-            if self.on_tail is not None:
-                self.on_tail(self)
-            if self.steps % self.poll == 0 and s + 2 < self.max_new_tokens:
-                self.host_reads += 1
-                if int(self.live.item()) == 0:
-                    break
-        self.host_reads += 1
+        self._poll_loop(self.max_new_tokens - 1, self.on_tail)
         host = {n: t.cpu().numpy() for n, t in self.state.items()}
         if host["live"][0]:                                      # pragma: no cover - the step that generates id max_new_tokens ends every search
             raise RuntimeError(f"beam loop: the search is still live after {self.steps} steps (scal {host['scal'].tolist()})")

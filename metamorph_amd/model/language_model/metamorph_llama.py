@@ -810,11 +810,8 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         cos, sin = self.model.rope_tables(max_len, dev)
         meta.cos, meta.sin = cos, sin
         cache = F.KVCache(len(self.model.layers), max_len, meta.Hkv * meta.d, dev, Hq=meta.Hq, d=meta.d, fmt=self._kv_cache_format())
-        chunk = self._prefill_chunk_rows()
-        if chunk is None:
-            x = F.decoder_prefill(inputs_embeds.reshape(L0, h).contiguous(), self.model.layers, meta, cache)[-1:].contiguous()
-        else:
-            x = F.decoder_prefill_chunked(inputs_embeds.reshape(L0, h).contiguous(), self.model.layers, meta, cache, chunk)[-1:].contiguous()
+        x = F.decoder_prefill_chunked(inputs_embeds.reshape(L0, h).contiguous(), self.model.layers, meta, cache,
+                                      self._prefill_chunk_rows())[-1:].contiguous()
         stepper = F.DecodeStepGraph(self.model.layers, meta, cache, cos, sin, h, dev)
         in_image_mode = False
         generated, image_embeds = [], []
@@ -1187,6 +1184,21 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         return (out, torch.from_numpy(scores[:n_ret].copy()).to(dev)) if output_scores else out
 
     # ------------------------------------------------------------------ HF generate() on the decode kernels (reference :711-738)
+    def _new_kv_cache(self, cache, rows, batch, device):
+        """`cache.kv`: a fresh functional.KVCache of `batch` sequences for a prompt of `rows` rows (the HipKVCache's own capacity and
+        format, else rows + 1024 + 2 and the config's), and `cache.meta`, the geometry of its steps with the RoPE tables of that capacity.
+        Returns (meta, cos, sin)."""
+        cap = cache.capacity if cache.capacity is not None else rows + 1024 + 2
+        if cap < rows + 1:
+            raise ValueError(f"HipKVCache capacity {cap} is smaller than the prompt ({rows} rows)")
+        cos, sin = self.model.rope_tables(cap, device)
+        _, meta = self._decode_meta(rows)
+        meta.cos, meta.sin = cos, sin
+        cache.kv = F.KVCache(len(self.model.layers), cap, meta.Hkv * meta.d, device, Hq=meta.Hq, d=meta.d, batch=batch,
+                             fmt=self._kv_cache_format(cache.kv_format))
+        cache.meta = meta
+        return meta, cos, sin
+
     def _prefill_batch(self, seqs, cache, stepper=True, chunk=None):
         """Prompt pass of a batch: seqs = one [L_b, h] tensor of prompt rows per sequence (padding already stripped) -> their hidden rows
         (pre final norm), one [L_b, h] tensor each; allocates and fills `cache.kv` and captures the per-token step.  Prompts of one length
@@ -1197,15 +1209,7 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         B, h = len(seqs), seqs[0].shape[1]
         lens = [int(x.shape[0]) for x in seqs]
         L0 = max(lens)
-        cap = cache.capacity if cache.capacity is not None else L0 + 1024 + 2
-        if cap < L0 + 1:
-            raise ValueError(f"HipKVCache capacity {cap} is smaller than the prompt ({L0} rows)")
-        cos, sin = self.model.rope_tables(cap, dev)
-        _, meta = self._decode_meta(L0)
-        meta.cos, meta.sin = cos, sin
-        cache.kv = F.KVCache(len(self.model.layers), cap, meta.Hkv * meta.d, dev, Hq=meta.Hq, d=meta.d, batch=B,
-                             fmt=self._kv_cache_format(cache.kv_format))
-        cache.meta = meta
+        meta, cos, sin = self._new_kv_cache(cache, L0, B, dev)
         if B > 1 and all(n == L0 for n in lens) and (chunk is None or L0 <= chunk):
             _, mb = self._decode_meta(L0)
             mb.B, mb.cos, mb.sin = B, cos, sin
@@ -1216,10 +1220,7 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
             for b, x2d in enumerate(seqs):
                 _, mb = self._decode_meta(lens[b])
                 mb.cos, mb.sin = cos, sin
-                if chunk is None:
-                    out.append(F.decoder_prefill(x2d.contiguous(), self.model.layers, mb, cache.kv, row=b))
-                else:
-                    out.append(F.decoder_prefill_chunked(x2d.contiguous(), self.model.layers, mb, cache.kv, chunk, row=b))
+                out.append(F.decoder_prefill_chunked(x2d.contiguous(), self.model.layers, mb, cache.kv, chunk, row=b))
         if stepper:
             cache.stepper = F.DecodeStepGraph(self.model.layers, meta, cache.kv, cos, sin, h, dev)
         return out
@@ -1231,23 +1232,12 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         sequence's first rows (KVCache.set_shared); else they are copied into every sequence's block (KVCache.copy_prefix) and the step
         runs on the batch's attention.  own_rows (beam_decode, which has checked that the shared route applies): the columns of the
         table of own rows, KVCache.set_shared(L, own_rows=...)."""
-        dev = x2d.device
         L, h = int(x2d.shape[0]), x2d.shape[1]
-        cap = cache.capacity if cache.capacity is not None else L + 1024 + 2
-        if cap < L + 1:
-            raise ValueError(f"HipKVCache capacity {cap} is smaller than the prompt ({L} rows)")
-        cos, sin = self.model.rope_tables(cap, dev)
-        _, meta = self._decode_meta(L)
-        meta.cos, meta.sin = cos, sin
-        kv = cache.kv = F.KVCache(len(self.model.layers), cap, meta.Hkv * meta.d, dev, Hq=meta.Hq, d=meta.d, batch=n,
-                                  fmt=self._kv_cache_format(cache.kv_format))
-        cache.meta = meta
+        meta, cos, sin = self._new_kv_cache(cache, L, n, x2d.device)
+        kv = cache.kv
         _, mb = self._decode_meta(L)
         mb.cos, mb.sin = cos, sin
-        if chunk is None:
-            rows = F.decoder_prefill(x2d.contiguous(), self.model.layers, mb, kv, row=0)
-        else:
-            rows = F.decoder_prefill_chunked(x2d.contiguous(), self.model.layers, mb, kv, chunk, row=0)
+        rows = F.decoder_prefill_chunked(x2d.contiguous(), self.model.layers, mb, kv, chunk, row=0)
         if F.VARIANTS["shared_prefix_attn"] and ops.attn_decode_shared_supported(meta.Hq, meta.Hkv, meta.d):
             kv.set_lengths([L] * n)
             kv.set_shared(L, own_rows=own_rows)
@@ -1272,22 +1262,11 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         lens = [int(x.shape[0]) for x in seqs]
         L0 = max(lens)
         assert B > 1 and 1 <= S <= min(lens) - 1, (B, S, lens)
-        cap = cache.capacity if cache.capacity is not None else L0 + 1024 + 2
-        if cap < L0 + 1:
-            raise ValueError(f"HipKVCache capacity {cap} is smaller than the prompt ({L0} rows)")
-        cos, sin = self.model.rope_tables(cap, dev)
-        _, meta = self._decode_meta(L0)
-        meta.cos, meta.sin = cos, sin
-        kv = cache.kv = F.KVCache(len(self.model.layers), cap, meta.Hkv * meta.d, dev, Hq=meta.Hq, d=meta.d, batch=B,
-                                  fmt=self._kv_cache_format(cache.kv_format))
-        cache.meta = meta
+        meta, cos, sin = self._new_kv_cache(cache, L0, B, dev)
+        kv = cache.kv
         _, mb = self._decode_meta(S)
         mb.cos, mb.sin = cos, sin
-        prefix = seqs[0][:S].contiguous()
-        if chunk is None:
-            F.decoder_prefill(prefix, self.model.layers, mb, kv, row=0)
-        else:
-            F.decoder_prefill_chunked(prefix, self.model.layers, mb, kv, chunk, row=0)
+        F.decoder_prefill_chunked(seqs[0][:S].contiguous(), self.model.layers, mb, kv, chunk, row=0)
         if F.VARIANTS["shared_prefix_attn"] and ops.attn_extend_shared_supported(meta.Hq, meta.Hkv, meta.d):
             kv.set_lengths([S] * B)
             kv.set_shared(S)
