@@ -551,7 +551,7 @@ int mm355_attn_extend_f8(const mm355_bf16* q, int64_t ld_q, const uint8_t* k_cac
                          int64_t workspace_floats, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * The decode step's attention for B sequences whose first shared_len cached rows are the SAME rows, stored once (csrc/attn_decode_shared.hip):
+ * The decode step's attention for B sequences whose first shared_len cached rows are the SAME rows, stored once (csrc/attn_extend_shared.hip):
  * n sampled continuations of one prompt.
  *   attn_decode_shared: q [B][Hq*d] (ld_q), ALREADY rotated; k_shared / v_shared [shared_len][Hkv*d] (row stride ld_shared), one copy;
  *         k_cache / v_cache [B][rows][Hkv*d] as mm355_attn_decode takes them; kv_lens[B] int32 on the device; o [B][Hq*d] (ld_o).  Query row b

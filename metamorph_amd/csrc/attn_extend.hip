@@ -14,9 +14,9 @@
 // The e4m3 form differs in the tile mover alone: 8 bytes per 8 columns plus the head-row's scale, widened to bf16 (exact: mm355.h, the
 // KV8 contract) where the tile is written into LDS.  Everything after that is the same code on the same bits.
 // Cache rows >= past[b] + n are never read: ragged tiles clamp their row index to the last visible row of the workgroup.
-// The tile mover, the 64-key softmax step and the fold of the partials live in attn_tile.h, shared with attn_decode_shared.hip.
+// The pieces of the kernel (Q fragment, tile mover, softmax step, tile walk, partial record and its fold) and of the host side (key runs,
+// dispatch, common refusals) live in attn_tile.h, shared with attn_extend_shared.hip.
 #include "attn_tile.h"
-#include <algorithm>
 
 namespace {
 using namespace attn_tile;
@@ -47,8 +47,7 @@ Plan make_plan(int64_t B, int64_t n, int64_t Hq, int64_t Hkv, int64_t max_kv_len
 template <int DP, bool F8>
 __global__ __launch_bounds__(NT) void extend_kernel(XArgs a) {
     using G_ = Geo<DP>;
-    constexpr int KS = G_::KS, NF = G_::NF;
-    constexpr int NV = (G_::V64 + NT - 1) / NT;
+    constexpr int KS = G_::KS, NF = G_::NF, NV = tile_nv<DP>;
     constexpr int EPI = 4 * 16 * DP * 2;                    // bf16 output staging
     constexpr int SMEM = 2 * G_::T64 > EPI ? 2 * G_::T64 : EPI;
     __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM];
@@ -73,19 +72,15 @@ __global__ __launch_bounds__(NT) void extend_kernel(XArgs a) {
     const int wave_lo = past + min(qw0, R - 1) / G, wave_hi = past + min(qw0 + 15, R - 1) / G;
     const bool wave_on = qw0 < R;
 
-    bf16x8 qf[KS];                                           // B operand: Q[row = fr][d chunk]
+    bf16x8 qf[KS];
     {
         const uint16_t* qp = a.q + ((int64_t)b * n + qi) * a.ld_q + (int64_t)(hk * G + qg) * d;
 #pragma unroll
-        for (int kk = 0; kk < KS; ++kk) {
-            const int c = kk * 32 + fq * 8;
-            qf[kk] = (c < d) ? *(const bf16x8*)(qp + c) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        }
+        for (int kk = 0; kk < KS; ++kk) qf[kk] = load_q(qp, kk, d, fq);
     }
-    f32x4 ot[NF];                                            // O^T[d = j*16 + fq*4 + r][row = fr]
-    float m_run = -INFINITY, l_run = 0.f;
-#pragma unroll
-    for (int j = 0; j < NF; ++j) ot[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 ot[NF];
+    float m_run, l_run;
+    init_acc<DP>(ot, m_run, l_run);
 
     constexpr int EB = F8 ? 1 : 2;
     const unsigned char* kbase = a.k + (int64_t)b * a.bs_kv + (int64_t)hk * d * EB;
@@ -94,42 +89,17 @@ __global__ __launch_bounds__(NT) void extend_kernel(XArgs a) {
     const float* vsb = F8 ? a.vs + (int64_t)b * a.bs_sc + hk : nullptr;
     const float sl2 = a.scale * 1.4426950408889634f;         // scores in log2 domain: exp2(s*sl2 - m), the scale on the fp32 side
 
-    if (t0 < t1) {
-        Stage<NV, F8> rk, rv;
-        load_tile<DP, NV, F8>(rk, kbase, ksb, a.ld_kv, a.ld_sc, t0 * 64, kv_end, d, tid);
-        load_tile<DP, NV, F8>(rv, vbase, vsb, a.ld_kv, a.ld_sc, t0 * 64, kv_end, d, tid);
-        store_tile<DP, NV, F8>(rk, sK, tid);
-        store_tile<DP, NV, F8>(rv, sV, tid);
-        __syncthreads();
-        for (int t = t0; t < t1; ++t) {
-            const int kv0 = t * 64;
-            const bool more = t + 1 < t1;
-            if (more) {
-                load_tile<DP, NV, F8>(rk, kbase, ksb, a.ld_kv, a.ld_sc, kv0 + 64, kv_end, d, tid);
-                load_tile<DP, NV, F8>(rv, vbase, vsb, a.ld_kv, a.ld_sc, kv0 + 64, kv_end, d, tid);
-            }
-            if (wave_on && kv0 <= wave_hi)                   // a wave whose rows all precede this tile has nothing to do here
-                softmax_tile<DP>(sK, sV, qf, ot, m_run, l_run, kv0, kv0 + 63 > wave_lo, klim, sl2, fr, fq);
-            __syncthreads();                                 // every wave is done reading this tile
-            if (more) {
-                store_tile<DP, NV, F8>(rk, sK, tid);
-                store_tile<DP, NV, F8>(rv, sV, tid);
-                __syncthreads();
-            }
-        }
-    }
+    // the run's tiles; loads clamp at the workgroup's kv_end, not at the run's end
+    auto fetch = [&](Stage<NV, F8>& rk, Stage<NV, F8>& rv, int row0, int end) {
+        load_tile<DP, NV, F8>(rk, kbase, ksb, a.ld_kv, a.ld_sc, row0, end, d, tid);
+        load_tile<DP, NV, F8>(rv, vbase, vsb, a.ld_kv, a.ld_sc, row0, end, d, tid);
+    };
+    walk_tiles<DP, F8>(fetch, sK, sV, qf, ot, m_run, l_run, t0 * 64, t1 - t0, kv_end, wave_on, wave_lo, wave_hi, klim, sl2, tid, fr, fq);
 
     if (a.nsplit > 1) {                                      // partial: unnormalised O, reference maximum (log2 domain) and sum
-        if (qw0 + fr < R) {
-            const int64_t row = (((int64_t)b * a.Hkv + hk) * a.nsplit + split) * a.rpad + qw0 + fr;
-            float* po = a.ws + row * DP;
-#pragma unroll
-            for (int j = 0; j < NF; ++j) *(f32x4*)(po + j * 16 + fq * 4) = ot[j];
-            if (fq == 0) {
-                float* ml = a.ws + (int64_t)gridDim.z * a.Hkv * a.nsplit * a.rpad * DP + row * 2;
-                ml[0] = m_run; ml[1] = l_run;
-            }
-        }
+        if (qw0 + fr < R)
+            store_partial<DP>(a.ws, (int64_t)gridDim.z * a.Hkv * a.nsplit * a.rpad, (((int64_t)b * a.Hkv + hk) * a.nsplit + split) * a.rpad + qw0 + fr,
+                              ot, m_run, l_run, fq);
         return;
     }
     // epilogue: O = O^T / l -> bf16 [row][d] in LDS -> row-contiguous 16-B stores
@@ -178,41 +148,19 @@ int launch(const XArgs& a, int64_t B, hipStream_t s) {
     return mm_launch_status();
 }
 
-int pick_dp(int64_t d) { return d <= 64 ? 64 : (d <= 96 ? 96 : 128); }
-
 // eb = bytes per cached element (2: bf16, 1: e4m3); ld_kv / bs_kv arrive in BYTES
 int extend_impl(const mm355_bf16* q, int64_t ld_q, const void* k, const void* v, int64_t ld_kv, int64_t bs_kv, int eb, const float* ks,
                 const float* vs, int64_t ld_sc, int64_t bs_sc, const int32_t* past, int64_t n, int64_t max_kv_len, mm355_bf16* o, int64_t ld_o,
                 int64_t B, int64_t Hq, int64_t Hkv, int64_t d, float scale, float* ws, int64_t ws_floats, void* stream) {
-    if (!q || !k || !v || !past || !o || B <= 0 || n <= 0 || Hq <= 0 || Hkv <= 0 || (Hq % Hkv) || d <= 0 || max_kv_len <= 0 || n > max_kv_len ||
-        max_kv_len > 0x7fffffc0ll || n * (Hq / Hkv) > 0x7fffffc0ll || B > 65535 || Hkv > 65535)
-        return MM355_EINVAL;
-    if ((d & 7) || d > 128) return MM355_EUNSUPPORTED;
-    const uintptr_t amask = eb == 2 ? 15u : 7u;              // one 16-byte (bf16) or 8-byte (e4m3) load per 8 columns
-    if (!mm_aligned16(q) || !mm_aligned16(o) || (ld_q & 7) || (ld_o & 7) || ld_q < Hq * d || ld_o < Hq * d || (((uintptr_t)k | (uintptr_t)v) & amask) ||
-        (ld_kv & (int64_t)amask) || (bs_kv & (int64_t)amask) || ld_kv < Hkv * d * eb)
-        return MM355_EINVAL;
-    if (eb == 1 && (((((uintptr_t)ks) | ((uintptr_t)vs)) & 3u) || ld_sc < Hkv)) return MM355_EINVAL;
-    const int64_t G = Hq / Hkv;
-    if (G != 1 && G != 2 && G != 4 && G != 8) return MM355_EUNSUPPORTED;      // GQA group sizes 1, 2, 4, 8
+    const CacheRef own{k, v, ld_kv, bs_kv, ks, vs, ld_sc, bs_sc};
+    const bool shape_ok = past && B > 0 && n > 0 && Hq > 0 && Hkv > 0 && !(Hq % Hkv) && d > 0 && max_kv_len > 0 && n <= max_kv_len &&
+                          max_kv_len <= 0x7fffffc0ll && n * (Hq / Hkv) <= 0x7fffffc0ll && B <= 65535 && Hkv <= 65535;
+    if (const int rc = refuse(shape_ok, q, ld_q, o, ld_o, own, nullptr, eb, Hq, Hkv, d)) return rc;
     const Plan p = make_plan(B, n, Hq, Hkv, max_kv_len);
-    const int dp = pick_dp(d);
-    if (p.nsplit > 1 && (!ws || (((uintptr_t)ws) & 15u) || ws_floats < B * Hkv * p.nsplit * p.rpad * (dp + 2))) return MM355_EINVAL;
+    if (p.nsplit > 1 && (!ws || (((uintptr_t)ws) & 15u) || ws_floats < B * Hkv * p.nsplit * p.rpad * (pick_dp(d) + 2))) return MM355_EINVAL;
     XArgs a{q, ld_q, (const unsigned char*)k, (const unsigned char*)v, ld_kv, bs_kv, ks, vs, ld_sc, bs_sc, past, o, ld_o, ws,
             (int)n, (int)Hkv, (int)d, p.G, p.R, p.nqt, p.nsplit, p.tps, (int)max_kv_len, p.rpad, scale};
-    hipStream_t s = (hipStream_t)stream;
-    if (eb == 2) {
-        switch (dp) {
-            case 64: return launch<64, false>(a, B, s);
-            case 96: return launch<96, false>(a, B, s);
-            default: return launch<128, false>(a, B, s);
-        }
-    }
-    switch (dp) {
-        case 64: return launch<64, true>(a, B, s);
-        case 96: return launch<96, true>(a, B, s);
-        default: return launch<128, true>(a, B, s);
-    }
+    return dispatch(eb, d, [&](auto dp_, auto f8_) { return launch<decltype(dp_)::value, decltype(f8_)::value>(a, B, (hipStream_t)stream); });
 }
 
 }  // namespace

@@ -1,9 +1,12 @@
-// What attn_extend.hip, attn_decode_shared.hip and attn_extend_shared.hip share on top of attn2.h: the K / V tile mover (bf16 and e4m3 cache),
-// one 64-key step of the "swapped" online softmax (S^T = K Q^T, O^T += V^T P^T, log2 domain, deferred rescale), the fold of per-key-run
-// partials and the host rule that deals the key tiles to runs.
+// What attn_extend.hip and attn_extend_shared.hip share on top of attn2.h.  Device: the Q fragment and the accumulators of a lane, the K / V
+// tile mover (bf16 and e4m3 cache), one 64-key step of the "swapped" online softmax (S^T = K Q^T, O^T += V^T P^T, log2 domain, deferred
+// rescale), the double-buffered walk over a run of 64-key tiles, the store of a partial record and the fold of the partials of a row.  Host:
+// the rule that deals the key tiles to runs, the padded head size, the dispatch over (e4m3, padded head size) and the refusals every entry
+// point has.
 #pragma once
 #include "attn2.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace attn_tile {
 using namespace attn2;
@@ -16,6 +19,68 @@ inline void key_runs(int64_t nwg, int ktiles, int& nsplit, int& tps) {
     ns = std::min(ns, 64);
     tps = (ktiles + ns - 1) / ns;
     nsplit = (ktiles + tps - 1) / tps;
+}
+
+inline int pick_dp(int64_t d) { return d <= 64 ? 64 : (d <= 96 ? 96 : 128); }      // the padded head size the kernels are built for
+
+// launch(DP, F8) as compile-time constants for a cache of eb bytes per element and head size d: `launch` is a generic lambda that reads
+// decltype(dp)::value and decltype(f8)::value
+template <class Launch>
+int dispatch(int eb, int64_t d, Launch&& launch) {
+    using std::integral_constant;
+    using std::bool_constant;
+    const int dp = pick_dp(d);
+    if (eb == 2) {
+        switch (dp) {
+            case 64: return launch(integral_constant<int, 64>{}, bool_constant<false>{});
+            case 96: return launch(integral_constant<int, 96>{}, bool_constant<false>{});
+            default: return launch(integral_constant<int, 128>{}, bool_constant<false>{});
+        }
+    }
+    switch (dp) {
+        case 64: return launch(integral_constant<int, 64>{}, bool_constant<true>{});
+        case 96: return launch(integral_constant<int, 96>{}, bool_constant<true>{});
+        default: return launch(integral_constant<int, 128>{}, bool_constant<true>{});
+    }
+}
+
+// K / V rows as an entry point hands them over: row and block strides in BYTES (one block: bs 0), the e4m3 form with its scales [rows][Hkv]
+// and their strides
+struct CacheRef { const void* k; const void* v; int64_t ld, bs; const float* ks; const float* vs; int64_t ld_sc, bs_sc; };
+
+// The refusals every entry point has, after its own (`shape_ok`: the lengths array, the counts and their limits, Hq % Hkv == 0): NULL
+// pointers, d, q / o alignment and leading dimensions, cache and scale alignment by element width eb (2: bf16, 1: e4m3), the GQA group.
+// `shared` is the second set of rows of the shared-prefix forms, or NULL.
+inline int refuse(bool shape_ok, const void* q, int64_t ld_q, const void* o, int64_t ld_o, const CacheRef& own, const CacheRef* shared, int eb,
+                  int64_t Hq, int64_t Hkv, int64_t d) {
+    if (!shape_ok || !q || !o || !own.k || !own.v || (shared && (!shared->k || !shared->v))) return MM355_EINVAL;
+    if ((d & 7) || d > 128) return MM355_EUNSUPPORTED;
+    if (!mm_aligned16(q) || !mm_aligned16(o) || (ld_q & 7) || (ld_o & 7) || ld_q < Hq * d || ld_o < Hq * d) return MM355_EINVAL;
+    const uintptr_t amask = eb == 2 ? 15u : 7u;              // one 16-byte (bf16) or 8-byte (e4m3) load per 8 columns
+    for (const CacheRef* c : {&own, shared}) {
+        if (!c) continue;
+        if ((((uintptr_t)c->k | (uintptr_t)c->v) & amask) || ((c->ld | c->bs) & (int64_t)amask) || c->ld < Hkv * d * eb) return MM355_EINVAL;
+        if (eb == 1 && (((((uintptr_t)c->ks) | ((uintptr_t)c->vs)) & 3u) || c->ld_sc < Hkv)) return MM355_EINVAL;
+    }
+    const int64_t G = Hq / Hkv;
+    if (G != 1 && G != 2 && G != 4 && G != 8) return MM355_EUNSUPPORTED;      // GQA group sizes 1, 2, 4, 8
+    return MM355_OK;
+}
+
+template <int DP> constexpr int tile_nv = (Geo<DP>::V64 + NT - 1) / NT;        // 16-byte vectors of a 64-row tile per thread
+
+// chunk kk of this lane's Q fragment (the B operand: Q[row = fr][d chunk]) from its query row and head at qp; columns >= d are zero.  (The
+// loop over the chunks stays in the kernels: as one function over the whole fragment it costs the d = 96 kernels an occupancy step.)
+MM_DEV bf16x8 load_q(const uint16_t* qp, int kk, int d, int fq) {
+    const int c = kk * 32 + fq * 8;
+    return (c < d) ? *(const bf16x8*)(qp + c) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+}
+// no key seen yet: O^T[d = j*16 + fq*4 + r][row = fr] = 0, running maximum -inf, sum 0
+template <int DP>
+MM_DEV void init_acc(f32x4 (&ot)[Geo<DP>::NF], float& m_run, float& l_run) {
+    m_run = -INFINITY; l_run = 0.f;
+#pragma unroll
+    for (int j = 0; j < Geo<DP>::NF; ++j) ot[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
 template <int NV, bool F8> struct Stage;
@@ -153,6 +218,49 @@ MM_DEV void softmax_tile(const unsigned char* sK, const unsigned char* sV, const
             const bf16x8 va = read_nat_perm<DS>(sV, kk * 32, j, fr, fq);      // V^T[d][keys perm]
             ot[j] = mfma16(va, pb, ot[j]);
         }
+    }
+}
+
+// The workgroup's walk over the ntiles 64-key tiles from key k_lo, double buffered: fetch(rk, rv, row0, end) moves the K and V tiles at row0
+// into registers, clamping its rows at `end` (load_tile's rule; the indexed form plugs in here), while the waves run softmax_tile on the tile
+// in sK / sV.  A wave takes part in a tile while it is `wave_on` and the tile starts at or before wave_hi, the largest key limit of its rows;
+// the per-lane mask (key > klim) is looked at only in tiles that reach beyond wave_lo, the smallest one.  All threads of the workgroup call.
+template <int DP, bool F8, class Fetch>
+MM_DEV void walk_tiles(Fetch&& fetch, unsigned char* sK, unsigned char* sV, const bf16x8 (&qf)[Geo<DP>::KS], f32x4 (&ot)[Geo<DP>::NF],
+                       float& m_run, float& l_run, int k_lo, int ntiles, int end, bool wave_on, int wave_lo, int wave_hi, int klim, float sl2,
+                       int tid, int fr, int fq) {
+    constexpr int NV = tile_nv<DP>;
+    if (ntiles <= 0) return;
+    Stage<NV, F8> rk, rv;
+    fetch(rk, rv, k_lo, end);
+    store_tile<DP, NV, F8>(rk, sK, tid);
+    store_tile<DP, NV, F8>(rv, sV, tid);
+    __syncthreads();
+    for (int t = 0; t < ntiles; ++t) {
+        const int kv0 = k_lo + t * 64;
+        const bool more = t + 1 < ntiles;
+        if (more) fetch(rk, rv, kv0 + 64, end);
+        if (wave_on && kv0 <= wave_hi)                       // a wave whose rows all precede this tile has nothing to do here
+            softmax_tile<DP>(sK, sV, qf, ot, m_run, l_run, kv0, kv0 + 63 > wave_lo, klim, sl2, fr, fq);
+        __syncthreads();                                     // every wave is done reading this tile
+        if (more) {
+            store_tile<DP, NV, F8>(rk, sK, tid);
+            store_tile<DP, NV, F8>(rv, sV, tid);
+            __syncthreads();
+        }
+    }
+}
+
+// A lane's share of the partial record of packed row `row` in a workspace of `nrows` records: unnormalised fp32 O [nrows][DP], then the
+// reference maximum (log2 domain) and the sum [nrows][2]
+template <int DP>
+MM_DEV void store_partial(float* ws, int64_t nrows, int64_t row, const f32x4 (&ot)[Geo<DP>::NF], float m_run, float l_run, int fq) {
+    float* po = ws + row * DP;
+#pragma unroll
+    for (int j = 0; j < Geo<DP>::NF; ++j) *(f32x4*)(po + j * 16 + fq * 4) = ot[j];
+    if (fq == 0) {
+        float* ml = ws + nrows * DP + row * 2;
+        ml[0] = m_run; ml[1] = l_run;
     }
 }
 

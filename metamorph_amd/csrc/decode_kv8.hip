@@ -1,4 +1,4 @@
-// Writing an FP8 KV cache (gfx950; its readers: attn_decode.hip, attn_extend.hip, attn_decode_shared.hip).  One cached head-row -- the d
+// Writing an FP8 KV cache (gfx950; its readers: attn_decode.hip, attn_extend.hip, attn_extend_shared.hip).  One cached head-row -- the d
 // post-RoPE bf16 values of one KV head of one token -- is stored as d OCP e4m3fn bytes plus ONE fp32 scale:
 //   scale = the smallest power of two with amax / scale <= 448 (a head-row of zeros: 1),  q[c] = RNE_e4m3(x[c] / scale)
 // x / scale is an exponent shift (exact), nothing saturates, fp32(q[c]) * scale is exact and a bf16 value.  So every reader of the cache can

@@ -713,19 +713,53 @@ def attn_decode_f8(q, k8, v8, k_scale, v_scale, kv_lens, max_kv_len, Hq, Hkv, d,
 
 # ------------------------------------------------------------------------------------------------ extending a filled cache by n rows
 
-def _extend_args(q, past, n, max_kv_len, rows, Hq, Hkv, d, out, workspace):
-    B = past.shape[0]
+def _cache_attn_args(q, lens, n, max_kv_len, rows, Hq, Hkv, d, out, workspace, ws_floats, shared_len=None, shared_rows=None):
+    """What the cache-attention wrappers below hand to the C side: n query rows per sequence (None: the decode forms, one row and no such
+    argument), lens the entry point's int32 [B] (past or kv_lens), ws_floats the name of its mm355_*_ws_floats, shared_len / shared_rows
+    where a prefix is stored once.  -> (B, q pointer, ld, out, its pointer, ld, workspace or None, its floats)"""
+    B = lens.shape[0]
     pq, R, W, ldq = _rows2d(q)
-    assert q.dtype == BF16 and R == B * n and W == Hq * d, (q.shape, B, n, Hq, d)
-    assert past.dtype == torch.int32 and n <= max_kv_len <= rows, (n, max_kv_len, rows)
-    out = torch.empty((B * n, Hq * d), device=q.device, dtype=BF16) if out is None else out
+    nn, sh = (() if n is None else (n,)), (() if shared_len is None else (shared_len,))      # what the entry point takes of the two
+    assert q.dtype == BF16 and R == B * (n or 1) and W == Hq * d, (q.shape, B, *nn, Hq, d)
+    assert lens.dtype == torch.int32 and (n is None or n <= max_kv_len) and max_kv_len <= rows and \
+        (shared_len is None or 0 <= shared_len <= max_kv_len and shared_len <= shared_rows), (*nn, *sh, max_kv_len, rows)
+    out = torch.empty((R, W), device=q.device, dtype=BF16) if out is None else out
     po, Ro, Wo, ldo = _rows2d(out)
     assert out.dtype == BF16 and (Ro, Wo) == (R, W)
-    n_ws = int(_L().mm355_attn_extend_ws_floats(B, n, Hq, Hkv, d, max_kv_len))
+    n_ws = int(getattr(_L(), ws_floats)(B, *nn, Hq, Hkv, d, *sh, max_kv_len))
     ws = workspace
     if n_ws and (ws is None or ws.numel() < n_ws):
         ws = torch.empty(n_ws, device=q.device, dtype=torch.float32)
     return B, pq, ldq, out, po, ldo, ws, (0 if ws is None else ws.numel())
+
+
+def _bf16_cache(k, v, B, Hkv, d):
+    """k / v [>= B, rows, Hkv*d] bf16 with the same strides -> rows"""
+    assert k.dim() == 3 and k.dtype == BF16 and k.shape == v.shape and k.stride(2) == 1 and v.stride() == k.stride() and k.shape[2] == Hkv * d
+    assert k.shape[0] >= B
+    return k.shape[1]
+
+
+def _kv8_caches(k8, v8, k_scale, v_scale, B, Hkv, d):
+    """_kv8_cache() of two caches [>= B, rows, Hkv*d] with the same strides"""
+    assert k8.shape == v8.shape and k8.stride() == v8.stride() and k_scale.stride() == v_scale.stride() and k8.shape[0] >= B
+    _kv8_cache(v8, v_scale, Hkv, d)
+    return _kv8_cache(k8, k_scale, Hkv, d)
+
+
+def _shared_rows(k_shared, v_shared, Hkv, d, dtype=BF16):
+    """the prefix stored once: k_shared / v_shared [rows, Hkv*d] of `dtype` with the same strides -> rows"""
+    assert k_shared.dim() == 2 and k_shared.dtype == dtype and k_shared.shape == v_shared.shape and k_shared.stride() == v_shared.stride()
+    assert k_shared.stride(1) == 1 and k_shared.shape[1] == Hkv * d
+    return k_shared.shape[0]
+
+
+def _shared_rows_f8(k_shared, v_shared, k_shared_scale, v_shared_scale, Hkv, d):
+    """_shared_rows() of e4m3 bytes with their scales [rows, Hkv] f32"""
+    rows = _shared_rows(k_shared, v_shared, Hkv, d, torch.uint8)
+    assert k_shared_scale.dtype == torch.float32 and tuple(k_shared_scale.shape) == (rows, Hkv) and k_shared_scale.stride(1) == 1
+    assert v_shared_scale.dtype == torch.float32 and v_shared_scale.shape == k_shared_scale.shape and v_shared_scale.stride() == k_shared_scale.stride()
+    return rows
 
 
 def attn_extend(q, k, v, past, n, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None):
@@ -733,9 +767,8 @@ def attn_extend(q, k, v, past, n, max_kv_len, Hq, Hkv, d, scale, out=None, works
     a column block of a wider tensor); k / v [B, rows, Hkv*d] bf16 already holding the chunk's own rows at past[b] .. past[b]+n-1; past int32
     [B] on the device; max_kv_len a host bound with past[b] + n <= max_kv_len <= rows.  Row (b, i) attends the keys j <= past[b] + i."""
     _chk_dev(q, k, v, past, out)
-    assert k.dim() == 3 and k.dtype == BF16 and k.shape == v.shape and k.stride(2) == 1 and v.stride() == k.stride() and k.shape[2] == Hkv * d
-    assert k.shape[0] >= past.shape[0]
-    B, pq, ldq, out, po, ldo, ws, n_ws = _extend_args(q, past, n, max_kv_len, k.shape[1], Hq, Hkv, d, out, workspace)
+    rows = _bf16_cache(k, v, past.shape[0], Hkv, d)
+    B, pq, ldq, out, po, ldo, ws, n_ws = _cache_attn_args(q, past, n, max_kv_len, rows, Hq, Hkv, d, out, workspace, "mm355_attn_extend_ws_floats")
     _lib.check(_L().mm355_attn_extend(pq, ldq, k.data_ptr(), v.data_ptr(), k.stride(1), k.stride(0), past.data_ptr(), n, max_kv_len, po, ldo,
                                       B, Hq, Hkv, d, scale, _p(ws), n_ws, _stream()), f"mm355_attn_extend B={B} n={n} Hq={Hq} Hkv={Hkv} d={d}")
     return out
@@ -745,10 +778,9 @@ def attn_extend_f8(q, k8, v8, k_scale, v_scale, past, n, max_kv_len, Hq, Hkv, d,
     """attn_extend() over an e4m3 cache: k8 / v8 [B, rows, Hkv*d] uint8, k_scale / v_scale [B, rows, Hkv] f32 (mm355_attn_extend_f8): equal to
     attn_extend() on dequant_kv8() of the cache bit for bit."""
     _chk_dev(q, k8, v8, k_scale, v_scale, past, out)
-    assert k8.shape == v8.shape and k8.stride() == v8.stride() and k_scale.stride() == v_scale.stride() and k8.shape[0] >= past.shape[0]
-    ldb, bsb, ldsc, bssc = _kv8_cache(k8, k_scale, Hkv, d)
-    _kv8_cache(v8, v_scale, Hkv, d)
-    B, pq, ldq, out, po, ldo, ws, n_ws = _extend_args(q, past, n, max_kv_len, k8.shape[1], Hq, Hkv, d, out, workspace)
+    ldb, bsb, ldsc, bssc = _kv8_caches(k8, v8, k_scale, v_scale, past.shape[0], Hkv, d)
+    B, pq, ldq, out, po, ldo, ws, n_ws = _cache_attn_args(q, past, n, max_kv_len, k8.shape[1], Hq, Hkv, d, out, workspace,
+                                                          "mm355_attn_extend_ws_floats")
     _lib.check(_L().mm355_attn_extend_f8(pq, ldq, k8.data_ptr(), v8.data_ptr(), ldb, bsb, k_scale.data_ptr(), v_scale.data_ptr(), ldsc, bssc,
                                          KV8_E4M3, past.data_ptr(), n, max_kv_len, po, ldo, B, Hq, Hkv, d, scale, _p(ws), n_ws, _stream()),
                f"mm355_attn_extend_f8 B={B} n={n} Hq={Hq} Hkv={Hkv} d={d}")
@@ -760,21 +792,6 @@ def attn_extend_f8(q, k8, v8, k_scale, v_scale, past, n, max_kv_len, Hq, Hkv, d,
 def attn_decode_shared_supported(Hq, Hkv, d):
     """the head shapes mm355_attn_decode_shared takes (else MM355_EUNSUPPORTED): d % 8 == 0, d <= 128, a GQA group of 1, 2, 4 or 8"""
     return d % 8 == 0 and d <= 128 and Hq % Hkv == 0 and Hq // Hkv in (1, 2, 4, 8)
-
-
-def _shared_args(q, kv_lens, shared_len, max_kv_len, shared_rows, rows, Hq, Hkv, d, out, workspace):
-    B = kv_lens.shape[0]
-    pq, R, W, ldq = _rows2d(q)
-    assert q.dtype == BF16 and R == B and W == Hq * d, (q.shape, B, Hq, d)
-    assert kv_lens.dtype == torch.int32 and 0 <= shared_len <= max_kv_len <= rows and shared_len <= shared_rows, (shared_len, max_kv_len, rows)
-    out = torch.empty((B, Hq * d), device=q.device, dtype=BF16) if out is None else out
-    po, Ro, Wo, ldo = _rows2d(out)
-    assert out.dtype == BF16 and (Ro, Wo) == (R, W)
-    n_ws = int(_L().mm355_attn_decode_shared_ws_floats(B, Hq, Hkv, d, shared_len, max_kv_len))
-    ws = workspace
-    if n_ws and (ws is None or ws.numel() < n_ws):
-        ws = torch.empty(n_ws, device=q.device, dtype=torch.float32)
-    return B, pq, ldq, out, po, ldo, ws, (0 if ws is None else ws.numel())
 
 
 def _own_block(own_block, B):
@@ -793,12 +810,9 @@ def attn_decode_shared(q, k_shared, v_shared, k_cache, v_cache, kv_lens, shared_
     own_block (uint8 [B, columns] on the device; the beams of a beam search): own row j of query b is row j of block own_block[b, j -
     shared_len] (mm355_attn_decode_shared_idx); None is the identity."""
     _chk_dev(q, k_shared, v_shared, k_cache, v_cache, kv_lens, out, own_block)
-    assert k_cache.dim() == 3 and k_cache.dtype == BF16 and k_cache.shape == v_cache.shape and k_cache.stride(2) == 1
-    assert v_cache.stride() == k_cache.stride() and k_cache.shape[2] == Hkv * d and k_cache.shape[0] >= kv_lens.shape[0]
-    assert k_shared.dim() == 2 and k_shared.dtype == BF16 and k_shared.shape == v_shared.shape and k_shared.stride() == v_shared.stride()
-    assert k_shared.stride(1) == 1 and k_shared.shape[1] == Hkv * d
-    B, pq, ldq, out, po, ldo, ws, n_ws = _shared_args(q, kv_lens, shared_len, max_kv_len, k_shared.shape[0], k_cache.shape[1], Hq, Hkv, d, out,
-                                                      workspace)
+    rows, shared_rows = _bf16_cache(k_cache, v_cache, kv_lens.shape[0], Hkv, d), _shared_rows(k_shared, v_shared, Hkv, d)
+    B, pq, ldq, out, po, ldo, ws, n_ws = _cache_attn_args(q, kv_lens, None, max_kv_len, rows, Hq, Hkv, d, out, workspace,
+                                                          "mm355_attn_decode_shared_ws_floats", shared_len, shared_rows)
     if own_block is not None:
         pt, ldt = _own_block(own_block, B)
         _lib.check(_L().mm355_attn_decode_shared_idx(pq, ldq, k_shared.data_ptr(), v_shared.data_ptr(), k_shared.stride(0), k_cache.data_ptr(),
@@ -819,14 +833,10 @@ def attn_decode_shared_f8(q, k_shared, v_shared, k_shared_scale, v_shared_scale,
     rows, Hkv*d] uint8 with k_scale / v_scale [B, rows, Hkv] f32 (mm355_attn_decode_shared_f8): equal to attn_decode_shared() on dequant_kv8()
     of the same bytes bit for bit.  own_block: as for attn_decode_shared (mm355_attn_decode_shared_idx_f8), bytes and scales follow it."""
     _chk_dev(q, k_shared, v_shared, k_shared_scale, v_shared_scale, k8, v8, k_scale, v_scale, kv_lens, out, own_block)
-    assert k8.shape == v8.shape and k8.stride() == v8.stride() and k_scale.stride() == v_scale.stride() and k8.shape[0] >= kv_lens.shape[0]
-    ldb, bsb, ldsc, bssc = _kv8_cache(k8, k_scale, Hkv, d)
-    _kv8_cache(v8, v_scale, Hkv, d)
-    assert k_shared.dtype == torch.uint8 and k_shared.dim() == 2 and k_shared.shape == v_shared.shape and k_shared.stride() == v_shared.stride()
-    assert k_shared.stride(1) == 1 and k_shared.shape[1] == Hkv * d
-    assert k_shared_scale.dtype == torch.float32 and tuple(k_shared_scale.shape) == (k_shared.shape[0], Hkv) and k_shared_scale.stride(1) == 1
-    assert v_shared_scale.dtype == torch.float32 and v_shared_scale.shape == k_shared_scale.shape and v_shared_scale.stride() == k_shared_scale.stride()
-    B, pq, ldq, out, po, ldo, ws, n_ws = _shared_args(q, kv_lens, shared_len, max_kv_len, k_shared.shape[0], k8.shape[1], Hq, Hkv, d, out, workspace)
+    ldb, bsb, ldsc, bssc = _kv8_caches(k8, v8, k_scale, v_scale, kv_lens.shape[0], Hkv, d)
+    shared_rows = _shared_rows_f8(k_shared, v_shared, k_shared_scale, v_shared_scale, Hkv, d)
+    B, pq, ldq, out, po, ldo, ws, n_ws = _cache_attn_args(q, kv_lens, None, max_kv_len, k8.shape[1], Hq, Hkv, d, out, workspace,
+                                                          "mm355_attn_decode_shared_ws_floats", shared_len, shared_rows)
     if own_block is not None:
         pt, ldt = _own_block(own_block, B)
         _lib.check(_L().mm355_attn_decode_shared_idx_f8(pq, ldq, k_shared.data_ptr(), v_shared.data_ptr(), k_shared.stride(0),
@@ -851,22 +861,6 @@ def attn_extend_shared_supported(Hq, Hkv, d):
     return attn_decode_shared_supported(Hq, Hkv, d)
 
 
-def _extend_shared_args(q, past, n, shared_len, max_kv_len, shared_rows, rows, Hq, Hkv, d, out, workspace):
-    B = past.shape[0]
-    pq, R, W, ldq = _rows2d(q)
-    assert q.dtype == BF16 and R == B * n and W == Hq * d, (q.shape, B, n, Hq, d)
-    assert past.dtype == torch.int32 and n <= max_kv_len and 0 <= shared_len <= max_kv_len <= rows and shared_len <= shared_rows, \
-        (n, shared_len, max_kv_len, rows)
-    out = torch.empty((B * n, Hq * d), device=q.device, dtype=BF16) if out is None else out
-    po, Ro, Wo, ldo = _rows2d(out)
-    assert out.dtype == BF16 and (Ro, Wo) == (R, W)
-    n_ws = int(_L().mm355_attn_extend_shared_ws_floats(B, n, Hq, Hkv, d, shared_len, max_kv_len))
-    ws = workspace
-    if n_ws and (ws is None or ws.numel() < n_ws):
-        ws = torch.empty(n_ws, device=q.device, dtype=torch.float32)
-    return B, pq, ldq, out, po, ldo, ws, (0 if ws is None else ws.numel())
-
-
 def attn_extend_shared(q, k_shared, v_shared, k_cache, v_cache, past, n, shared_len, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None):
     """n new rows per sequence for B sequences whose first shared_len cached rows are the same rows, stored once (mm355_attn_extend_shared):
     q [B*n, Hq*d] bf16, already rotated, row (b, i) at b*n + i (may be a column block of a wider tensor); k_shared / v_shared [>= shared_len,
@@ -874,12 +868,9 @@ def attn_extend_shared(q, k_shared, v_shared, k_cache, v_cache, past, n, shared_
     device, past[b] >= shared_len; n, shared_len and max_kv_len host bounds.  Row (b, i) attends the shared rows and then rows [shared_len,
     past[b] + i] of block b.  Rows [0, shared_len) of the own blocks are never read."""
     _chk_dev(q, k_shared, v_shared, k_cache, v_cache, past, out)
-    assert k_cache.dim() == 3 and k_cache.dtype == BF16 and k_cache.shape == v_cache.shape and k_cache.stride(2) == 1
-    assert v_cache.stride() == k_cache.stride() and k_cache.shape[2] == Hkv * d and k_cache.shape[0] >= past.shape[0]
-    assert k_shared.dim() == 2 and k_shared.dtype == BF16 and k_shared.shape == v_shared.shape and k_shared.stride() == v_shared.stride()
-    assert k_shared.stride(1) == 1 and k_shared.shape[1] == Hkv * d
-    B, pq, ldq, out, po, ldo, ws, n_ws = _extend_shared_args(q, past, n, shared_len, max_kv_len, k_shared.shape[0], k_cache.shape[1], Hq, Hkv, d,
-                                                             out, workspace)
+    rows, shared_rows = _bf16_cache(k_cache, v_cache, past.shape[0], Hkv, d), _shared_rows(k_shared, v_shared, Hkv, d)
+    B, pq, ldq, out, po, ldo, ws, n_ws = _cache_attn_args(q, past, n, max_kv_len, rows, Hq, Hkv, d, out, workspace,
+                                                          "mm355_attn_extend_shared_ws_floats", shared_len, shared_rows)
     _lib.check(_L().mm355_attn_extend_shared(pq, ldq, k_shared.data_ptr(), v_shared.data_ptr(), k_shared.stride(0), k_cache.data_ptr(),
                                              v_cache.data_ptr(), k_cache.stride(1), k_cache.stride(0), past.data_ptr(), n, shared_len,
                                              max_kv_len, po, ldo, B, Hq, Hkv, d, scale, _p(ws), n_ws, _stream()),
@@ -893,15 +884,10 @@ def attn_extend_shared_f8(q, k_shared, v_shared, k_shared_scale, v_shared_scale,
     rows, Hkv*d] uint8 with k_scale / v_scale [B, rows, Hkv] f32 (mm355_attn_extend_shared_f8): equal to attn_extend_shared() on dequant_kv8()
     of the same bytes bit for bit."""
     _chk_dev(q, k_shared, v_shared, k_shared_scale, v_shared_scale, k8, v8, k_scale, v_scale, past, out)
-    assert k8.shape == v8.shape and k8.stride() == v8.stride() and k_scale.stride() == v_scale.stride() and k8.shape[0] >= past.shape[0]
-    ldb, bsb, ldsc, bssc = _kv8_cache(k8, k_scale, Hkv, d)
-    _kv8_cache(v8, v_scale, Hkv, d)
-    assert k_shared.dtype == torch.uint8 and k_shared.dim() == 2 and k_shared.shape == v_shared.shape and k_shared.stride() == v_shared.stride()
-    assert k_shared.stride(1) == 1 and k_shared.shape[1] == Hkv * d
-    assert k_shared_scale.dtype == torch.float32 and tuple(k_shared_scale.shape) == (k_shared.shape[0], Hkv) and k_shared_scale.stride(1) == 1
-    assert v_shared_scale.dtype == torch.float32 and v_shared_scale.shape == k_shared_scale.shape and v_shared_scale.stride() == k_shared_scale.stride()
-    B, pq, ldq, out, po, ldo, ws, n_ws = _extend_shared_args(q, past, n, shared_len, max_kv_len, k_shared.shape[0], k8.shape[1], Hq, Hkv, d, out,
-                                                             workspace)
+    ldb, bsb, ldsc, bssc = _kv8_caches(k8, v8, k_scale, v_scale, past.shape[0], Hkv, d)
+    shared_rows = _shared_rows_f8(k_shared, v_shared, k_shared_scale, v_shared_scale, Hkv, d)
+    B, pq, ldq, out, po, ldo, ws, n_ws = _cache_attn_args(q, past, n, max_kv_len, k8.shape[1], Hq, Hkv, d, out, workspace,
+                                                          "mm355_attn_extend_shared_ws_floats", shared_len, shared_rows)
     _lib.check(_L().mm355_attn_extend_shared_f8(pq, ldq, k_shared.data_ptr(), v_shared.data_ptr(), k_shared.stride(0), k_shared_scale.data_ptr(),
                                                 v_shared_scale.data_ptr(), k_shared_scale.stride(0), k8.data_ptr(), v8.data_ptr(), ldb, bsb,
                                                 k_scale.data_ptr(), v_scale.data_ptr(), ldsc, bssc, KV8_E4M3, past.data_ptr(), n, shared_len,

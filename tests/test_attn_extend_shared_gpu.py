@@ -26,7 +26,13 @@ CASES = [(1, 1, 2, 1, 128, 1, (0,)),                              # the smallest
          (5, 3, 8, 1, 40, 65, _ragged(5, 0, 70)),                 # G = 8, d below the padded width
          (2, 4, 8, 2, 128, 1100, (0, 9)),                         # the shared key split
          (4, 6, 4, 2, 96, 0, (1, 2, 0, 30)),                      # no shared rows
-         (17, 2, 8, 2, 128, 130, _ragged(17, 0, 90))]             # more than 16 sequences
+         (17, 2, 8, 2, 128, 130, _ragged(17, 0, 90)),             # more than 16 sequences
+         # n == 1, the decode-shared case, on each path of the row map
+         (3, 1, 4, 4, 64, 63, (0, 1, 63)),                        # G = 1, ragged shared tile
+         (5, 1, 8, 1, 40, 65, _ragged(5, 0, 70)),                 # G = 8, d below the padded width
+         (4, 1, 4, 2, 96, 0, (1, 2, 0, 30)),                      # d = 96, no shared rows
+         (17, 1, 8, 2, 128, 1100, _ragged(17, 0, 90)),            # the shared key split, two row tiles
+         (3, 1, 8, 2, 128, 513, (0, 0, 0))]                       # the own part is the one new row
 CASE_IDS = [f"{c[0]}-{c[1]}-{c[2]}-{c[3]}-{c[4]}-S{c[5]}" for c in CASES]
 PAD = 5                                                           # capacity = longest length + PAD
 
@@ -163,7 +169,7 @@ def test_attn_extend_shared_on_hostile_scores(ops, kind):
     close(got, ref, 2.0 ** -7, 2.0 ** -7, f"attn_extend_shared {kind}")
 
 
-@pytest.mark.parametrize("case", [CASES[2], CASES[4], CASES[5], CASES[6]], ids=[CASE_IDS[i] for i in (2, 4, 5, 6)])
+@pytest.mark.parametrize("case", [CASES[i] for i in (2, 4, 5, 6, 9, 11)], ids=[CASE_IDS[i] for i in (2, 4, 5, 6, 9, 11)])
 def test_attn_extend_shared_f8_equals_the_bf16_form_on_the_dequantised_cache(ops, case):
     B, n, Hq, Hkv, d, S, own = case
     past = [S + x for x in own]
@@ -185,6 +191,9 @@ def test_attn_extend_shared_f8_equals_the_bf16_form_on_the_dequantised_cache(ops
         got = ops.attn_extend_shared_f8(q, *D(ksh8, vsh8, kshs, vshs, k8, v8, ks, vs), pd, n, S, bound, Hq, Hkv, d, d ** -0.5)
         assert bool(torch.isfinite(got.float()).all()) and torch.equal(got, ref), (case, bound)
         assert torch.equal(ops.attn_extend_shared_f8(q, *D(ksh8, vsh8, kshs, vshs, k8, v8, ks, vs), pd, n, S, bound, Hq, Hkv, d, d ** -0.5), got)
+        if n == 1:                                                # the decode-shared case on the same bytes, bit for bit
+            lens = torch.tensor(ends, dtype=torch.int32, device=DEV)
+            assert torch.equal(ops.attn_decode_shared_f8(q, *D(ksh8, vsh8, kshs, vshs, k8, v8, ks, vs), lens, S, bound, Hq, Hkv, d, d ** -0.5), got)
 
 
 def test_no_shared_rows_is_the_extend_case(ops):

@@ -1,7 +1,8 @@
 """mm355_attn_decode_shared / mm355_attn_decode_shared_f8 on the device: one query row per sequence over P shared rows (stored once) followed
 by the sequence's own rows [P, kv_lens[b]).  Against the fp32 formula on the CPU at close(1e-2, 1e-2) (the bar of test_attn_extend_gpu.py)
 with everything the contract says is never read poisoned: rows [0, P) of every own block, shared rows >= P, own rows >= kv_lens[b].  On
-sink and cliff scores against fp64 at 2^-7; the e4m3 form bit for bit against the bf16 form on the dequantised bytes.
+sink and cliff scores against fp64 at 2^-7; the e4m3 form bit for bit against the bf16 form on the dequantised bytes; the indexed form over
+the identity table bit for bit against the call without a table, in both formats.
 Then the loop: n continuations of one prompt through generate(num_return_sequences=n) on the tiny fixture models -- the reference's
 recorded walk for every continuation on the shared and on the fan-out route, the draws against the host model, replay against eager
 launches, and what the two routes launch."""
@@ -35,6 +36,12 @@ CASES = [(1, 8, 2, 128, 1, (1,)),                                 # the smallest
          (3, 8, 2, 128, 513, (0, 0, 1))]                          # no own rows
 CASE_IDS = [f"{c[0]}-{c[1]}-{c[2]}-{c[3]}-P{c[4]}" for c in CASES]
 PAD = 5                                                           # capacity = longest length + PAD
+IDENTITY = (CASES[3], CASES[5])                                   # where the indexed form runs too, over the table that names every row's own block
+
+
+def _identity(case):
+    B, own = case[0], case[5]
+    return torch.arange(B, dtype=torch.uint8).view(B, 1).repeat(1, max(own) + 3).to(DEV)
 
 
 @pytest.fixture(scope="module")
@@ -113,6 +120,9 @@ def test_attn_decode_shared_against_the_formula(ops, case):
     cap = ops.attn_decode_shared(qd, ks, vs, kd, vd, ld, P, rows, Hq, Hkv, d, sc, workspace=ws)
     close(cap, ref, 1e-2, 1e-2, f"attn_decode_shared {case}, bound = capacity")
     assert torch.equal(ops.attn_decode_shared(qd, ks, vs, kd, vd, ld, P, rows, Hq, Hkv, d, sc, workspace=ws), cap)
+    if case in IDENTITY:                                          # the indexed form over the identity table: the same bits
+        assert torch.equal(ops.attn_decode_shared(qd, ks, vs, kd, vd, ld, P, max(lens), Hq, Hkv, d, sc, own_block=_identity(case)), got)
+        assert torch.equal(ops.attn_decode_shared(qd, ks, vs, kd, vd, ld, P, rows, Hq, Hkv, d, sc, own_block=_identity(case)), cap)
     # q and o as column views of a wider tensor (the q block of a fused q|k|v activation; an output block)
     wide_q = torch.full((B, Hq * d + 2 * Hkv * d), float("nan"), device=DEV, dtype=BF16)
     wide_q[:, :Hq * d] = qd
@@ -179,6 +189,10 @@ def test_attn_decode_shared_f8_equals_the_bf16_form_on_the_dequantised_cache(ops
         ref = ops.attn_decode_shared(q, *D(kshb, vshb, kb, vb), ld, P, bound, Hq, Hkv, d, d ** -0.5)
         got = ops.attn_decode_shared_f8(q, *D(ksh8, vsh8, kshs, vshs, k8, v8, ks, vs), ld, P, bound, Hq, Hkv, d, d ** -0.5)
         assert bool(torch.isfinite(got.float()).all()) and torch.equal(got, ref), (case, bound)
+        if case in IDENTITY:                                      # the indexed form over the identity table: the same bits
+            idx = ops.attn_decode_shared_f8(q, *D(ksh8, vsh8, kshs, vshs, k8, v8, ks, vs), ld, P, bound, Hq, Hkv, d, d ** -0.5,
+                                            own_block=_identity(case))
+            assert torch.equal(idx, got), (case, bound)
 
 
 # ------------------------------------------------------------------ the loop: n continuations of one prompt
