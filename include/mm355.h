@@ -551,6 +551,55 @@ int mm355_attn_extend_f8(const mm355_bf16* q, int64_t ld_q, const uint8_t* k_cac
                          int64_t workspace_floats, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Extending B filled (or empty) caches by DIFFERENT numbers of rows in one pass (csrc/attn_extend.hip): a ragged batch of prompts, or of
+ * follow-up turns, as one packed row block (reference: the cached generate() of metamorph_llama.py:502-597, run per sequence).
+ *   attn_extend_ragged: mm355_attn_extend with a row table in place of n.  row_start int32 [B + 1] on the device, non-decreasing: sequence b
+ *         brings n_b = row_start[b + 1] - row_start[b] query rows, at rows row_start[b] + i of q / o [q_rows][Hq*d] (packed, no padding rows).
+ *         The cache already holds them at past[b] .. past[b] + n_b - 1 of block b (the append comes first); row (b, i) attends the keys j <=
+ *         past[b] + i of block b; fp32 softmax, the scale on the fp32 side.  Right for n_b == 0 (nothing of that sequence is read or written,
+ *         its block included) and past[b] == 0 (a prompt).  n_max (host, >= every n_b) sizes the launch, the workspace
+ *         (mm355_attn_extend_ragged_ws_floats) and the split: they are mm355_attn_extend's for n = n_max, a function of (B, n_max, Hq, Hkv,
+ *         max_kv_len) alone, so with row_start[b] = b * n and n_max = n the output is mm355_attn_extend's bit for bit.  Workgroups whose row
+ *         tile lies beyond n_b * G leave at once, and the merge launch skips the same rows.  A wrong table stays inside the buffers: n_b is
+ *         clamped into [0, n_max], a row index into [0, q_rows), key rows below min(past[b] + n_b, max_kv_len); cache rows >= past[b] + n_b
+ *         are never read and o rows that belong to no sequence are never written.
+ *   attn_extend_ragged_f8: the same over an e4m3 cache; differs in the tile mover only: equal to the bf16 form on the dequantised cache bit
+ *         for bit.
+ *   Before any launch: mm355_attn_extend's refusals and codes (with n_max for n); a NULL row_start, n_max < 1, n_max > max_kv_len or q_rows < 1:
+ *   MM355_EINVAL.
+ * ------------------------------------------------------------------------------------------------ */
+int64_t mm355_attn_extend_ragged_ws_floats(int64_t B, int64_t n_max, int64_t Hq, int64_t Hkv, int64_t d, int64_t max_kv_len);
+int mm355_attn_extend_ragged(const mm355_bf16* q, int64_t ld_q, const mm355_bf16* k_cache, const mm355_bf16* v_cache, int64_t ld_kv,
+                             int64_t batch_stride_kv, const int32_t* past, const int32_t* row_start, int64_t n_max, int64_t q_rows,
+                             int64_t max_kv_len, mm355_bf16* o, int64_t ld_o, int64_t B, int64_t Hq, int64_t Hkv, int64_t d, float scale,
+                             float* workspace, int64_t workspace_floats, void* stream);
+int mm355_attn_extend_ragged_f8(const mm355_bf16* q, int64_t ld_q, const uint8_t* k_cache, const uint8_t* v_cache, int64_t ld_kv_bytes,
+                                int64_t batch_stride_kv_bytes, const float* k_scale, const float* v_scale, int64_t ld_scale,
+                                int64_t batch_stride_scale, int fmt, const int32_t* past, const int32_t* row_start, int64_t n_max,
+                                int64_t q_rows, int64_t max_kv_len, mm355_bf16* o, int64_t ld_o, int64_t B, int64_t Hq, int64_t Hkv,
+                                int64_t d, float scale, float* workspace, int64_t workspace_floats, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * RoPE + cache append with a block and a position PER ROW (csrc/decode.hip, csrc/decode_kv8.hip): the append of a packed ragged batch.
+ *   rope_kv_append_rows: mm355_rope_kv_append for R rows (on grid.x: R is not bound by 65535): row r of the fused qkv activation is rotated
+ *         at positions[r] (the same arithmetic and rounding order), q left in place, rotated k and v written to row positions[r] of block
+ *         blocks[r] of the caches [n_blocks][rows_per_block][Hkv*d].  blocks == NULL: block r for row r (needs n_blocks >= R), the bits of
+ *         mm355_rope_kv_append; with a table each row's result equals a one-row call of that kernel on its block.  blocks[r] is clamped into
+ *         [0, n_blocks) and positions[r] into [0, rows_per_block) (host bounds); no cache row other than the R named ones is written.
+ *   rope_kv_append_rows_f8: the twin over an e4m3 cache; quantises exactly as mm355_rope_kv_append_f8 does.
+ *   Before any launch: the refusals of mm355_rope_kv_append(_f8); n_blocks < 1 or rows_per_block < 1: MM355_EINVAL.
+ * ------------------------------------------------------------------------------------------------ */
+int mm355_rope_kv_append_rows(mm355_bf16* qkv, int64_t ld, int64_t R, int64_t Hq, int64_t Hkv, int64_t d, const mm355_bf16* cos_t,
+                              const mm355_bf16* sin_t, const int32_t* positions, const int32_t* blocks, int64_t n_blocks,
+                              int64_t rows_per_block, mm355_bf16* k_cache, mm355_bf16* v_cache, int64_t ld_kv, int64_t batch_stride_kv,
+                              void* stream);
+int mm355_rope_kv_append_rows_f8(mm355_bf16* qkv, int64_t ld, int64_t R, int64_t Hq, int64_t Hkv, int64_t d, const mm355_bf16* cos_t,
+                                 const mm355_bf16* sin_t, const int32_t* positions, const int32_t* blocks, int64_t n_blocks,
+                                 int64_t rows_per_block, uint8_t* k_cache, uint8_t* v_cache, int64_t ld_kv_bytes,
+                                 int64_t batch_stride_kv_bytes, float* k_scale, float* v_scale, int64_t ld_scale, int64_t batch_stride_scale,
+                                 int fmt, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * The decode step's attention for B sequences whose first shared_len cached rows are the SAME rows, stored once (csrc/attn_extend_shared.hip):
  * n sampled continuations of one prompt.
  *   attn_decode_shared: q [B][Hq*d] (ld_q), ALREADY rotated; k_shared / v_shared [shared_len][Hkv*d] (row stride ld_shared), one copy;

@@ -16,6 +16,11 @@
 // Cache rows >= past[b] + n are never read: ragged tiles clamp their row index to the last visible row of the workgroup.
 // The pieces of the kernel (Q fragment, tile mover, softmax step, tile walk, partial record and its fold) and of the host side (key runs,
 // dispatch, common refusals) live in attn_tile.h, shared with attn_extend_shared.hip.
+//
+// The ragged form (RAG; mm355_attn_extend_ragged) is the same kernel with a row table: sequence b brings n_b = row_start[b + 1] - row_start[b]
+// rows, packed at rows row_start[b] + i of q / o.  The launch is sized by the host bound n_max; n_b is clamped into [0, n_max], a row index
+// into [0, q_rows), and a workgroup whose row tile lies beyond n_b * G leaves before it reads anything of its sequence.  The plan is a
+// function of the launch arguments (n_max for n), so a uniform table runs the very workgroups of the plain form.
 #include "attn_tile.h"
 
 namespace {
@@ -26,6 +31,7 @@ struct XArgs {
     const unsigned char* k; const unsigned char* v; int64_t ld_kv, bs_kv;      // BYTES per cache row / per sequence
     const float* ks; const float* vs; int64_t ld_sc, bs_sc;                    // e4m3 form: scales [B][rows][Hkv]
     const int32_t* past; uint16_t* o; int64_t ld_o; float* ws;
+    const int32_t* row_start; int q_rows;                                      // ragged form: n below is n_max, R and nqt belong to it
     int n, Hkv, d, G, R, nqt, nsplit, tps, max_kv; int64_t rpad;
     float scale;
 };
@@ -44,7 +50,19 @@ Plan make_plan(int64_t B, int64_t n, int64_t Hq, int64_t Hkv, int64_t max_kv_len
     return p;
 }
 
-template <int DP, bool F8>
+// the rows of sequence b in the ragged form: n_b clamped into [0, n_max]; first = row_start[b]
+MM_DEV int ragged_rows(const XArgs& a, int b, int& first) {
+    first = a.row_start[b];
+    return (int)min(max((int64_t)a.row_start[b + 1] - first, (int64_t)0), (int64_t)a.n);
+}
+// row i of sequence b in q / o: b * n + i, or the table's row clamped into [0, q_rows)
+template <bool RAG>
+MM_DEV int64_t seq_row(const XArgs& a, int b, int n, int first, int i) {
+    if constexpr (RAG) return min(max((int64_t)first + i, (int64_t)0), (int64_t)a.q_rows - 1);
+    else return (int64_t)b * n + i;
+}
+
+template <int DP, bool F8, bool RAG>
 __global__ __launch_bounds__(NT) void extend_kernel(XArgs a) {
     using G_ = Geo<DP>;
     constexpr int KS = G_::KS, NF = G_::NF, NV = tile_nv<DP>;
@@ -58,9 +76,15 @@ __global__ __launch_bounds__(NT) void extend_kernel(XArgs a) {
     const int fr = lane & 15, fq = lane >> 4;
     const int qt = blockIdx.x / a.nsplit, split = blockIdx.x % a.nsplit;
     const int hk = blockIdx.y, b = blockIdx.z;
-    const int d = a.d, G = a.G, R = a.R, n = a.n;
-    const int past = a.past[b];
+    const int d = a.d, G = a.G;
     const int q0 = qt * 64, qw0 = q0 + wave * 16;
+    int R = a.R, n = a.n, first = 0;
+    if constexpr (RAG) {
+        n = ragged_rows(a, b, first);
+        R = n * G;
+        if (q0 >= R) return;                                 // (the whole workgroup: an empty sequence, a tile beyond its rows)
+    }
+    const int past = a.past[b];
     // last key (exclusive) any row of this workgroup sees; the host bound keeps a wrong past[] inside the cache
     const int kv_end = min(past + min(R - 1, q0 + 63) / G + 1, a.max_kv);
     const int ntiles = (kv_end + 63) >> 6;
@@ -74,7 +98,7 @@ __global__ __launch_bounds__(NT) void extend_kernel(XArgs a) {
 
     bf16x8 qf[KS];
     {
-        const uint16_t* qp = a.q + ((int64_t)b * n + qi) * a.ld_q + (int64_t)(hk * G + qg) * d;
+        const uint16_t* qp = a.q + seq_row<RAG>(a, b, n, first, qi) * a.ld_q + (int64_t)(hk * G + qg) * d;
 #pragma unroll
         for (int kk = 0; kk < KS; ++kk) qf[kk] = load_q(qp, kk, d, fq);
     }
@@ -118,49 +142,60 @@ __global__ __launch_bounds__(NT) void extend_kernel(XArgs a) {
         const int p = qw0 + r;
         if (p < R) {
             const int i = p / G, g = p - i * G;
-            *(u32x4*)(a.o + ((int64_t)b * n + i) * a.ld_o + (int64_t)(hk * G + g) * d + c) = *(const u32x4*)(so + r * (DP * 2) + c * 2);
+            *(u32x4*)(a.o + seq_row<RAG>(a, b, n, first, i) * a.ld_o + (int64_t)(hk * G + g) * d + c) = *(const u32x4*)(so + r * (DP * 2) + c * 2);
         }
     }
 }
 
 // o[row][4 columns] = sum_s 2^(m_s - M) O_s / sum_s 2^(m_s - M) l_s over the key runs of one packed row; a run that saw no key has m = -inf
-template <int DP>
+template <int DP, bool RAG>
 __global__ __launch_bounds__(NT) void extend_merge_kernel(XArgs a) {
     const int hk = blockIdx.y, b = blockIdx.z;
     const int idx = blockIdx.x * NT + threadIdx.x;
     const int p = idx / (DP / 4), c = (idx % (DP / 4)) * 4;
-    if (p >= a.R || c >= a.d) return;
+    int R = a.R, n = a.n, first = 0;
+    if constexpr (RAG) {                                     // the rows the first launch skipped have no partials
+        n = ragged_rows(a, b, first);
+        R = n * a.G;
+    }
+    if (p >= R || c >= a.d) return;
     const int64_t row0 = ((int64_t)b * a.Hkv + hk) * a.nsplit * a.rpad + p;
     const float* ml = a.ws + (int64_t)gridDim.z * a.Hkv * a.nsplit * a.rpad * DP;
     const u32x2 w = merge_partials<DP>(a.ws, ml, row0, a.rpad, a.nsplit, c);
     const int i = p / a.G, g = p - i * a.G;
-    *(u32x2*)(a.o + ((int64_t)b * a.n + i) * a.ld_o + (int64_t)(hk * a.G + g) * a.d + c) = w;
+    *(u32x2*)(a.o + seq_row<RAG>(a, b, n, first, i) * a.ld_o + (int64_t)(hk * a.G + g) * a.d + c) = w;
 }
 
-template <int DP, bool F8>
+template <int DP, bool F8, bool RAG>
 int launch(const XArgs& a, int64_t B, hipStream_t s) {
-    hipLaunchKernelGGL((extend_kernel<DP, F8>), dim3((unsigned)(a.nqt * a.nsplit), (unsigned)a.Hkv, (unsigned)B), dim3(NT), 0, s, a);
+    hipLaunchKernelGGL((extend_kernel<DP, F8, RAG>), dim3((unsigned)(a.nqt * a.nsplit), (unsigned)a.Hkv, (unsigned)B), dim3(NT), 0, s, a);
     if (a.nsplit > 1) {
         if (mm_launch_status() != MM355_OK) return MM355_ELAUNCH;
         const unsigned gx = (unsigned)(((int64_t)a.R * (DP / 4) + NT - 1) / NT);
-        hipLaunchKernelGGL((extend_merge_kernel<DP>), dim3(gx, (unsigned)a.Hkv, (unsigned)B), dim3(NT), 0, s, a);
+        hipLaunchKernelGGL((extend_merge_kernel<DP, RAG>), dim3(gx, (unsigned)a.Hkv, (unsigned)B), dim3(NT), 0, s, a);
     }
     return mm_launch_status();
 }
 
-// eb = bytes per cached element (2: bf16, 1: e4m3); ld_kv / bs_kv arrive in BYTES
+// eb = bytes per cached element (2: bf16, 1: e4m3); ld_kv / bs_kv arrive in BYTES.  row_start: the ragged form's table (then n is n_max and
+// q_rows the rows of q / o), NULL for the plain form
 int extend_impl(const mm355_bf16* q, int64_t ld_q, const void* k, const void* v, int64_t ld_kv, int64_t bs_kv, int eb, const float* ks,
-                const float* vs, int64_t ld_sc, int64_t bs_sc, const int32_t* past, int64_t n, int64_t max_kv_len, mm355_bf16* o, int64_t ld_o,
+                const float* vs, int64_t ld_sc, int64_t bs_sc, const int32_t* past, const int32_t* row_start, int64_t n, int64_t q_rows, int64_t max_kv_len,
+                mm355_bf16* o, int64_t ld_o,
                 int64_t B, int64_t Hq, int64_t Hkv, int64_t d, float scale, float* ws, int64_t ws_floats, void* stream) {
     const CacheRef own{k, v, ld_kv, bs_kv, ks, vs, ld_sc, bs_sc};
     const bool shape_ok = past && B > 0 && n > 0 && Hq > 0 && Hkv > 0 && !(Hq % Hkv) && d > 0 && max_kv_len > 0 && n <= max_kv_len &&
-                          max_kv_len <= 0x7fffffc0ll && n * (Hq / Hkv) <= 0x7fffffc0ll && B <= 65535 && Hkv <= 65535;
+                          max_kv_len <= 0x7fffffc0ll && n * (Hq / Hkv) <= 0x7fffffc0ll && B <= 65535 && Hkv <= 65535 && q_rows <= 0x7fffffffll;
     if (const int rc = refuse(shape_ok, q, ld_q, o, ld_o, own, nullptr, eb, Hq, Hkv, d)) return rc;
     const Plan p = make_plan(B, n, Hq, Hkv, max_kv_len);
     if (p.nsplit > 1 && (!ws || (((uintptr_t)ws) & 15u) || ws_floats < B * Hkv * p.nsplit * p.rpad * (pick_dp(d) + 2))) return MM355_EINVAL;
-    XArgs a{q, ld_q, (const unsigned char*)k, (const unsigned char*)v, ld_kv, bs_kv, ks, vs, ld_sc, bs_sc, past, o, ld_o, ws,
+    XArgs a{q, ld_q, (const unsigned char*)k, (const unsigned char*)v, ld_kv, bs_kv, ks, vs, ld_sc, bs_sc, past, o, ld_o, ws, row_start, (int)q_rows,
             (int)n, (int)Hkv, (int)d, p.G, p.R, p.nqt, p.nsplit, p.tps, (int)max_kv_len, p.rpad, scale};
-    return dispatch(eb, d, [&](auto dp_, auto f8_) { return launch<decltype(dp_)::value, decltype(f8_)::value>(a, B, (hipStream_t)stream); });
+    return dispatch(eb, d, [&](auto dp_, auto f8_) {
+        constexpr int DP = decltype(dp_)::value;
+        constexpr bool F8 = decltype(f8_)::value;
+        return row_start ? launch<DP, F8, true>(a, B, (hipStream_t)stream) : launch<DP, F8, false>(a, B, (hipStream_t)stream);
+    });
 }
 
 }  // namespace
@@ -176,8 +211,8 @@ extern "C" int mm355_attn_extend(const mm355_bf16* q, int64_t ld_q, const mm355_
                                  int64_t B, int64_t Hq, int64_t Hkv, int64_t d, float scale, float* workspace, int64_t workspace_floats,
                                  void* stream) {
     (void)hipGetLastError();
-    return extend_impl(q, ld_q, k_cache, v_cache, ld_kv * 2, batch_stride_kv * 2, 2, nullptr, nullptr, 0, 0, past, n, max_kv_len, o, ld_o, B, Hq, Hkv,
-                       d, scale, workspace, workspace_floats, stream);
+    return extend_impl(q, ld_q, k_cache, v_cache, ld_kv * 2, batch_stride_kv * 2, 2, nullptr, nullptr, 0, 0, past, nullptr, n, 0, max_kv_len, o, ld_o, B,
+                       Hq, Hkv, d, scale, workspace, workspace_floats, stream);
 }
 
 extern "C" int mm355_attn_extend_f8(const mm355_bf16* q, int64_t ld_q, const uint8_t* k_cache, const uint8_t* v_cache, int64_t ld_kv_bytes,
@@ -187,6 +222,31 @@ extern "C" int mm355_attn_extend_f8(const mm355_bf16* q, int64_t ld_q, const uin
                                     int64_t workspace_floats, void* stream) {
     (void)hipGetLastError();
     if (fmt != MM355_KV8_E4M3 || !k_scale || !v_scale) return MM355_EINVAL;
-    return extend_impl(q, ld_q, k_cache, v_cache, ld_kv_bytes, batch_stride_kv_bytes, 1, k_scale, v_scale, ld_scale, batch_stride_scale, past, n,
-                       max_kv_len, o, ld_o, B, Hq, Hkv, d, scale, workspace, workspace_floats, stream);
+    return extend_impl(q, ld_q, k_cache, v_cache, ld_kv_bytes, batch_stride_kv_bytes, 1, k_scale, v_scale, ld_scale, batch_stride_scale, past, nullptr, n,
+                       0, max_kv_len, o, ld_o, B, Hq, Hkv, d, scale, workspace, workspace_floats, stream);
+}
+
+extern "C" int64_t mm355_attn_extend_ragged_ws_floats(int64_t B, int64_t n_max, int64_t Hq, int64_t Hkv, int64_t d, int64_t max_kv_len) {
+    return mm355_attn_extend_ws_floats(B, n_max, Hq, Hkv, d, max_kv_len);
+}
+
+extern "C" int mm355_attn_extend_ragged(const mm355_bf16* q, int64_t ld_q, const mm355_bf16* k_cache, const mm355_bf16* v_cache, int64_t ld_kv,
+                                        int64_t batch_stride_kv, const int32_t* past, const int32_t* row_start, int64_t n_max, int64_t q_rows,
+                                        int64_t max_kv_len, mm355_bf16* o, int64_t ld_o, int64_t B, int64_t Hq, int64_t Hkv, int64_t d, float scale,
+                                        float* workspace, int64_t workspace_floats, void* stream) {
+    (void)hipGetLastError();
+    if (!row_start || n_max < 1 || q_rows < 1) return MM355_EINVAL;
+    return extend_impl(q, ld_q, k_cache, v_cache, ld_kv * 2, batch_stride_kv * 2, 2, nullptr, nullptr, 0, 0, past, row_start, n_max, q_rows, max_kv_len,
+                       o, ld_o, B, Hq, Hkv, d, scale, workspace, workspace_floats, stream);
+}
+
+extern "C" int mm355_attn_extend_ragged_f8(const mm355_bf16* q, int64_t ld_q, const uint8_t* k_cache, const uint8_t* v_cache, int64_t ld_kv_bytes,
+                                           int64_t batch_stride_kv_bytes, const float* k_scale, const float* v_scale, int64_t ld_scale,
+                                           int64_t batch_stride_scale, int fmt, const int32_t* past, const int32_t* row_start, int64_t n_max,
+                                           int64_t q_rows, int64_t max_kv_len, mm355_bf16* o, int64_t ld_o, int64_t B, int64_t Hq, int64_t Hkv,
+                                           int64_t d, float scale, float* workspace, int64_t workspace_floats, void* stream) {
+    (void)hipGetLastError();
+    if (fmt != MM355_KV8_E4M3 || !k_scale || !v_scale || !row_start || n_max < 1 || q_rows < 1) return MM355_EINVAL;
+    return extend_impl(q, ld_q, k_cache, v_cache, ld_kv_bytes, batch_stride_kv_bytes, 1, k_scale, v_scale, ld_scale, batch_stride_scale, past,
+                       row_start, n_max, q_rows, max_kv_len, o, ld_o, B, Hq, Hkv, d, scale, workspace, workspace_floats, stream);
 }

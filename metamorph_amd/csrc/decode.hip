@@ -910,19 +910,13 @@ int launch_gemv_deep(GemvMfmaArgs& g, int64_t units, bool prenorm, hipStream_t s
 // One new qkv row per sample: rotate q and k at position positions[b] (HF rounding order, as rope_qk_kernel), leave q in
 // place and write the rotated k and the v row into cache row positions[b].  Positions come from DEVICE memory so that the
 // whole per-token step is replayable as a hipGraph.
-__global__ __launch_bounds__(NT) void rope_kv_append_kernel(uint16_t* __restrict__ qkv, int64_t ld, int Hq, int Hkv, int d,
-                                                            const uint16_t* __restrict__ cos_t, const uint16_t* __restrict__ sin_t,
-                                                            const int32_t* __restrict__ positions, uint16_t* __restrict__ kc,
-                                                            uint16_t* __restrict__ vc, int64_t ld_kv, int64_t bs_kv) {
-    const int b = blockIdx.y;
-    const int pos = positions[b];
+// The items [i0, i0 + istep, ..) of one row: `row` rotated at `pos`, q in place, k -> krow, v -> vrow (the two cache rows of the row).
+MM_DEV void rope_kv_append_row(uint16_t* __restrict__ row, int pos, int Hq, int Hkv, int d, const uint16_t* __restrict__ cos_t,
+                               const uint16_t* __restrict__ sin_t, uint16_t* __restrict__ krow, uint16_t* __restrict__ vrow, int i0, int istep) {
     const int half = d >> 1, vph = half >> 3;
     const int H = Hq + Hkv;
-    uint16_t* row = qkv + (int64_t)b * ld;
-    uint16_t* krow = kc + (int64_t)b * bs_kv + (int64_t)pos * ld_kv;
-    uint16_t* vrow = vc + (int64_t)b * bs_kv + (int64_t)pos * ld_kv;
     const int rot = H * vph, cpy = Hkv * d / 8;
-    for (int i = blockIdx.x * NT + threadIdx.x; i < rot + cpy; i += gridDim.x * NT) {
+    for (int i = i0; i < rot + cpy; i += istep) {
         if (i < rot) {
             const int v = i % vph, hd = i / vph;
             uint16_t* p1 = row + (int64_t)hd * d + v * 8;
@@ -948,6 +942,30 @@ __global__ __launch_bounds__(NT) void rope_kv_append_kernel(uint16_t* __restrict
             *(u32x4*)(vrow + j * 8) = *(const u32x4*)(row + (int64_t)H * d + j * 8);
         }
     }
+}
+
+__global__ __launch_bounds__(NT) void rope_kv_append_kernel(uint16_t* __restrict__ qkv, int64_t ld, int Hq, int Hkv, int d,
+                                                            const uint16_t* __restrict__ cos_t, const uint16_t* __restrict__ sin_t,
+                                                            const int32_t* __restrict__ positions, uint16_t* __restrict__ kc,
+                                                            uint16_t* __restrict__ vc, int64_t ld_kv, int64_t bs_kv) {
+    const int b = blockIdx.y;
+    const int pos = positions[b];
+    rope_kv_append_row(qkv + (int64_t)b * ld, pos, Hq, Hkv, d, cos_t, sin_t, kc + (int64_t)b * bs_kv + (int64_t)pos * ld_kv,
+                       vc + (int64_t)b * bs_kv + (int64_t)pos * ld_kv, blockIdx.x * NT + threadIdx.x, gridDim.x * NT);
+}
+
+// The same per ROW of a packed batch: row r (grid.x: no 65535 bound) goes to row positions[r] of block blocks[r] (NULL: block r), both
+// clamped into the cache; the row's items are dealt over grid.y.
+__global__ __launch_bounds__(NT) void rope_kv_append_rows_kernel(uint16_t* __restrict__ qkv, int64_t ld, int Hq, int Hkv, int d,
+                                                                 const uint16_t* __restrict__ cos_t, const uint16_t* __restrict__ sin_t,
+                                                                 const int32_t* __restrict__ positions, const int32_t* __restrict__ blocks,
+                                                                 int n_blocks, int rows_per_block, uint16_t* __restrict__ kc,
+                                                                 uint16_t* __restrict__ vc, int64_t ld_kv, int64_t bs_kv) {
+    const int r = blockIdx.x;
+    const int pos = min(max(positions[r], 0), rows_per_block - 1);
+    const int blk = min(max(blocks ? blocks[r] : r, 0), n_blocks - 1);
+    rope_kv_append_row(qkv + (int64_t)r * ld, pos, Hq, Hkv, d, cos_t, sin_t, kc + (int64_t)blk * bs_kv + (int64_t)pos * ld_kv,
+                       vc + (int64_t)blk * bs_kv + (int64_t)pos * ld_kv, blockIdx.y * NT + threadIdx.x, gridDim.y * NT);
 }
 
 }  // namespace
@@ -1002,6 +1020,22 @@ extern "C" int mm355_rope_kv_append(mm355_bf16* qkv, int64_t ld, int64_t B, int6
     const int64_t work = (Hq + Hkv) * (d / 16) + Hkv * d / 8;
     hipLaunchKernelGGL(rope_kv_append_kernel, dim3((unsigned)((work + NT - 1) / NT), (unsigned)B), dim3(NT), 0, (hipStream_t)stream, qkv, ld,
                        (int)Hq, (int)Hkv, (int)d, cos_t, sin_t, positions, k_cache, v_cache, ld_kv, batch_stride_kv);
+    return mm_launch_status();
+}
+
+extern "C" int mm355_rope_kv_append_rows(mm355_bf16* qkv, int64_t ld, int64_t R, int64_t Hq, int64_t Hkv, int64_t d, const mm355_bf16* cos_t,
+                                         const mm355_bf16* sin_t, const int32_t* positions, const int32_t* blocks, int64_t n_blocks,
+                                         int64_t rows_per_block, mm355_bf16* k_cache, mm355_bf16* v_cache, int64_t ld_kv, int64_t batch_stride_kv,
+                                         void* stream) {
+    (void)hipGetLastError();
+    if (!qkv || !cos_t || !sin_t || !positions || !k_cache || !v_cache || R <= 0 || Hq <= 0 || Hkv <= 0 || d <= 0 || (d & 15) || (ld & 7) ||
+        (ld_kv & 7) || (batch_stride_kv & 7) || R > 0x7fffffffll || n_blocks < 1 || rows_per_block < 1 || n_blocks > 0x7fffffffll ||
+        rows_per_block > 0x7fffffffll || (!blocks && n_blocks < R))
+        return MM355_EINVAL;
+    const int64_t work = (Hq + Hkv) * (d / 16) + Hkv * d / 8;
+    hipLaunchKernelGGL(rope_kv_append_rows_kernel, dim3((unsigned)R, (unsigned)((work + NT - 1) / NT)), dim3(NT), 0, (hipStream_t)stream, qkv, ld,
+                       (int)Hq, (int)Hkv, (int)d, cos_t, sin_t, positions, blocks, (int)n_blocks, (int)rows_per_block, k_cache, v_cache, ld_kv,
+                       batch_stride_kv);
     return mm_launch_status();
 }
 

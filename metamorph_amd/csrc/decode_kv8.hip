@@ -55,17 +55,12 @@ __global__ __launch_bounds__(NT) void kv_quant_kernel(const uint16_t* __restrict
 // rope_kv_append_kernel with an e4m3 cache: blocks [0, nqb) rotate q in place (that kernel's items), the others take one K or V head-row per
 // 16-lane group: a lane rotates its own 8 columns (the partner half is a second load), rounds them to bf16 as the bf16 kernel stores them,
 // and the group quantises that row.
-__global__ __launch_bounds__(NT) void rope_kv_append_f8_kernel(uint16_t* __restrict__ qkv, int64_t ld, int Hq, int Hkv, int d,
-                                                               const uint16_t* __restrict__ cos_t, const uint16_t* __restrict__ sin_t,
-                                                               const int32_t* __restrict__ positions, uint8_t* __restrict__ kc,
-                                                               uint8_t* __restrict__ vc, int64_t ld_kv, int64_t bs_kv, float* __restrict__ ks,
-                                                               float* __restrict__ vs, int64_t ld_sc, int64_t bs_sc, int nqb) {
-    const int b = blockIdx.y;
-    const int pos = positions[b];
+MM_DEV void rope_kv_append_f8_row(uint16_t* __restrict__ row, int pos, int Hq, int Hkv, int d, const uint16_t* __restrict__ cos_t,
+                                  const uint16_t* __restrict__ sin_t, uint8_t* __restrict__ krow, uint8_t* __restrict__ vrow,
+                                  float* __restrict__ ksrow, float* __restrict__ vsrow, int nqb, int bx) {
     const int half = d >> 1, vph = half >> 3;
-    uint16_t* row = qkv + (int64_t)b * ld;
-    if ((int)blockIdx.x < nqb) {
-        const int i = blockIdx.x * NT + threadIdx.x;
+    if (bx < nqb) {
+        const int i = bx * NT + threadIdx.x;
         if (i >= Hq * vph) return;
         const int v = i % vph, hd = i / vph;
         uint16_t* p1 = row + (int64_t)hd * d + v * 8;
@@ -85,7 +80,7 @@ __global__ __launch_bounds__(NT) void rope_kv_append_f8_kernel(uint16_t* __restr
         return;
     }
     const int dc = threadIdx.x & 15;
-    const int grp = ((int)blockIdx.x - nqb) * (NT / 16) + (threadIdx.x >> 4);      // [0, Hkv): K heads, [Hkv, 2 Hkv): V heads
+    const int grp = (bx - nqb) * (NT / 16) + (threadIdx.x >> 4);      // [0, Hkv): K heads, [Hkv, 2 Hkv): V heads
     const bool live = grp < 2 * Hkv;
     const bool isv = grp >= Hkv;
     const int hk = live ? (isv ? grp - Hkv : grp) : 0;
@@ -113,9 +108,34 @@ __global__ __launch_bounds__(NT) void rope_kv_append_f8_kernel(uint16_t* __restr
     u32x2 q;
     const float sc = quant_headrow8(x, q);
     if (!live) return;
-    uint8_t* dst = (isv ? vc : kc) + (int64_t)b * bs_kv + (int64_t)pos * ld_kv + (int64_t)hk * d;
+    uint8_t* dst = (isv ? vrow : krow) + (int64_t)hk * d;
     if (on) *(u32x2*)(dst + dc * 8) = q;
-    if (dc == 0) (isv ? vs : ks)[(int64_t)b * bs_sc + (int64_t)pos * ld_sc + hk] = sc;
+    if (dc == 0) (isv ? vsrow : ksrow)[hk] = sc;
+}
+
+__global__ __launch_bounds__(NT) void rope_kv_append_f8_kernel(uint16_t* __restrict__ qkv, int64_t ld, int Hq, int Hkv, int d,
+                                                               const uint16_t* __restrict__ cos_t, const uint16_t* __restrict__ sin_t,
+                                                               const int32_t* __restrict__ positions, uint8_t* __restrict__ kc,
+                                                               uint8_t* __restrict__ vc, int64_t ld_kv, int64_t bs_kv, float* __restrict__ ks,
+                                                               float* __restrict__ vs, int64_t ld_sc, int64_t bs_sc, int nqb) {
+    const int b = blockIdx.y;
+    const int pos = positions[b];
+    const int64_t ob = (int64_t)b * bs_kv + (int64_t)pos * ld_kv, os = (int64_t)b * bs_sc + (int64_t)pos * ld_sc;
+    rope_kv_append_f8_row(qkv + (int64_t)b * ld, pos, Hq, Hkv, d, cos_t, sin_t, kc + ob, vc + ob, ks + os, vs + os, nqb, (int)blockIdx.x);
+}
+
+// rope_kv_append_rows_kernel (decode.hip) with an e4m3 cache: row r on grid.x, its q blocks and head-row groups on grid.y
+__global__ __launch_bounds__(NT) void rope_kv_append_rows_f8_kernel(uint16_t* __restrict__ qkv, int64_t ld, int Hq, int Hkv, int d,
+                                                                    const uint16_t* __restrict__ cos_t, const uint16_t* __restrict__ sin_t,
+                                                                    const int32_t* __restrict__ positions, const int32_t* __restrict__ blocks,
+                                                                    int n_blocks, int rows_per_block, uint8_t* __restrict__ kc,
+                                                                    uint8_t* __restrict__ vc, int64_t ld_kv, int64_t bs_kv, float* __restrict__ ks,
+                                                                    float* __restrict__ vs, int64_t ld_sc, int64_t bs_sc, int nqb) {
+    const int r = blockIdx.x;
+    const int pos = min(max(positions[r], 0), rows_per_block - 1);
+    const int blk = min(max(blocks ? blocks[r] : r, 0), n_blocks - 1);
+    const int64_t ob = (int64_t)blk * bs_kv + (int64_t)pos * ld_kv, os = (int64_t)blk * bs_sc + (int64_t)pos * ld_sc;
+    rope_kv_append_f8_row(qkv + (int64_t)r * ld, pos, Hq, Hkv, d, cos_t, sin_t, kc + ob, vc + ob, ks + os, vs + os, nqb, (int)blockIdx.y);
 }
 
 bool aligned8(const void* p) { return (((uintptr_t)p) & 7u) == 0; }
@@ -158,5 +178,29 @@ extern "C" int mm355_rope_kv_append_f8(mm355_bf16* qkv, int64_t ld, int64_t B, i
     hipLaunchKernelGGL(rope_kv_append_f8_kernel, dim3((unsigned)(nqb + nkb), (unsigned)B), dim3(NT), 0, (hipStream_t)stream, qkv, ld, (int)Hq,
                        (int)Hkv, (int)d, cos_t, sin_t, positions, k_cache, v_cache, ld_kv_bytes, batch_stride_kv_bytes, k_scale, v_scale, ld_scale,
                        batch_stride_scale, nqb);
+    return mm_launch_status();
+}
+
+extern "C" int mm355_rope_kv_append_rows_f8(mm355_bf16* qkv, int64_t ld, int64_t R, int64_t Hq, int64_t Hkv, int64_t d, const mm355_bf16* cos_t,
+                                            const mm355_bf16* sin_t, const int32_t* positions, const int32_t* blocks, int64_t n_blocks,
+                                            int64_t rows_per_block, uint8_t* k_cache, uint8_t* v_cache, int64_t ld_kv_bytes,
+                                            int64_t batch_stride_kv_bytes, float* k_scale, float* v_scale, int64_t ld_scale,
+                                            int64_t batch_stride_scale, int fmt, void* stream) {
+    (void)hipGetLastError();
+    if (fmt != MM355_KV8_E4M3 || !qkv || !cos_t || !sin_t || !positions || !k_cache || !v_cache || !k_scale || !v_scale || R <= 0 || Hq <= 0 ||
+        Hkv <= 0 || d <= 0 || R > 0x7fffffffll || n_blocks < 1 || rows_per_block < 1 || n_blocks > 0x7fffffffll || rows_per_block > 0x7fffffffll ||
+        (!blocks && n_blocks < R))
+        return MM355_EINVAL;
+    if ((d & 7) || d > 128) return MM355_EUNSUPPORTED;
+    if (d & 15) return MM355_EINVAL;
+    if ((ld & 7) || !mm_aligned16(qkv) || !mm_aligned16(cos_t) || !mm_aligned16(sin_t) || !aligned8(k_cache) || !aligned8(v_cache) ||
+        (ld_kv_bytes & 7) || (batch_stride_kv_bytes & 7) || ((((uintptr_t)k_scale) | ((uintptr_t)v_scale)) & 3u) || ld_kv_bytes < Hkv * d ||
+        ld_scale < Hkv)
+        return MM355_EINVAL;
+    const int nqb = (int)((Hq * (d / 16) + NT - 1) / NT);
+    const int nkb = (int)((2 * Hkv + NT / 16 - 1) / (NT / 16));
+    hipLaunchKernelGGL(rope_kv_append_rows_f8_kernel, dim3((unsigned)R, (unsigned)(nqb + nkb)), dim3(NT), 0, (hipStream_t)stream, qkv, ld, (int)Hq,
+                       (int)Hkv, (int)d, cos_t, sin_t, positions, blocks, (int)n_blocks, (int)rows_per_block, k_cache, v_cache, ld_kv_bytes,
+                       batch_stride_kv_bytes, k_scale, v_scale, ld_scale, batch_stride_scale, nqb);
     return mm_launch_status();
 }

@@ -60,7 +60,11 @@ VARIANTS = {"fuse_swiglu": True, "fuse_rope": True, "fuse_swiglu_bwd": True, "de
             # shared route (the prefix once + one decoder_extend_shared pass); below it the ordinary batch.  512: the smallest measured prefix
             # from which no cell of profiles/shared_prefix_batch.md loses -- at 1 / 16 / 128 shared rows two passes over the weights cost
             # more than the one batched prompt pass of prompts of equal length (0.56 - 0.90 x); an int S is taken at its word
-            "shared_prefix_min_rows": 512}
+            "shared_prefix_min_rows": 512,
+            # a model with config.mm355_ragged_pass = True: ragged prompts, and follow-up turns of B > 1 sequences, as ONE packed pass over the
+            # weights with mm355_attn_extend_ragged (decoder_extend_ragged); off: one sequence after the other, as without the config field.
+            # The tools' switch for same-process A/B runs (profiles/ragged_pass.md); the config field, default off, is the product's
+            "ragged_pass_attn": True}
 
 
 def set_variant(name, value):
@@ -1160,6 +1164,102 @@ def decoder_extend_shared(x, layers, meta, cache, past=None):
         x = _plain_walk(x, layers, meta, splitk, append_attend)
     cache.set_lengths([p + n for p in past])
     return x.view(B, n, h)
+
+
+RaggedRowsPlan = namedtuple("RaggedRowsPlan", "row_start positions blocks past n_max bound")
+
+
+def ragged_rows_plan(lens, past, rows):
+    """The tables of one packed pass (host, numpy): sequence rows[j] of a cache holds past[j] rows and brings lens[j] >= 1 new ones.  The
+    packed rows stand in BLOCK order (the sequences sorted by rows[j]), as mm355_attn_extend_ragged's non-decreasing table needs them.
+    With B = max(rows) + 1 blocks and R = sum(lens) rows -> row_start int32 [B + 1] (a block that is not named brings no row), past int32 [B]
+    (0 for such a block), positions int32 [R] (past + i of the row's sequence: its RoPE position and its cache row), blocks int32 [R] (its
+    block), n_max = max(lens) and bound = max(past[j] + lens[j]), the two host bounds of the launch."""
+    lens, past, rows = [int(n) for n in lens], [int(p) for p in past], [int(b) for b in rows]
+    if not lens or len(past) != len(lens) or len(rows) != len(lens):
+        raise ValueError(f"ragged_rows_plan: {len(lens)} row counts, {len(past)} cached lengths and {len(rows)} sequences: one of each per entry, at least one entry")
+    if min(lens) < 1:
+        raise ValueError(f"ragged_rows_plan: an entry without new rows ({lens}): leave the sequence out instead")
+    if min(past) < 0 or min(rows) < 0 or len(set(rows)) != len(rows):
+        raise ValueError(f"ragged_rows_plan: sequences {rows} holding {past} rows: distinct sequences, no negative index or length")
+    B = max(rows) + 1
+    n_b, past_b = np.zeros(B, np.int64), np.zeros(B, np.int32)
+    n_b[rows], past_b[rows] = lens, past
+    row_start = np.zeros(B + 1, np.int64)
+    np.cumsum(n_b, out=row_start[1:])
+    blocks = np.repeat(np.arange(B, dtype=np.int32), n_b)
+    positions = (np.arange(row_start[-1]) - row_start[blocks] + past_b[blocks]).astype(np.int32)
+    return RaggedRowsPlan(row_start.astype(np.int32), positions, blocks, past_b, max(lens), max(p + n for p, n in zip(past, lens)))
+
+
+def ragged_pass_supported(meta):
+    """the head shapes decoder_extend_ragged takes: those of mm355_attn_extend_ragged with d % 16 == 0 (mm355_rope_kv_append_rows)"""
+    return ops.attn_extend_ragged_supported(meta.Hq, meta.Hkv, meta.d) and meta.d % 16 == 0
+
+
+def decoder_extend_ragged(xs, layers, meta, cache, rows=None):
+    """New rows of SEVERAL sequences of one cache, a different number each, in ONE pass over the weights: xs = a list of [n_j, h] bf16
+    tensors, n_j >= 1, the new rows of the distinct sequences rows[j] (default: all sequences, in order) -> their hidden rows (pre final
+    norm), one [n_j, h] tensor each.  Sequence rows[j] holds past_j = cache.lengths[rows[j]] rows -- 0 is allowed: a prompt -- and
+    afterwards past_j + n_j.  A ragged batch of prompts, or the follow-up turns of a batch.
+    The sum(n_j) rows run packed, without padding rows (ragged_rows_plan), through decoder_extend_shared's two routes, chosen and routed
+    (w8_route, W8Scratch, the split-K limits) on the packed row count; the attention step is the plain split projection, ONE
+    mm355_rope_kv_append_rows launch (RoPE at the row's position, k and v into its row of its block) and ONE mm355_attn_extend_ragged call
+    over the cache, which then holds the new rows; the workspace is made once per pass.  An fp8_e4m3 cache is read back quantised, as
+    decoder_extend reads it: every row sees the quantised form of all rows, its own included.  A PROMPT on this route therefore has the
+    semantics of the later slices of decoder_prefill_chunked, not of decoder_prefill, whose rows attend the unquantised K / V of the
+    pass; on a bf16 cache the two agree up to the order of the sums."""
+    xs = list(xs)
+    rows = list(range(cache.batch)) if rows is None else [int(b) for b in rows]
+    if cache.shared_len > 0:
+        raise ValueError(f"decoder_extend_ragged on a cache with a shared prefix of {cache.shared_len} rows: sequences 1.. do not hold the "
+                         "prefix; their own rows go through decoder_extend_shared")
+    if not xs or len(xs) != len(rows):
+        raise ValueError(f"decoder_extend_ragged: {len(xs)} row blocks for {len(rows)} sequences")
+    if len(set(rows)) != len(rows) or min(rows) < 0 or max(rows) >= cache.batch:
+        raise ValueError(f"decoder_extend_ragged: sequences {rows} of a cache of {cache.batch}: distinct sequences of the cache")
+    h = xs[0].shape[-1]
+    if any(x.dim() != 2 or x.shape[0] < 1 or x.shape[1] != h or x.dtype != BF16 for x in xs):
+        raise ValueError(f"decoder_extend_ragged takes [n_j, {h}] bf16 tensors with n_j >= 1, got {[(tuple(x.shape), x.dtype) for x in xs]}")
+    if not ragged_pass_supported(meta):
+        raise ValueError(f"decoder_extend_ragged: no kernel for Hq={meta.Hq} Hkv={meta.Hkv} d={meta.d} (ops.attn_extend_ragged_supported, "
+                         "d % 16 == 0)")
+    lens = [int(x.shape[0]) for x in xs]
+    plan = ragged_rows_plan(lens, [cache.lengths[b] for b in rows], rows)
+    if plan.bound > cache.max_len:
+        raise ValueError(f"KV cache capacity of {cache.max_len} rows is too small for {plan.bound} rows (cached + new) of one sequence")
+    if torch.is_grad_enabled():
+        raise RuntimeError("decoder_extend_ragged is an inference pass (torch.no_grad())")
+    dev = xs[0].device
+    x = torch.cat([xs[j] for j in sorted(range(len(rows)), key=rows.__getitem__)], 0)      # block order
+    R = x.shape[0]
+    B = plan.past.shape[0]
+    tables = torch.from_numpy(np.concatenate([plan.row_start, plan.past, plan.positions, plan.blocks])).to(dev)      # one copy
+    row_start, past_dev, pos, blk = tables[:B + 1], tables[B + 1:2 * B + 1], tables[2 * B + 1:2 * B + 1 + R], tables[2 * B + 1 + R:]
+    H = (meta.Hq, meta.Hkv, meta.d)
+    nq = meta.Hq * meta.d
+    n_ws = int(ops._L().mm355_attn_extend_ragged_ws_floats(B, plan.n_max, *H, plan.bound))
+    ws = torch.empty(max(n_ws, 4), device=dev, dtype=torch.float32)
+
+    def append_attend(qkv, i):                                # rotation + (quantising) append per row, attention over the cache rows
+        k, v = cache.k[i], cache.v[i]
+        if cache.kv8 is not None:
+            ks, vs = cache.k_scale[i], cache.v_scale[i]
+            ops.rope_kv_append_rows_f8_(qkv, *H, meta.cos, meta.sin, pos, blk, k, v, ks, vs)
+            return ops.attn_extend_ragged_f8(qkv[:, :nq], k, v, ks, vs, past_dev, row_start, plan.n_max, plan.bound, *H, meta.scale, workspace=ws)
+        ops.rope_kv_append_rows_(qkv, *H, meta.cos, meta.sin, pos, blk, k, v)
+        return ops.attn_extend_ragged(qkv[:, :nq], k, v, past_dev, row_start, plan.n_max, plan.bound, *H, meta.scale, workspace=ws)
+
+    splitk = VARIANTS["prefill_splitk"] and R <= 4096
+    if splitk and VARIANTS["prefill_fused"] and ops.gemm_splitk_splits(R, (meta.Hq + 2 * meta.Hkv) * meta.d, h):
+        x = _fused_walk(x, layers, meta, lambda qkv, i: append_attend(qkv("gemm", ops.gemm_splitk), i), prompt=True)
+    else:
+        x = _plain_walk(x, layers, meta, splitk, append_attend)
+    new = list(cache.lengths)
+    for b, n in zip(rows, lens):
+        new[b] += n
+    cache.set_lengths(new)
+    return [x[int(plan.row_start[b]):int(plan.row_start[b]) + n] for b, n in zip(rows, lens)]
 
 
 def decoder_prefill_chunked(x, layers, meta, cache, chunk, row=0):

@@ -796,6 +796,15 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
                 raise ValueError(f"config.mm355_prefill_chunk_rows = {n}: a prompt is run in slices of at least 1 row (None: in one pass)")
         return None if n is None else int(n)
 
+    def _ragged_pass(self, meta):
+        """Whether a ragged batch of prompts, and a follow-up turn of B > 1 sequences, runs as one packed pass
+        (functional.decoder_extend_ragged): config.mm355_ragged_pass (a bool; absent: False), and then functional.VARIANTS["ragged_pass_attn"]
+        and a head shape the pass takes."""
+        on = getattr(self.config, "mm355_ragged_pass", False)
+        if not isinstance(on, bool):
+            raise ValueError(f"config.mm355_ragged_pass = {on!r}: True or False (absent: False)")
+        return on and F.VARIANTS["ragged_pass_attn"] and F.ragged_pass_supported(meta)
+
     def _greedy_decode_cached(self, inputs_embeds, start_image_token_id, end_image_token_id, eos_token_id, max_new_tokens,
                               output_image):
         assert inputs_embeds.shape[0] == 1                     # (a batch takes _greedy_decode_loop)
@@ -1202,7 +1211,8 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
     def _prefill_batch(self, seqs, cache, stepper=True, chunk=None):
         """Prompt pass of a batch: seqs = one [L_b, h] tensor of prompt rows per sequence (padding already stripped) -> their hidden rows
         (pre final norm), one [L_b, h] tensor each; allocates and fills `cache.kv` and captures the per-token step.  Prompts of one length
-        (the beams of a beam search, an unpadded batch) go through the decoder as ONE batch; ragged prompts one after the other.
+        (the beams of a beam search, an unpadded batch) go through the decoder as ONE batch; ragged prompts one after the other -- or, with
+        config.mm355_ragged_pass = True and no chunking, packed into ONE functional.decoder_extend_ragged pass on the fresh cache.
         stepper=False: no DecodeStepGraph is captured (the greedy loop brings its own step); chunk: rows per slice of a chunked prompt pass
         (functional.decoder_prefill_chunked), one sequence after the other."""
         dev = seqs[0].device
@@ -1210,11 +1220,14 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         lens = [int(x.shape[0]) for x in seqs]
         L0 = max(lens)
         meta, cos, sin = self._new_kv_cache(cache, L0, B, dev)
+        ragged = self._ragged_pass(meta)
         if B > 1 and all(n == L0 for n in lens) and (chunk is None or L0 <= chunk):
             _, mb = self._decode_meta(L0)
             mb.B, mb.cos, mb.sin = B, cos, sin
             rows = F.decoder_prefill(torch.cat(seqs, 0), self.model.layers, mb, cache.kv)
             out = list(rows.view(B, L0, h).unbind(0))
+        elif ragged and B > 1 and (chunk is None or L0 <= chunk):
+            out = F.decoder_extend_ragged([x2d.contiguous() for x2d in seqs], self.model.layers, meta, cache.kv)
         else:
             out = []
             for b, x2d in enumerate(seqs):
@@ -1288,7 +1301,8 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
 
     def _extend_batch(self, x, cache, rows=None):
         """n > 1 new rows per sequence x [B, n, h] on the FILLED cache -> their hidden rows [B, n, h] (pre final norm): one extend pass per
-        sequence (functional.decoder_extend: the weights streamed once for its n rows), one sequence after the other as ragged prompts run.
+        sequence (functional.decoder_extend: the weights streamed once for its n rows), one sequence after the other as ragged prompts run
+        -- or, with config.mm355_ragged_pass = True and B > 1, ONE functional.decoder_extend_ragged pass for all B sequences.
         rows: the sequences of the cache the B row blocks belong to (default: all of them, in order).  functional.set_variant("extend_pass",
         False), or fewer than VARIANTS["extend_min_rows"] rows: the captured decode step once per row (all sequences at once)."""
         B, n, h = x.shape
@@ -1302,6 +1316,8 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
                              "(size it with HipKVCache(capacity=...); a cache is not grown)")
         if (not F.VARIANTS["extend_pass"] or n < F.VARIANTS["extend_min_rows"]) and rows == list(range(kv.batch)):
             return MetaMorphLlamaForCausalLM._decode_batch(self, x, cache)
+        if self._ragged_pass(cache.meta) and B > 1:             # one pass for all B sequences, each at its own cached length
+            return torch.stack(F.decoder_extend_ragged(list(x.contiguous().unbind(0)), self.model.layers, cache.meta, kv, rows=rows), 0)
         return torch.stack([F.decoder_extend(x[j].contiguous(), self.model.layers, cache.meta, kv, row=b) for j, b in enumerate(rows)], 0)
 
     def _rows_logits(self, rows, return_hidden=False):

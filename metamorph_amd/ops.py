@@ -787,6 +787,98 @@ def attn_extend_f8(q, k8, v8, k_scale, v_scale, past, n, max_kv_len, Hq, Hkv, d,
     return out
 
 
+# ------------------------------------------------------------------------------------------------ a ragged batch: n_b new rows per sequence
+
+def attn_extend_ragged_supported(Hq, Hkv, d):
+    """the head shapes mm355_attn_extend_ragged takes (else MM355_EUNSUPPORTED): those of mm355_attn_extend"""
+    return d % 8 == 0 and d <= 128 and Hq % Hkv == 0 and Hq // Hkv in (1, 2, 4, 8)
+
+
+def _ragged_attn_args(q, past, row_start, n_max, max_kv_len, rows, Hq, Hkv, d, out, workspace):
+    """_cache_attn_args for the ragged forms: q / out [q_rows, Hq*d], row_start int32 [B + 1] on the device next to past [B]
+    -> (B, q pointer, ld, q_rows, out, its pointer, ld, workspace or None, its floats)"""
+    B = past.shape[0]
+    pq, R, W, ldq = _rows2d(q)
+    assert q.dtype == BF16 and W == Hq * d, (q.shape, Hq, d)
+    assert past.dtype == torch.int32 and row_start.dtype == torch.int32 and row_start.dim() == 1 and row_start.shape[0] == B + 1 and \
+        row_start.is_contiguous(), (past.dtype, row_start.dtype, row_start.shape, B)
+    assert 1 <= n_max <= max_kv_len <= rows, (n_max, max_kv_len, rows)
+    out = torch.empty((R, W), device=q.device, dtype=BF16) if out is None else out
+    po, Ro, Wo, ldo = _rows2d(out)
+    assert out.dtype == BF16 and (Ro, Wo) == (R, W)
+    n_ws = int(_L().mm355_attn_extend_ragged_ws_floats(B, n_max, Hq, Hkv, d, max_kv_len))
+    ws = workspace
+    if n_ws and (ws is None or ws.numel() < n_ws):
+        ws = torch.empty(n_ws, device=q.device, dtype=torch.float32)
+    return B, pq, ldq, R, out, po, ldo, ws, (0 if ws is None else ws.numel())
+
+
+def attn_extend_ragged(q, k, v, past, row_start, n_max, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None):
+    """n_b = row_start[b+1] - row_start[b] new rows of sequence b against its cache (mm355_attn_extend_ragged): q [rows, Hq*d] bf16, already
+    rotated, the rows of sequence b packed at row_start[b] + i (may be a column block of a wider tensor); k / v [B, rows, Hkv*d] bf16 already
+    holding them at past[b] .. past[b]+n_b-1; past int32 [B], row_start int32 [B + 1] on the device; n_max >= every n_b and max_kv_len >= every
+    past[b] + n_b are host bounds.  Row (b, i) attends the keys j <= past[b] + i of block b; n_b == 0 and past[b] == 0 are right."""
+    _chk_dev(q, k, v, past, row_start, out)
+    rows = _bf16_cache(k, v, past.shape[0], Hkv, d)
+    B, pq, ldq, R, out, po, ldo, ws, n_ws = _ragged_attn_args(q, past, row_start, n_max, max_kv_len, rows, Hq, Hkv, d, out, workspace)
+    _lib.check(_L().mm355_attn_extend_ragged(pq, ldq, k.data_ptr(), v.data_ptr(), k.stride(1), k.stride(0), past.data_ptr(), row_start.data_ptr(),
+                                             n_max, R, max_kv_len, po, ldo, B, Hq, Hkv, d, scale, _p(ws), n_ws, _stream()),
+               f"mm355_attn_extend_ragged B={B} n_max={n_max} rows={R} Hq={Hq} Hkv={Hkv} d={d}")
+    return out
+
+
+def attn_extend_ragged_f8(q, k8, v8, k_scale, v_scale, past, row_start, n_max, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None):
+    """attn_extend_ragged() over an e4m3 cache: k8 / v8 [B, rows, Hkv*d] uint8, k_scale / v_scale [B, rows, Hkv] f32
+    (mm355_attn_extend_ragged_f8): equal to attn_extend_ragged() on dequant_kv8() of the cache bit for bit."""
+    _chk_dev(q, k8, v8, k_scale, v_scale, past, row_start, out)
+    ldb, bsb, ldsc, bssc = _kv8_caches(k8, v8, k_scale, v_scale, past.shape[0], Hkv, d)
+    B, pq, ldq, R, out, po, ldo, ws, n_ws = _ragged_attn_args(q, past, row_start, n_max, max_kv_len, k8.shape[1], Hq, Hkv, d, out, workspace)
+    _lib.check(_L().mm355_attn_extend_ragged_f8(pq, ldq, k8.data_ptr(), v8.data_ptr(), ldb, bsb, k_scale.data_ptr(), v_scale.data_ptr(), ldsc,
+                                                bssc, KV8_E4M3, past.data_ptr(), row_start.data_ptr(), n_max, R, max_kv_len, po, ldo, B, Hq,
+                                                Hkv, d, scale, _p(ws), n_ws, _stream()),
+               f"mm355_attn_extend_ragged_f8 B={B} n_max={n_max} rows={R} Hq={Hq} Hkv={Hkv} d={d}")
+    return out
+
+
+def _row_tables(qkv, positions, blocks, n_blocks):
+    """positions / blocks int32 [R] of the rows of qkv (blocks None: block r for row r) -> the blocks pointer"""
+    R = qkv.shape[0]
+    assert positions.dtype == torch.int32 and positions.dim() == 1 and positions.shape[0] == R and positions.is_contiguous()
+    if blocks is None:
+        assert n_blocks >= R, (n_blocks, R)
+        return None
+    assert blocks.dtype == torch.int32 and blocks.dim() == 1 and blocks.shape[0] == R and blocks.is_contiguous()
+    return blocks.data_ptr()
+
+
+def rope_kv_append_rows_(qkv, Hq, Hkv, d, cos, sin, positions, blocks, k_cache, v_cache):
+    """rope_kv_append_() with a block per row (mm355_rope_kv_append_rows): qkv [R, (Hq+2Hkv)*d] new rows, any R: q (in place) and k rotated at
+    positions[r]; k, v -> row positions[r] of block blocks[r] of k_cache / v_cache [blocks, rows, Hkv*d] (int32 [R] each, on the device;
+    blocks None: block r).  Out-of-range entries are clamped into the cache."""
+    _chk_dev(qkv, cos, sin, positions, blocks, k_cache, v_cache)
+    assert k_cache.dim() == 3 and k_cache.stride() == v_cache.stride() and k_cache.stride(2) == 1
+    pb = _row_tables(qkv, positions, blocks, k_cache.shape[0])
+    _lib.check(_L().mm355_rope_kv_append_rows(qkv.data_ptr(), qkv.stride(0), qkv.shape[0], Hq, Hkv, d, cos.data_ptr(), sin.data_ptr(),
+                                              positions.data_ptr(), pb, k_cache.shape[0], k_cache.shape[1], k_cache.data_ptr(), v_cache.data_ptr(),
+                                              k_cache.stride(1), k_cache.stride(0), _stream()), "mm355_rope_kv_append_rows")
+    return qkv
+
+
+def rope_kv_append_rows_f8_(qkv, Hq, Hkv, d, cos, sin, positions, blocks, k8, v8, k_scale, v_scale):
+    """rope_kv_append_rows_() into an e4m3 cache (mm355_rope_kv_append_rows_f8): bytes and scales of row positions[r] of block blocks[r],
+    quantised as rope_kv_append_f8_() quantises them."""
+    _chk_dev(qkv, cos, sin, positions, blocks, k8, v8, k_scale, v_scale)
+    assert k8.stride() == v8.stride() and k_scale.stride() == v_scale.stride()
+    ldb, bsb, ldsc, bssc = _kv8_cache(k8, k_scale, Hkv, d)
+    _kv8_cache(v8, v_scale, Hkv, d)
+    pb = _row_tables(qkv, positions, blocks, k8.shape[0])
+    _lib.check(_L().mm355_rope_kv_append_rows_f8(qkv.data_ptr(), qkv.stride(0), qkv.shape[0], Hq, Hkv, d, cos.data_ptr(), sin.data_ptr(),
+                                                 positions.data_ptr(), pb, k8.shape[0], k8.shape[1], k8.data_ptr(), v8.data_ptr(), ldb, bsb,
+                                                 k_scale.data_ptr(), v_scale.data_ptr(), ldsc, bssc, KV8_E4M3, _stream()),
+               "mm355_rope_kv_append_rows_f8")
+    return qkv
+
+
 # ------------------------------------------------------------------------------------------------ decode over a shared prompt cache
 
 def attn_decode_shared_supported(Hq, Hkv, d):
