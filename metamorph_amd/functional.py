@@ -766,10 +766,68 @@ def linear(x2d, module):
     return LinearFn.apply(x2d, module.weight, module.bias, module)
 
 
+class KVRows:
+    """The cached rows of ONE layer, in the cache's format: k / v [sequences, max_len, width] and, fp8_e4m3, their scales [sequences,
+    max_len, Hkv] (bf16: None).  The one place that knows the format: every method is the cache operation of that name in `ops`, in the
+    format's form (rope_kv_append_ / rope_kv_append_f8_, ...) with the format's tensor group at its place among the arguments; the passes
+    hand over everything else.  The op is looked up by name when it is called: tests and tools wrap the names of `ops`."""
+
+    def __init__(self, k, v, k_scale=None, v_scale=None):
+        self.k, self.v, self.k_scale, self.v_scale = k, v, k_scale, v_scale
+        self.f8 = k_scale is not None
+        self.sfx = "_f8" if self.f8 else ""
+        self.kv = (k, v, k_scale, v_scale) if self.f8 else (k, v)
+
+    def seq(self, row):
+        """the same record narrowed to sequence `row` (the batch dimension stays)"""
+        return KVRows(*(t[row:row + 1] for t in self.kv))
+
+    def prefix(self):
+        """the rows of sequence 0, [max_len, width] each: where a prefix is stored once (KVCache.set_shared)"""
+        return tuple(t[0] for t in self.kv)
+
+    def rope_append_(self, qkv, *args):
+        return getattr(ops, f"rope_kv_append{self.sfx}_")(qkv, *args, *self.kv)
+
+    def rope_append_rows_(self, qkv, *args):
+        return getattr(ops, f"rope_kv_append_rows{self.sfx}_")(qkv, *args, *self.kv)
+
+    def attn_decode(self, q, *args, **kw):
+        return getattr(ops, "attn_decode" + self.sfx)(q, *self.kv, *args, **kw)
+
+    def attn_extend(self, q, *args, **kw):
+        return getattr(ops, "attn_extend" + self.sfx)(q, *self.kv, *args, **kw)
+
+    def attn_extend_ragged(self, q, *args, **kw):
+        return getattr(ops, "attn_extend_ragged" + self.sfx)(q, *self.kv, *args, **kw)
+
+    def attn_decode_shared(self, q, *args, **kw):
+        return getattr(ops, "attn_decode_shared" + self.sfx)(q, *self.prefix(), *self.kv, *args, **kw)
+
+    def attn_extend_shared(self, q, *args, **kw):
+        return getattr(ops, "attn_extend_shared" + self.sfx)(q, *self.prefix(), *self.kv, *args, **kw)
+
+    def store_rows(self, k_rows, v_rows, Hkv, d, row0, n, ident=None):
+        """Already rotated k / v rows [sequences * n, width] (may be column blocks of a wider tensor) -> rows row0 .. row0 + n - 1 of every
+        sequence.  fp8_e4m3: quantised on the way, one launch each.  bf16: ONE sequence with ident = arange(n) int32 as a strided row copy
+        with 16-byte vectors (mm355_rows_gather with the identity map: ~3 us; ATen's strided bf16 copy took 28 us per call, 1.3 of the
+        10.8 ms of a 512-row prompt pass), ident None: a tensor copy into all sequences."""
+        if self.f8:
+            ops.kv_quant_f8(k_rows, Hkv, d, self.k, self.k_scale, row0=row0, rows_per_seq=n)
+            ops.kv_quant_f8(v_rows, Hkv, d, self.v, self.v_scale, row0=row0, rows_per_seq=n)
+        elif ident is not None:
+            ops.rows_gather(k_rows, ident, out=self.k[0, row0:row0 + n])
+            ops.rows_gather(v_rows, ident, out=self.v[0, row0:row0 + n])
+        else:
+            self.k[:, row0:row0 + n].copy_(k_rows.view(-1, n, k_rows.shape[1]))
+            self.v[:, row0:row0 + n].copy_(v_rows.view(-1, n, v_rows.shape[1]))
+
+
 class KVCache:
     """Post-RoPE keys and values of every decoder layer for a BATCH of sequences: [layers, batch, max_len, Hkv*d] bf16 each (one sequence:
     batch = 1).  Every row of the batch has its own length; the write positions live on the device as well (pos_dev / len_dev, int32
-    [batch]) so that a decode step -- ONE pass over the weights for all rows -- is replayable as a hipGraph."""
+    [batch]) so that a decode step -- ONE pass over the weights for all rows -- is replayable as a hipGraph.  `rows[i]` is layer i as the
+    passes use it (KVRows, made once: the buffers never move)."""
 
     def __init__(self, n_layers, max_len, width, device, Hq=None, d=None, batch=1, fmt="bf16"):
         if fmt not in ops.KV_FORMATS:
@@ -788,6 +846,7 @@ class KVCache:
         else:
             self.k = torch.empty((n_layers, batch, max_len, width), device=device, dtype=BF16)
             self.v = torch.empty((n_layers, batch, max_len, width), device=device, dtype=BF16)
+        self.rows = [KVRows(*(t[i] for t in (self.k, self.v, self.k_scale, self.v_scale) if t is not None)) for i in range(n_layers)]
         self.max_len = max_len
         self.lengths = [0] * batch                                               # host mirror of pos_dev
         self.pos_dev = torch.zeros(batch, device=device, dtype=torch.int32)      # row the next token of sequence b is written to
@@ -882,7 +941,6 @@ def decoder_prefill(x, layers, meta, cache, row=0):
     """Prompt pass of a cached decode: the training-path layer forward, keeping each layer's post-RoPE k / v rows.
     x [meta.B * L, h] -> hidden rows (pre final norm).  meta.B == 1: the prompt of sequence `row`; meta.B == cache.batch: all sequences
     at once (prompts of ONE length -- the beams of a beam search, a batch without padding)."""
-    nq, nk = meta.Hq * meta.d, meta.Hkv * meta.d
     B = meta.B
     L = x.shape[0] // B
     assert B == 1 or (B == cache.batch and row == 0)
@@ -897,22 +955,7 @@ def decoder_prefill(x, layers, meta, cache, row=0):
         params_ready(layer)
         w8_materialize(layer)                                 # (a quantised layer: ALL four projections dequantised into the shared scratch, see W8Scratch -- a one-sequence prompt gets here once q|k|v is no longer split, 960 rows at 8B widths)
         x, saved = decoder_layer_forward(x, layer, meta)
-        qkv = saved[0]
-        if cache.kv8 is not None:                            # fp8_e4m3 cache: the rows are quantised as they enter it (one launch each for k and v)
-            kr = cache.k[i, row:row + 1] if B == 1 else cache.k[i]
-            vr = cache.v[i, row:row + 1] if B == 1 else cache.v[i]
-            ksr = cache.k_scale[i, row:row + 1] if B == 1 else cache.k_scale[i]
-            vsr = cache.v_scale[i, row:row + 1] if B == 1 else cache.v_scale[i]
-            ops.kv_quant_f8(qkv[:, nq:nq + nk], meta.Hkv, meta.d, kr, ksr, rows_per_seq=L)
-            ops.kv_quant_f8(qkv[:, nq + nk:], meta.Hkv, meta.d, vr, vsr, rows_per_seq=L)
-        elif B == 1:
-            # the k / v column blocks of the fused activation -> cache rows: a strided row copy with 16-byte vectors (mm355_rows_gather with the
-            # identity map: ~3 us; ATen's strided bf16 copy took 28 us per call, 1.3 of the 10.8 ms of a 512-row prompt pass)
-            ops.rows_gather(qkv[:, nq:nq + nk], ident, out=cache.k[i, row, :L])
-            ops.rows_gather(qkv[:, nq + nk:], ident, out=cache.v[i, row, :L])
-        else:
-            cache.k[i, :, :L].copy_(qkv[:, nq:nq + nk].view(B, L, nk))
-            cache.v[i, :, :L].copy_(qkv[:, nq + nk:].view(B, L, nk))
+        _store_kv(cache.rows[i].seq(row) if B == 1 else cache.rows[i], saved[0], meta, 0, ident)
         del saved
     if B == 1:
         cache.set_length(L, row)
@@ -925,6 +968,12 @@ def _seq_rows(t, n):
     """Cache rows t [max_len, width] of ONE sequence as the [n, max_len, width] cache operand of a call with n rows: a batch stride of 0,
     every row of the call belongs to this sequence."""
     return t.as_strided((n, t.shape[0], t.shape[1]), (0, t.stride(0), 1))
+
+
+def _store_kv(rows, qkv, meta, row0, ident=None):
+    """the rotated k and the v columns of the new q|k|v rows -> cache rows row0 .. of every sequence of `rows` (KVRows.store_rows)"""
+    nq, nk = meta.Hq * meta.d, meta.Hkv * meta.d
+    rows.store_rows(qkv[:, nq:nq + nk], qkv[:, nq + nk:], meta.Hkv, meta.d, row0, qkv.shape[0] // rows.k.shape[0], ident)
 
 
 def _gate_up(on8, rec, mlp, n2, meta, prompt):
@@ -997,6 +1046,18 @@ def _plain_walk(x, layers, meta, splitk, append_attend):
     return x
 
 
+def _extend_walk(x, layers, meta, append_attend, attend=None):
+    """The route of a pass that extends a cache by the rows x [R, h], chosen on R: _fused_walk where the prompt pass's fused walk applies (up
+    to 4096 rows, q|k|v split, d % 16 == 0), else _plain_walk.  append_attend(qkv, i) -> o: rotation, append and attention of layer i on
+    the projected rows; attend: the fused walk's step where the pass has one of its own (a fused q|k|v form), else the plain split
+    projection in front of append_attend."""
+    R, h = x.shape
+    splitk = VARIANTS["prefill_splitk"] and R <= 4096
+    if splitk and VARIANTS["prefill_fused"] and meta.d % 16 == 0 and ops.gemm_splitk_splits(R, (meta.Hq + 2 * meta.Hkv) * meta.d, h):
+        return _fused_walk(x, layers, meta, attend or (lambda qkv, i: append_attend(qkv("gemm", ops.gemm_splitk), i)), prompt=True)
+    return _plain_walk(x, layers, meta, splitk, append_attend)
+
+
 def _prefill_layers_fused(x, layers, meta, cache, row, ident):
     """decoder_prefill for one sequence of a few hundred rows on _fused_walk: q|k|v -> RoPE at the row's position -> rotated k and v
     straight into the cache rows (mm355_gemm_splitk_rope_append_bf16 on _seq_rows), attention reads K / V from the cache rows.  The bits of
@@ -1010,36 +1071,16 @@ def _prefill_layers_fused(x, layers, meta, cache, row, ident):
         stage = torch.empty((2, L, meta.Hkv * meta.d), device=x.device, dtype=BF16)
 
     def attend(qkv, i):
-        kc, vc = (stage[0], stage[1]) if stage is not None else (cache.k[i, row], cache.v[i, row])   # [max_len, width]
+        rows = cache.rows[i].seq(row)
+        kc, vc = (stage[0], stage[1]) if stage is not None else (rows.k[0], rows.v[0])   # [max_len, width]
         q = qkv("gemm_rope_append", ops.gemm_splitk_rope_append, meta.Hq, meta.Hkv, meta.d, meta.cos, meta.sin, ident,
                 _seq_rows(kc, L), _seq_rows(vc, L))
         o, _ = ops.attn_fwd(q[:, :nq], kc[:L], vc[:L], 1, L, meta.Hq, meta.Hkv, meta.d, meta.scale, True, meta.seqlens)
         if stage is not None:
-            ops.kv_quant_f8(stage[0], meta.Hkv, meta.d, cache.k[i, row:row + 1], cache.k_scale[i, row:row + 1])
-            ops.kv_quant_f8(stage[1], meta.Hkv, meta.d, cache.v[i, row:row + 1], cache.v_scale[i, row:row + 1])
+            rows.store_rows(stage[0], stage[1], meta.Hkv, meta.d, 0, L)
         return o
 
     return _fused_walk(x, layers, meta, attend, prompt=True)
-
-
-def _attend_extend(q, cache, i, row, past_dev, n, bound, meta):
-    """attention of the n new rows of sequence `row` over layer i of the cache, which already holds them"""
-    if cache.kv8 is not None:
-        return ops.attn_extend_f8(q, cache.k[i, row:row + 1], cache.v[i, row:row + 1], cache.k_scale[i, row:row + 1],
-                                  cache.v_scale[i, row:row + 1], past_dev, n, bound, meta.Hq, meta.Hkv, meta.d, meta.scale)
-    return ops.attn_extend(q, cache.k[i, row:row + 1], cache.v[i, row:row + 1], past_dev, n, bound, meta.Hq, meta.Hkv, meta.d, meta.scale)
-
-
-def _append_rows(qkv, cache, i, row, past, ident, meta):
-    """the rotated k and the v columns of the new rows -> cache rows past .. past + n - 1 of layer i (an fp8_e4m3 cache: quantised on the way)"""
-    nq, nk = meta.Hq * meta.d, meta.Hkv * meta.d
-    n = qkv.shape[0]
-    if cache.kv8 is not None:
-        ops.kv_quant_f8(qkv[:, nq:nq + nk], meta.Hkv, meta.d, cache.k[i, row:row + 1], cache.k_scale[i, row:row + 1], row0=past)
-        ops.kv_quant_f8(qkv[:, nq + nk:], meta.Hkv, meta.d, cache.v[i, row:row + 1], cache.v_scale[i, row:row + 1], row0=past)
-    else:
-        ops.rows_gather(qkv[:, nq:nq + nk], ident, out=cache.k[i, row, past:past + n])
-        ops.rows_gather(qkv[:, nq + nk:], ident, out=cache.v[i, row, past:past + n])
 
 
 def decoder_extend(x, layers, meta, cache, row=0):
@@ -1051,8 +1092,8 @@ def decoder_extend(x, layers, meta, cache, row=0):
     rotated in the q|k|v activation, quantised into the cache at row past and attended from there: the semantics of n decode steps (every
     row sees the quantised form of all rows, its own included), not of the first prompt pass.  The projections take the prompt pass's
     routes (w8_route, W8Scratch, the split-K limits); where the fused walk does not apply (more than 4096 rows, q|k|v not split,
-    d % 16 != 0) the plain route (_plain_walk) with mm355_rope_qk_pos and a row copy into the cache."""
-    n, h = x.shape
+    d % 16 != 0) the plain route (_plain_walk) with mm355_rope_qk_pos and a row copy into the cache (_extend_walk)."""
+    n = x.shape[0]
     if cache.shared_len > 0:
         raise ValueError(f"decoder_extend on a cache with a shared prefix of {cache.shared_len} rows: sequences 1.. do not hold the prefix "
                          "(only sequence 0 stores it), so their rows cannot be extended in place")
@@ -1063,58 +1104,29 @@ def decoder_extend(x, layers, meta, cache, row=0):
         raise ValueError(f"KV cache capacity of {cache.max_len} rows is too small for {past} cached + {n} new rows")
     if torch.is_grad_enabled():
         raise RuntimeError("decoder_extend is an inference pass (torch.no_grad())")
+    H = (meta.Hq, meta.Hkv, meta.d)
     nq = meta.Hq * meta.d
     bound = past + n
     ident = torch.arange(n, device=x.device, dtype=torch.int32)
     pos = ident + past
     past_dev = pos[:1]
-    splitk = VARIANTS["prefill_splitk"] and n <= 4096
 
     def append_attend(qkv, i):                                # rotation in place, (quantising) append, attention over the cache rows
-        ops.rope_qk_(qkv, 1, n, meta.Hq, meta.Hkv, meta.d, meta.cos, meta.sin, pos_offset=past_dev)
-        _append_rows(qkv, cache, i, row, past, ident, meta)
-        return _attend_extend(qkv[:, :nq], cache, i, row, past_dev, n, bound, meta)
+        rows = cache.rows[i].seq(row)
+        ops.rope_qk_(qkv, 1, n, *H, meta.cos, meta.sin, pos_offset=past_dev)
+        _store_kv(rows, qkv, meta, past, ident)
+        return rows.attn_extend(qkv[:, :nq], past_dev, n, bound, *H, meta.scale)
 
     def attend(qkv, i):
         if cache.kv8 is not None:                             # plain split projection, then as the plain route (no fused f8 form)
             return append_attend(qkv("gemm", ops.gemm_splitk), i)
-        q = qkv("gemm_rope_append", ops.gemm_splitk_rope_append, meta.Hq, meta.Hkv, meta.d, meta.cos, meta.sin, pos,
-                _seq_rows(cache.k[i, row], n), _seq_rows(cache.v[i, row], n))
-        return _attend_extend(q[:, :nq], cache, i, row, past_dev, n, bound, meta)
+        rows = cache.rows[i].seq(row)
+        q = qkv("gemm_rope_append", ops.gemm_splitk_rope_append, *H, meta.cos, meta.sin, pos, _seq_rows(rows.k[0], n), _seq_rows(rows.v[0], n))
+        return rows.attn_extend(q[:, :nq], past_dev, n, bound, *H, meta.scale)
 
-    if splitk and VARIANTS["prefill_fused"] and meta.d % 16 == 0 and ops.gemm_splitk_splits(n, (meta.Hq + 2 * meta.Hkv) * meta.d, h):
-        x = _fused_walk(x, layers, meta, attend, prompt=True)
-    else:
-        x = _plain_walk(x, layers, meta, splitk, append_attend)
+    x = _extend_walk(x, layers, meta, append_attend, attend)
     cache.set_length(past + n, row)
     return x
-
-
-def _append_rows_batch(qkv, cache, i, past, n, ident, meta):
-    """_append_rows for B sequences of n rows each: rows (b, *) of qkv -> rows past[b] .. past[b] + n - 1 of block b.  One launch per tensor
-    where all sequences start at the same row, else sequence by sequence."""
-    nq, nk = meta.Hq * meta.d, meta.Hkv * meta.d
-    B = len(past)
-    if len(set(past)) > 1:
-        for b in range(B):
-            _append_rows(qkv[b * n:(b + 1) * n], cache, i, b, past[b], ident, meta)
-    elif cache.kv8 is not None:
-        ops.kv_quant_f8(qkv[:, nq:nq + nk], meta.Hkv, meta.d, cache.k[i], cache.k_scale[i], row0=past[0], rows_per_seq=n)
-        ops.kv_quant_f8(qkv[:, nq + nk:], meta.Hkv, meta.d, cache.v[i], cache.v_scale[i], row0=past[0], rows_per_seq=n)
-    else:
-        cache.k[i, :, past[0]:past[0] + n].copy_(qkv[:, nq:nq + nk].view(B, n, nk))
-        cache.v[i, :, past[0]:past[0] + n].copy_(qkv[:, nq + nk:].view(B, n, nk))
-
-
-def _attend_extend_shared(q, cache, i, past_dev, n, bound, meta, ws):
-    """attention of the n new rows of every sequence over layer i of a cache with a shared prefix, which already holds them: the shared rows
-    are rows [0, shared_len) of sequence 0, as _attend_decode picks them"""
-    H = (meta.Hq, meta.Hkv, meta.d, meta.scale)
-    k, v, P = cache.k, cache.v, cache.shared_len
-    if cache.kv8 is not None:
-        ks, vs = cache.kv8
-        return ops.attn_extend_shared_f8(q, k[i, 0], v[i, 0], ks[i, 0], vs[i, 0], k[i], v[i], ks[i], vs[i], past_dev, n, P, bound, *H, workspace=ws)
-    return ops.attn_extend_shared(q, k[i, 0], v[i, 0], k[i], v[i], past_dev, n, P, bound, *H, workspace=ws)
 
 
 def decoder_extend_shared(x, layers, meta, cache, past=None):
@@ -1123,9 +1135,10 @@ def decoder_extend_shared(x, layers, meta, cache, past=None):
     cache.lengths; past[b] >= cache.shared_len) and attends the shared rows and then rows [shared_len, past[b] + i] of block b; afterwards
     cache.lengths[b] == past[b] + n.  B different questions over one context: the pass between the prefix and the decode loop.
     decoder_extend's two routes and its projection routing (w8_route, W8Scratch, the split-K limits, on the row count B * n) with three
-    differences: the positions are per row (mm355_rope_qk_pos with B sequences of n rows); the append goes into block b per sequence, so
-    q|k|v is always the plain split projection + rotation + append that decoder_extend takes on an fp8_e4m3 cache (the fused reduce launch
-    cannot name a block per row); attention is mm355_attn_extend_shared.  An fp8_e4m3 cache is read back quantised, as decoder_extend reads it.
+    differences: the positions are per row (mm355_rope_qk_pos with B sequences of n rows); the append goes into block b per sequence (one
+    launch per tensor where all sequences start at the same row, else sequence by sequence), so q|k|v is always the plain split
+    projection + rotation + append that decoder_extend takes on an fp8_e4m3 cache (the fused reduce launch cannot name a block per row);
+    attention is mm355_attn_extend_shared.  An fp8_e4m3 cache is read back quantised, as decoder_extend reads it.
     Sequences of unequal length: right-pad x with zero rows to the longest and set_lengths afterwards.  Rows are independent outside
     attention and attention is causal over the own rows, so a valid row never sees a padding row; the padding rows' K / V land at own rows
     beyond the sequence's length, where no kernel reads them before a later append overwrites them."""
@@ -1143,25 +1156,26 @@ def decoder_extend_shared(x, layers, meta, cache, past=None):
         raise ValueError(f"KV cache capacity of {cache.max_len} rows is too small for {max(past)} cached + {n} new rows")
     if torch.is_grad_enabled():
         raise RuntimeError("decoder_extend_shared is an inference pass (torch.no_grad())")
-    R = B * n
-    x = x.reshape(R, h)
+    x = x.reshape(B * n, h)
+    H = (meta.Hq, meta.Hkv, meta.d)
     nq = meta.Hq * meta.d
     bound = max(past) + n
     ident = torch.arange(n, device=x.device, dtype=torch.int32)
     past_dev = torch.tensor(past, dtype=torch.int32).to(x.device)
-    n_ws = int(ops._L().mm355_attn_extend_shared_ws_floats(B, n, meta.Hq, meta.Hkv, meta.d, S, bound))
+    n_ws = int(ops._L().mm355_attn_extend_shared_ws_floats(B, n, *H, S, bound))
     ws = torch.empty(max(n_ws, 4), device=x.device, dtype=torch.float32)
 
     def append_attend(qkv, i):
-        ops.rope_qk_(qkv, B, n, meta.Hq, meta.Hkv, meta.d, meta.cos, meta.sin, pos_offset=past_dev)
-        _append_rows_batch(qkv, cache, i, past, n, ident, meta)
-        return _attend_extend_shared(qkv[:, :nq], cache, i, past_dev, n, bound, meta, ws)
+        rows = cache.rows[i]
+        ops.rope_qk_(qkv, B, n, *H, meta.cos, meta.sin, pos_offset=past_dev)
+        if len(set(past)) > 1:
+            for b in range(B):
+                _store_kv(rows.seq(b), qkv[b * n:(b + 1) * n], meta, past[b], ident)
+        else:
+            _store_kv(rows, qkv, meta, past[0])
+        return rows.attn_extend_shared(qkv[:, :nq], past_dev, n, S, bound, *H, meta.scale, workspace=ws)
 
-    splitk = VARIANTS["prefill_splitk"] and R <= 4096
-    if splitk and VARIANTS["prefill_fused"] and meta.d % 16 == 0 and ops.gemm_splitk_splits(R, (meta.Hq + 2 * meta.Hkv) * meta.d, h):
-        x = _fused_walk(x, layers, meta, lambda qkv, i: append_attend(qkv("gemm", ops.gemm_splitk), i), prompt=True)
-    else:
-        x = _plain_walk(x, layers, meta, splitk, append_attend)
+    x = _extend_walk(x, layers, meta, append_attend)
     cache.set_lengths([p + n for p in past])
     return x.view(B, n, h)
 
@@ -1242,19 +1256,10 @@ def decoder_extend_ragged(xs, layers, meta, cache, rows=None):
     ws = torch.empty(max(n_ws, 4), device=dev, dtype=torch.float32)
 
     def append_attend(qkv, i):                                # rotation + (quantising) append per row, attention over the cache rows
-        k, v = cache.k[i], cache.v[i]
-        if cache.kv8 is not None:
-            ks, vs = cache.k_scale[i], cache.v_scale[i]
-            ops.rope_kv_append_rows_f8_(qkv, *H, meta.cos, meta.sin, pos, blk, k, v, ks, vs)
-            return ops.attn_extend_ragged_f8(qkv[:, :nq], k, v, ks, vs, past_dev, row_start, plan.n_max, plan.bound, *H, meta.scale, workspace=ws)
-        ops.rope_kv_append_rows_(qkv, *H, meta.cos, meta.sin, pos, blk, k, v)
-        return ops.attn_extend_ragged(qkv[:, :nq], k, v, past_dev, row_start, plan.n_max, plan.bound, *H, meta.scale, workspace=ws)
+        cache.rows[i].rope_append_rows_(qkv, *H, meta.cos, meta.sin, pos, blk)
+        return cache.rows[i].attn_extend_ragged(qkv[:, :nq], past_dev, row_start, plan.n_max, plan.bound, *H, meta.scale, workspace=ws)
 
-    splitk = VARIANTS["prefill_splitk"] and R <= 4096
-    if splitk and VARIANTS["prefill_fused"] and ops.gemm_splitk_splits(R, (meta.Hq + 2 * meta.Hkv) * meta.d, h):
-        x = _fused_walk(x, layers, meta, lambda qkv, i: append_attend(qkv("gemm", ops.gemm_splitk), i), prompt=True)
-    else:
-        x = _plain_walk(x, layers, meta, splitk, append_attend)
+    x = _extend_walk(x, layers, meta, append_attend)
     new = list(cache.lengths)
     for b, n in zip(rows, lens):
         new[b] += n
@@ -1459,29 +1464,23 @@ def _proj(on8, rec, name, weights, w8_op, bf16_op, x, *args, **kw):
     return bf16_op(x, weights[0] if len(weights) == 1 else fused_weight(weights), *args, **kw)
 
 
-def _attend_decode(q, i, meta, k, v, kv8, len_dev, ws, kv_bound, shared=None):
-    """Attention of the step's new rows (one per sequence, already appended) over layer i of the cache: every sequence over its own rows
-    (mm355_attn_decode / _f8), or, on a cache whose first rows are shared (KVCache.shared: (shared_len, workspace)), over rows [0,
-    shared_len) of sequence 0 and then its own rows (mm355_attn_decode_shared / _f8); a third entry of `shared` is the table that says in
-    which block each own row lives (mm355_attn_decode_shared_idx / _idx_f8)."""
+def _attend_decode(q, rows, meta, cache, kv_bound):
+    """Attention of the step's new rows (one per sequence, already appended) over `rows`, one layer of the cache: every sequence over its own
+    rows (mm355_attn_decode), or, on a cache whose first rows are shared (KVCache.set_shared), over rows [0, shared_len) of sequence 0 and
+    then its own rows (mm355_attn_decode_shared); with the cache's table own_block, which says in which block each own row lives,
+    mm355_attn_decode_shared_idx."""
     H = (meta.Hq, meta.Hkv, meta.d, meta.scale)
-    if shared is not None:
-        P, sws, *tbl = shared
-        tbl = {"own_block": tbl[0]} if tbl else {}
-        if kv8 is not None:
-            return ops.attn_decode_shared_f8(q, k[i, 0], v[i, 0], kv8[0][i, 0], kv8[1][i, 0], k[i], v[i], kv8[0][i], kv8[1][i], len_dev, P,
-                                             kv_bound, *H, workspace=sws, **tbl)
-        return ops.attn_decode_shared(q, k[i, 0], v[i, 0], k[i], v[i], len_dev, P, kv_bound, *H, workspace=sws, **tbl)
-    if kv8 is not None:
-        return ops.attn_decode_f8(q, k[i], v[i], kv8[0][i], kv8[1][i], len_dev, kv_bound, *H, workspace=ws)
-    return ops.attn_decode(q, k[i], v[i], len_dev, kv_bound, *H, workspace=ws)
+    if cache.shared_len > 0:
+        tbl = {} if cache.own_block is None else {"own_block": cache.own_block}
+        return rows.attn_decode_shared(q, cache.len_dev, cache.shared_len, kv_bound, *H, workspace=cache.shared_ws, **tbl)
+    return rows.attn_decode(q, cache.len_dev, kv_bound, *H, workspace=cache.ws)
 
 
-def _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound, shared=None):
-    """The new q|k|v rows against layer i of an fp8_e4m3 cache (k / v: the bytes, kv8: the scales): RoPE + quantising append, then attention
-    over the bytes -- the row just appended included.  Two launches; the projection in front is the plain one."""
-    ops.rope_kv_append_f8_(qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i], kv8[0][i], kv8[1][i])
-    return _attend_decode(qkv[:, :meta.Hq * meta.d], i, meta, k, v, kv8, len_dev, ws, kv_bound, shared)
+def _append_attend(qkv, rows, meta, cache, cos, sin, kv_bound):
+    """The step's new q|k|v rows against `rows`: RoPE + (quantising) append, then attention over the cache -- the row just appended
+    included.  Two launches; the projection in front is the plain one."""
+    rows.rope_append_(qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, cache.pos_dev)
+    return _attend_decode(qkv[:, :meta.Hq * meta.d], rows, meta, cache, kv_bound)
 
 
 _Rows16 = namedtuple("_Rows16", "gemv gemv_swiglu gemv_rope_append qkv o gu down")
@@ -1497,14 +1496,15 @@ def _bf16_rows16(layer):
                    (fused_weight([mlp.gate_proj.weight, mlp.up_proj.weight]),), (mlp.down_proj.weight,))
 
 
-def _decode_rows16(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound, kv8=None, shared=None):
-    """<= 16 new rows (one per sequence) through every decoder layer against their cache rows k / v [layers, rows, max_len, width]:
+def _decode_rows16(x, layers, meta, cache, cos, sin, kv_bound):
+    """<= 16 new rows (one per sequence) through every decoder layer against their cache rows (cache.rows[i]):
     every weight is streamed ONCE for all rows (mm355_gemv* take M <= 16: up to four rows on the vector ALU, 5 .. 16 on MFMA), attention per
     row at its own length.  One launch sequence for every weight format: a quantised layer runs it on its record's own kernels (W8Layer:
     mm355_gemv*_w8, W4Layer: mm355_gemv*_w4), a bf16 layer on mm355_gemv*_bf16 through _bf16_rows16."""
     nq = meta.Hq * meta.d
     fused = VARIANTS["decode_fused"] and meta.I % 2 == 0 and meta.d % 4 == 0
     for i, layer in enumerate(layers):
+        rows = cache.rows[i]
         rec = getattr(layer, "w8", None)
         if rec is None:
             params_ready(layer)
@@ -1515,28 +1515,23 @@ def _decode_rows16(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bou
             # Five rows and more (the MFMA GEMVs): the norm runs as its own launch -- folded in, every workgroup would normalise ALL rows again
             # (measured, cached step of 32 layers: four rows 3.50 -> 3.38 ms with the norms folded, eight rows slower) -- seven launches, same bits.
             fold = x.shape[0] <= VARIANTS["decode_fold_rows"]
-            if kv8 is not None:
+            if cache.kv8 is not None:
                 # fp8_e4m3 cache: the norm and the plain projection as launches of their own (no fused *_rope_append_f8 form), then the
                 # quantising append and attention over the bytes: seven launches per layer up to the fold limit, eight beyond
                 qkv = rec.gemv(ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps), *rec.qkv)
-                o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound, shared)
+                o = _append_attend(qkv, rows, meta, cache, cos, sin, kv_bound)
             else:
                 n1 = x if fold else ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
-                qkv = rec.gemv_rope_append(n1, *rec.qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i],
+                qkv = rec.gemv_rope_append(n1, *rec.qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, cache.pos_dev, rows.k, rows.v,
                                            norm_w=layer.input_layernorm.weight if fold else None, eps=meta.eps)
-                o = _attend_decode(qkv[:, :nq], i, meta, k, v, None, len_dev, ws, kv_bound, shared)
+                o = _attend_decode(qkv[:, :nq], rows, meta, cache, kv_bound)
             x2 = rec.gemv(o, *rec.o, residual=x)
             n2 = x2 if fold else ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
             act = rec.gemv_swiglu(n2, *rec.gu, meta.I, norm_w=layer.post_attention_layernorm.weight if fold else None, eps=meta.eps)
             x = rec.gemv(act, *rec.down, residual=x2)
             continue
         n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
-        qkv = rec.gemv(n1, *rec.qkv)
-        if kv8 is not None:
-            o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound, shared)
-        else:
-            ops.rope_kv_append_(qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
-            o = _attend_decode(qkv[:, :nq], i, meta, k, v, None, len_dev, ws, kv_bound, shared)
+        o = _append_attend(rec.gemv(n1, *rec.qkv), rows, meta, cache, cos, sin, kv_bound)
         x2 = rec.gemv(o, *rec.o, residual=x)
         n2 = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
         act = ops.swiglu_fwd(rec.gemv(n2, *rec.gu), meta.I)
@@ -1544,7 +1539,7 @@ def _decode_rows16(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bou
     return x
 
 
-def _decode_rows_gemm(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_bound, kv8=None, shared=None):
+def _decode_rows_gemm(x, layers, meta, cache, cos, sin, kv_bound):
     """17 new rows and more (one per sequence) through every decoder layer in ONE pass over the weights (round 6; rounds 5: chunks of 16 rows,
     i.e. the 15 GB read once per chunk).  The GEMV kernels hold one 16-row MFMA operand; beyond it the projections take the split-K GEMM of
     the prompt pass (mm355_gemm_splitk_bf16: 64 x 128 tiles x K slices -- at 32 rows a weight-streaming problem with ~3 workgroups per CU),
@@ -1555,10 +1550,11 @@ def _decode_rows_gemm(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_
     if VARIANTS["decode_wide_fused"] and meta.d % 16 == 0:
         # what follows a split projection rides in its reduce launch (mm355_gemm_splitk_{rope_append,norm,swiglu}_bf16): 9 launches per layer
         def attend(qkv, i):
-            if kv8 is not None:                              # fp8_e4m3 cache: the plain split projection, then the quantising append (ten launches per layer)
-                return _append_attend_f8(qkv("gemm", ops.gemm_splitk), i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound, shared)
-            q = qkv("gemm_rope_append", ops.gemm_splitk_rope_append, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
-            return _attend_decode(q[:, :nq], i, meta, k, v, None, len_dev, ws, kv_bound, shared)
+            rows = cache.rows[i]
+            if cache.kv8 is not None:                        # fp8_e4m3 cache: the plain split projection, then the quantising append (ten launches per layer)
+                return _append_attend(qkv("gemm", ops.gemm_splitk), rows, meta, cache, cos, sin, kv_bound)
+            q = qkv("gemm_rope_append", ops.gemm_splitk_rope_append, meta.Hq, meta.Hkv, meta.d, cos, sin, cache.pos_dev, rows.k, rows.v)
+            return _attend_decode(q[:, :nq], rows, meta, cache, kv_bound)
 
         return _fused_walk(x, layers, meta, attend, prompt=False)
     for i, layer in enumerate(layers):
@@ -1568,11 +1564,7 @@ def _decode_rows_gemm(x, layers, meta, cos, sin, k, v, pos_dev, len_dev, ws, kv_
         att, mlp = layer.self_attn, layer.mlp
         n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
         qkv = _proj(on8, rec, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), "gemm", ops.gemm_splitk, n1)
-        if kv8 is not None:
-            o = _append_attend_f8(qkv, i, meta, cos, sin, k, v, kv8, pos_dev, len_dev, ws, kv_bound, shared)
-        else:
-            ops.rope_kv_append_(qkv, meta.Hq, meta.Hkv, meta.d, cos, sin, pos_dev, k[i], v[i])
-            o = _attend_decode(qkv[:, :nq], i, meta, k, v, None, len_dev, ws, kv_bound, shared)
+        o = _append_attend(qkv, cache.rows[i], meta, cache, cos, sin, kv_bound)
         x2 = _proj(on8, rec, "o", (att.o_proj.weight,), "gemm", ops.gemm_splitk, o, residual=x)
         n2 = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
         gu = _proj(on8, rec, "gu", (mlp.gate_proj.weight, mlp.up_proj.weight), "gemm", ops.gemm_splitk, n2)
@@ -1607,10 +1599,7 @@ def decoder_decode_row(x, layers, meta, cache, cos, sin, kv_bound=None):
     if cache.length + 1 > bound:
         # the bound is a launch parameter (number of key groups): a sequence longer than it would silently attend to its first `bound` keys
         raise ValueError(f"decode bound {bound} is below the longest sequence + 1 ({cache.length + 1}); lengths change only through set_lengths")
-    if B <= 16:
-        y = _decode_rows16(x, layers, meta, cos, sin, cache.k, cache.v, cache.pos_dev, cache.len_dev, cache.ws, bound, cache.kv8, cache.shared)
-    else:
-        y = _decode_rows_gemm(x, layers, meta, cos, sin, cache.k, cache.v, cache.pos_dev, cache.len_dev, cache.ws, bound, cache.kv8, cache.shared)
+    y = (_decode_rows16 if B <= 16 else _decode_rows_gemm)(x, layers, meta, cache, cos, sin, bound)
     cache.pos_dev.add_(1)
     cache.len_dev.add_(1)
     cache.lengths = [n + 1 for n in cache.lengths]

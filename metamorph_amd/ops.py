@@ -602,33 +602,6 @@ def gemm_w4_rope_append(x, wq, s, Hq, Hkv, d, cos, sin, positions, k_cache, v_ca
     return _wq_gemm_rope_append(_W4, x, wq, s, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache)
 
 
-def rope_kv_append_(qkv, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache):
-    """qkv [B, (Hq+2Hkv)*d] new rows: rotate q (in place) and k at positions[b] (int32, device); k, v -> cache row positions[b]."""
-    _chk_dev(qkv, cos, sin, positions, k_cache, v_cache)
-    assert positions.dtype == torch.int32 and k_cache.stride() == v_cache.stride() and k_cache.stride(2) == 1
-    B = qkv.shape[0]
-    _lib.check(_L().mm355_rope_kv_append(qkv.data_ptr(), qkv.stride(0), B, Hq, Hkv, d, cos.data_ptr(), sin.data_ptr(), positions.data_ptr(),
-                                         k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(1), k_cache.stride(0), _stream()),
-               "mm355_rope_kv_append")
-    return qkv
-
-
-def attn_decode(q, k_cache, v_cache, kv_lens, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None, variant=0):
-    """q [B, Hq*d]; caches [B, Lmax, Hkv*d]; kv_lens int32 [B] on the device (valid rows incl. the current one)."""
-    _chk_dev(q, k_cache, v_cache, kv_lens)
-    B = q.shape[0]
-    assert k_cache.dim() == 3 and k_cache.shape == v_cache.shape and k_cache.stride(2) == 1 and v_cache.stride() == k_cache.stride()
-    assert kv_lens.dtype == torch.int32 and max_kv_len <= k_cache.shape[1]
-    out = torch.empty((B, Hq * d), device=q.device, dtype=BF16) if out is None else out
-    ws = workspace
-    if ws is None:
-        ws = torch.zeros(int(_L().mm355_attn_decode_ws_floats(B, Hq, d, max_kv_len)), device=q.device, dtype=torch.float32)   # arrival counters start at 0
-    _lib.check(_L().mm355_attn_decode_variant(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(1), k_cache.stride(0),
-                                              kv_lens.data_ptr(), max_kv_len, out.data_ptr(), out.stride(0), B, Hq, Hkv, d, scale, ws.data_ptr(),
-                                              int(variant), _stream()), "mm355_attn_decode")
-    return out
-
-
 # ------------------------------------------------------------------------------------------------ FP8 KV cache (decode)
 
 KV8_E4M3 = 1                                                 # MM355_KV8_E4M3
@@ -678,166 +651,69 @@ def kv_quant_f8(src, Hkv, d, dst, dst_scale, row0=0, rows_per_seq=None):
                                       _stream()), f"mm355_kv_quant_f8 R={R} Hkv={Hkv} d={d}")
 
 
-def rope_kv_append_f8_(qkv, Hq, Hkv, d, cos, sin, positions, k8, v8, k_scale, v_scale):
-    """rope_kv_append_() into an e4m3 cache: q rotated in place (the same bits), the rotated k row (rounded to bf16 as the bf16 cache would
-    hold it) and the v row quantised into row positions[b] of k8 / v8 [B, Lmax, Hkv*d] uint8 and k_scale / v_scale [B, Lmax, Hkv] f32."""
-    _chk_dev(qkv, cos, sin, positions, k8, v8, k_scale, v_scale)
-    assert positions.dtype == torch.int32 and k8.stride() == v8.stride() and k_scale.stride() == v_scale.stride()
-    ldb, bsb, ldsc, bssc = _kv8_cache(k8, k_scale, Hkv, d)
-    _kv8_cache(v8, v_scale, Hkv, d)
-    B = qkv.shape[0]
-    _lib.check(_L().mm355_rope_kv_append_f8(qkv.data_ptr(), qkv.stride(0), B, Hq, Hkv, d, cos.data_ptr(), sin.data_ptr(), positions.data_ptr(),
-                                            k8.data_ptr(), v8.data_ptr(), ldb, bsb, k_scale.data_ptr(), v_scale.data_ptr(), ldsc, bssc,
-                                            KV8_E4M3, _stream()), "mm355_rope_kv_append_f8")
-    return qkv
+# ------------------------------------------------------------------------------------------------ one wrapper per KV-cache operation
+
+class _KVFormat:
+    """One KV-cache format as the wrappers below need it: the suffix of its C symbols and of the public names (mm355_attn_extend<sfx>,
+    ops.attn_extend<sfx>), `cache(kv, B, Hkv, d)`: the format's own checks of its cache tensors kv (bf16: k, v; e4m3: k8, v8, k_scale,
+    v_scale) for B sequences -> (rows, the C operands that describe the cache in every call of the format, its MM355_* constant last), and
+    `prefix(sh, Hkv, d)`: the same for the rows of a prefix stored once (k_shared, v_shared and, e4m3, their scales)."""
+
+    def __init__(self, sfx, cache, prefix):
+        self.sfx, self.cache, self.prefix = sfx, cache, prefix
+
+    def sym(self, pattern):
+        """"attn_extend{}" -> mm355_attn_extend_f8: (the library's function, its name for messages)."""
+        name = "mm355_" + pattern.format(self.sfx)
+        return getattr(_L(), name), name
 
 
-def attn_decode_f8(q, k8, v8, k_scale, v_scale, kv_lens, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None, variant=0):
-    """attn_decode() over an e4m3 cache: k8 / v8 [B, Lmax, Hkv*d] uint8, k_scale / v_scale [B, Lmax, Hkv] f32 (variants 0 and 2)."""
-    _chk_dev(q, k8, v8, k_scale, v_scale, kv_lens)
-    B = q.shape[0]
-    assert k8.shape == v8.shape and k8.stride() == v8.stride() and k_scale.stride() == v_scale.stride()
-    ldb, bsb, ldsc, bssc = _kv8_cache(k8, k_scale, Hkv, d)
-    _kv8_cache(v8, v_scale, Hkv, d)
-    assert kv_lens.dtype == torch.int32 and max_kv_len <= k8.shape[1]
-    out = torch.empty((B, Hq * d), device=q.device, dtype=BF16) if out is None else out
-    ws = workspace
-    if ws is None:
-        ws = torch.zeros(int(_L().mm355_attn_decode_ws_floats(B, Hq, d, max_kv_len)), device=q.device, dtype=torch.float32)   # arrival counters start at 0
-    _lib.check(_L().mm355_attn_decode_f8_variant(q.data_ptr(), q.stride(0), k8.data_ptr(), v8.data_ptr(), ldb, bsb, k_scale.data_ptr(),
-                                                 v_scale.data_ptr(), ldsc, bssc, KV8_E4M3, kv_lens.data_ptr(), max_kv_len, out.data_ptr(),
-                                                 out.stride(0), B, Hq, Hkv, d, scale, ws.data_ptr(), int(variant), _stream()),
-               "mm355_attn_decode_f8")
-    return out
-
-
-# ------------------------------------------------------------------------------------------------ extending a filled cache by n rows
-
-def _cache_attn_args(q, lens, n, max_kv_len, rows, Hq, Hkv, d, out, workspace, ws_floats, shared_len=None, shared_rows=None):
-    """What the cache-attention wrappers below hand to the C side: n query rows per sequence (None: the decode forms, one row and no such
-    argument), lens the entry point's int32 [B] (past or kv_lens), ws_floats the name of its mm355_*_ws_floats, shared_len / shared_rows
-    where a prefix is stored once.  -> (B, q pointer, ld, out, its pointer, ld, workspace or None, its floats)"""
-    B = lens.shape[0]
-    pq, R, W, ldq = _rows2d(q)
-    nn, sh = (() if n is None else (n,)), (() if shared_len is None else (shared_len,))      # what the entry point takes of the two
-    assert q.dtype == BF16 and R == B * (n or 1) and W == Hq * d, (q.shape, B, *nn, Hq, d)
-    assert lens.dtype == torch.int32 and (n is None or n <= max_kv_len) and max_kv_len <= rows and \
-        (shared_len is None or 0 <= shared_len <= max_kv_len and shared_len <= shared_rows), (*nn, *sh, max_kv_len, rows)
-    out = torch.empty((R, W), device=q.device, dtype=BF16) if out is None else out
-    po, Ro, Wo, ldo = _rows2d(out)
-    assert out.dtype == BF16 and (Ro, Wo) == (R, W)
-    n_ws = int(getattr(_L(), ws_floats)(B, *nn, Hq, Hkv, d, *sh, max_kv_len))
-    ws = workspace
-    if n_ws and (ws is None or ws.numel() < n_ws):
-        ws = torch.empty(n_ws, device=q.device, dtype=torch.float32)
-    return B, pq, ldq, out, po, ldo, ws, (0 if ws is None else ws.numel())
-
-
-def _bf16_cache(k, v, B, Hkv, d):
-    """k / v [>= B, rows, Hkv*d] bf16 with the same strides -> rows"""
+def _bf16_kv_operands(kv, B, Hkv, d):
+    """k / v [>= B, rows, Hkv*d] bf16 with the same strides"""
+    k, v = kv
     assert k.dim() == 3 and k.dtype == BF16 and k.shape == v.shape and k.stride(2) == 1 and v.stride() == k.stride() and k.shape[2] == Hkv * d
     assert k.shape[0] >= B
-    return k.shape[1]
+    return k.shape[1], (k.data_ptr(), v.data_ptr(), k.stride(1), k.stride(0))
 
 
-def _kv8_caches(k8, v8, k_scale, v_scale, B, Hkv, d):
+def _f8_kv_operands(kv, B, Hkv, d):
     """_kv8_cache() of two caches [>= B, rows, Hkv*d] with the same strides"""
+    k8, v8, k_scale, v_scale = kv
     assert k8.shape == v8.shape and k8.stride() == v8.stride() and k_scale.stride() == v_scale.stride() and k8.shape[0] >= B
     _kv8_cache(v8, v_scale, Hkv, d)
-    return _kv8_cache(k8, k_scale, Hkv, d)
+    ldb, bsb, ldsc, bssc = _kv8_cache(k8, k_scale, Hkv, d)
+    return k8.shape[1], (k8.data_ptr(), v8.data_ptr(), ldb, bsb, k_scale.data_ptr(), v_scale.data_ptr(), ldsc, bssc, KV8_E4M3)
 
 
-def _shared_rows(k_shared, v_shared, Hkv, d, dtype=BF16):
-    """the prefix stored once: k_shared / v_shared [rows, Hkv*d] of `dtype` with the same strides -> rows"""
-    assert k_shared.dim() == 2 and k_shared.dtype == dtype and k_shared.shape == v_shared.shape and k_shared.stride() == v_shared.stride()
-    assert k_shared.stride(1) == 1 and k_shared.shape[1] == Hkv * d
-    return k_shared.shape[0]
+def _bf16_prefix_operands(sh, Hkv, d, dtype=BF16):
+    """the prefix stored once: k_shared / v_shared [rows, Hkv*d] of `dtype` with the same strides"""
+    k_sh, v_sh = sh
+    assert k_sh.dim() == 2 and k_sh.dtype == dtype and k_sh.shape == v_sh.shape and k_sh.stride() == v_sh.stride()
+    assert k_sh.stride(1) == 1 and k_sh.shape[1] == Hkv * d
+    return k_sh.shape[0], (k_sh.data_ptr(), v_sh.data_ptr(), k_sh.stride(0))
 
 
-def _shared_rows_f8(k_shared, v_shared, k_shared_scale, v_shared_scale, Hkv, d):
-    """_shared_rows() of e4m3 bytes with their scales [rows, Hkv] f32"""
-    rows = _shared_rows(k_shared, v_shared, Hkv, d, torch.uint8)
-    assert k_shared_scale.dtype == torch.float32 and tuple(k_shared_scale.shape) == (rows, Hkv) and k_shared_scale.stride(1) == 1
-    assert v_shared_scale.dtype == torch.float32 and v_shared_scale.shape == k_shared_scale.shape and v_shared_scale.stride() == k_shared_scale.stride()
-    return rows
+def _f8_prefix_operands(sh, Hkv, d):
+    """_bf16_prefix_operands() of e4m3 bytes, and their scales [rows, Hkv] f32"""
+    rows, csh = _bf16_prefix_operands(sh[:2], Hkv, d, torch.uint8)
+    ks, vs = sh[2:]
+    assert ks.dtype == torch.float32 and tuple(ks.shape) == (rows, Hkv) and ks.stride(1) == 1
+    assert vs.dtype == torch.float32 and vs.shape == ks.shape and vs.stride() == ks.stride()
+    return rows, (*csh, ks.data_ptr(), vs.data_ptr(), ks.stride(0))
 
 
-def attn_extend(q, k, v, past, n, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None):
-    """n new rows per sequence against a filled cache (mm355_attn_extend): q [B*n, Hq*d] bf16, already rotated, row (b, i) at b*n + i (may be
-    a column block of a wider tensor); k / v [B, rows, Hkv*d] bf16 already holding the chunk's own rows at past[b] .. past[b]+n-1; past int32
-    [B] on the device; max_kv_len a host bound with past[b] + n <= max_kv_len <= rows.  Row (b, i) attends the keys j <= past[b] + i."""
-    _chk_dev(q, k, v, past, out)
-    rows = _bf16_cache(k, v, past.shape[0], Hkv, d)
-    B, pq, ldq, out, po, ldo, ws, n_ws = _cache_attn_args(q, past, n, max_kv_len, rows, Hq, Hkv, d, out, workspace, "mm355_attn_extend_ws_floats")
-    _lib.check(_L().mm355_attn_extend(pq, ldq, k.data_ptr(), v.data_ptr(), k.stride(1), k.stride(0), past.data_ptr(), n, max_kv_len, po, ldo,
-                                      B, Hq, Hkv, d, scale, _p(ws), n_ws, _stream()), f"mm355_attn_extend B={B} n={n} Hq={Hq} Hkv={Hkv} d={d}")
-    return out
+_KV_BF16 = _KVFormat("", _bf16_kv_operands, _bf16_prefix_operands)
+_KV_F8 = _KVFormat("_f8", _f8_kv_operands, _f8_prefix_operands)
 
 
-def attn_extend_f8(q, k8, v8, k_scale, v_scale, past, n, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None):
-    """attn_extend() over an e4m3 cache: k8 / v8 [B, rows, Hkv*d] uint8, k_scale / v_scale [B, rows, Hkv] f32 (mm355_attn_extend_f8): equal to
-    attn_extend() on dequant_kv8() of the cache bit for bit."""
-    _chk_dev(q, k8, v8, k_scale, v_scale, past, out)
-    ldb, bsb, ldsc, bssc = _kv8_caches(k8, v8, k_scale, v_scale, past.shape[0], Hkv, d)
-    B, pq, ldq, out, po, ldo, ws, n_ws = _cache_attn_args(q, past, n, max_kv_len, k8.shape[1], Hq, Hkv, d, out, workspace,
-                                                          "mm355_attn_extend_ws_floats")
-    _lib.check(_L().mm355_attn_extend_f8(pq, ldq, k8.data_ptr(), v8.data_ptr(), ldb, bsb, k_scale.data_ptr(), v_scale.data_ptr(), ldsc, bssc,
-                                         KV8_E4M3, past.data_ptr(), n, max_kv_len, po, ldo, B, Hq, Hkv, d, scale, _p(ws), n_ws, _stream()),
-               f"mm355_attn_extend_f8 B={B} n={n} Hq={Hq} Hkv={Hkv} d={d}")
-    return out
-
-
-# ------------------------------------------------------------------------------------------------ a ragged batch: n_b new rows per sequence
-
-def attn_extend_ragged_supported(Hq, Hkv, d):
-    """the head shapes mm355_attn_extend_ragged takes (else MM355_EUNSUPPORTED): those of mm355_attn_extend"""
-    return d % 8 == 0 and d <= 128 and Hq % Hkv == 0 and Hq // Hkv in (1, 2, 4, 8)
-
-
-def _ragged_attn_args(q, past, row_start, n_max, max_kv_len, rows, Hq, Hkv, d, out, workspace):
-    """_cache_attn_args for the ragged forms: q / out [q_rows, Hq*d], row_start int32 [B + 1] on the device next to past [B]
-    -> (B, q pointer, ld, q_rows, out, its pointer, ld, workspace or None, its floats)"""
-    B = past.shape[0]
-    pq, R, W, ldq = _rows2d(q)
-    assert q.dtype == BF16 and W == Hq * d, (q.shape, Hq, d)
-    assert past.dtype == torch.int32 and row_start.dtype == torch.int32 and row_start.dim() == 1 and row_start.shape[0] == B + 1 and \
-        row_start.is_contiguous(), (past.dtype, row_start.dtype, row_start.shape, B)
-    assert 1 <= n_max <= max_kv_len <= rows, (n_max, max_kv_len, rows)
-    out = torch.empty((R, W), device=q.device, dtype=BF16) if out is None else out
-    po, Ro, Wo, ldo = _rows2d(out)
-    assert out.dtype == BF16 and (Ro, Wo) == (R, W)
-    n_ws = int(_L().mm355_attn_extend_ragged_ws_floats(B, n_max, Hq, Hkv, d, max_kv_len))
-    ws = workspace
-    if n_ws and (ws is None or ws.numel() < n_ws):
-        ws = torch.empty(n_ws, device=q.device, dtype=torch.float32)
-    return B, pq, ldq, R, out, po, ldo, ws, (0 if ws is None else ws.numel())
-
-
-def attn_extend_ragged(q, k, v, past, row_start, n_max, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None):
-    """n_b = row_start[b+1] - row_start[b] new rows of sequence b against its cache (mm355_attn_extend_ragged): q [rows, Hq*d] bf16, already
-    rotated, the rows of sequence b packed at row_start[b] + i (may be a column block of a wider tensor); k / v [B, rows, Hkv*d] bf16 already
-    holding them at past[b] .. past[b]+n_b-1; past int32 [B], row_start int32 [B + 1] on the device; n_max >= every n_b and max_kv_len >= every
-    past[b] + n_b are host bounds.  Row (b, i) attends the keys j <= past[b] + i of block b; n_b == 0 and past[b] == 0 are right."""
-    _chk_dev(q, k, v, past, row_start, out)
-    rows = _bf16_cache(k, v, past.shape[0], Hkv, d)
-    B, pq, ldq, R, out, po, ldo, ws, n_ws = _ragged_attn_args(q, past, row_start, n_max, max_kv_len, rows, Hq, Hkv, d, out, workspace)
-    _lib.check(_L().mm355_attn_extend_ragged(pq, ldq, k.data_ptr(), v.data_ptr(), k.stride(1), k.stride(0), past.data_ptr(), row_start.data_ptr(),
-                                             n_max, R, max_kv_len, po, ldo, B, Hq, Hkv, d, scale, _p(ws), n_ws, _stream()),
-               f"mm355_attn_extend_ragged B={B} n_max={n_max} rows={R} Hq={Hq} Hkv={Hkv} d={d}")
-    return out
-
-
-def attn_extend_ragged_f8(q, k8, v8, k_scale, v_scale, past, row_start, n_max, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None):
-    """attn_extend_ragged() over an e4m3 cache: k8 / v8 [B, rows, Hkv*d] uint8, k_scale / v_scale [B, rows, Hkv] f32
-    (mm355_attn_extend_ragged_f8): equal to attn_extend_ragged() on dequant_kv8() of the cache bit for bit."""
-    _chk_dev(q, k8, v8, k_scale, v_scale, past, row_start, out)
-    ldb, bsb, ldsc, bssc = _kv8_caches(k8, v8, k_scale, v_scale, past.shape[0], Hkv, d)
-    B, pq, ldq, R, out, po, ldo, ws, n_ws = _ragged_attn_args(q, past, row_start, n_max, max_kv_len, k8.shape[1], Hq, Hkv, d, out, workspace)
-    _lib.check(_L().mm355_attn_extend_ragged_f8(pq, ldq, k8.data_ptr(), v8.data_ptr(), ldb, bsb, k_scale.data_ptr(), v_scale.data_ptr(), ldsc,
-                                                bssc, KV8_E4M3, past.data_ptr(), row_start.data_ptr(), n_max, R, max_kv_len, po, ldo, B, Hq,
-                                                Hkv, d, scale, _p(ws), n_ws, _stream()),
-               f"mm355_attn_extend_ragged_f8 B={B} n_max={n_max} rows={R} Hq={Hq} Hkv={Hkv} d={d}")
-    return out
+def _kv_rope_append(fmt, qkv, Hq, Hkv, d, cos, sin, positions, kv):
+    _chk_dev(qkv, cos, sin, positions, *kv)
+    assert positions.dtype == torch.int32
+    B = qkv.shape[0]
+    _, ckv = fmt.cache(kv, B, Hkv, d)
+    fn, name = fmt.sym("rope_kv_append{}")
+    _lib.check(fn(qkv.data_ptr(), qkv.stride(0), B, Hq, Hkv, d, cos.data_ptr(), sin.data_ptr(), positions.data_ptr(), *ckv, _stream()), name)
+    return qkv
 
 
 def _row_tables(qkv, positions, blocks, n_blocks):
@@ -851,39 +727,76 @@ def _row_tables(qkv, positions, blocks, n_blocks):
     return blocks.data_ptr()
 
 
-def rope_kv_append_rows_(qkv, Hq, Hkv, d, cos, sin, positions, blocks, k_cache, v_cache):
-    """rope_kv_append_() with a block per row (mm355_rope_kv_append_rows): qkv [R, (Hq+2Hkv)*d] new rows, any R: q (in place) and k rotated at
-    positions[r]; k, v -> row positions[r] of block blocks[r] of k_cache / v_cache [blocks, rows, Hkv*d] (int32 [R] each, on the device;
-    blocks None: block r).  Out-of-range entries are clamped into the cache."""
-    _chk_dev(qkv, cos, sin, positions, blocks, k_cache, v_cache)
-    assert k_cache.dim() == 3 and k_cache.stride() == v_cache.stride() and k_cache.stride(2) == 1
-    pb = _row_tables(qkv, positions, blocks, k_cache.shape[0])
-    _lib.check(_L().mm355_rope_kv_append_rows(qkv.data_ptr(), qkv.stride(0), qkv.shape[0], Hq, Hkv, d, cos.data_ptr(), sin.data_ptr(),
-                                              positions.data_ptr(), pb, k_cache.shape[0], k_cache.shape[1], k_cache.data_ptr(), v_cache.data_ptr(),
-                                              k_cache.stride(1), k_cache.stride(0), _stream()), "mm355_rope_kv_append_rows")
+def _kv_rope_append_rows(fmt, qkv, Hq, Hkv, d, cos, sin, positions, blocks, kv):
+    _chk_dev(qkv, cos, sin, positions, blocks, *kv)
+    rows, ckv = fmt.cache(kv, 0, Hkv, d)                      # (any number of blocks: the table names them)
+    n_blocks = kv[0].shape[0]
+    pb = _row_tables(qkv, positions, blocks, n_blocks)
+    fn, name = fmt.sym("rope_kv_append_rows{}")
+    _lib.check(fn(qkv.data_ptr(), qkv.stride(0), qkv.shape[0], Hq, Hkv, d, cos.data_ptr(), sin.data_ptr(), positions.data_ptr(), pb, n_blocks,
+                  rows, *ckv, _stream()), name)
     return qkv
 
 
-def rope_kv_append_rows_f8_(qkv, Hq, Hkv, d, cos, sin, positions, blocks, k8, v8, k_scale, v_scale):
-    """rope_kv_append_rows_() into an e4m3 cache (mm355_rope_kv_append_rows_f8): bytes and scales of row positions[r] of block blocks[r],
-    quantised as rope_kv_append_f8_() quantises them."""
-    _chk_dev(qkv, cos, sin, positions, blocks, k8, v8, k_scale, v_scale)
-    assert k8.stride() == v8.stride() and k_scale.stride() == v_scale.stride()
-    ldb, bsb, ldsc, bssc = _kv8_cache(k8, k_scale, Hkv, d)
-    _kv8_cache(v8, v_scale, Hkv, d)
-    pb = _row_tables(qkv, positions, blocks, k8.shape[0])
-    _lib.check(_L().mm355_rope_kv_append_rows_f8(qkv.data_ptr(), qkv.stride(0), qkv.shape[0], Hq, Hkv, d, cos.data_ptr(), sin.data_ptr(),
-                                                 positions.data_ptr(), pb, k8.shape[0], k8.shape[1], k8.data_ptr(), v8.data_ptr(), ldb, bsb,
-                                                 k_scale.data_ptr(), v_scale.data_ptr(), ldsc, bssc, KV8_E4M3, _stream()),
-               "mm355_rope_kv_append_rows_f8")
-    return qkv
+def _kv_attn_decode(fmt, q, kv, kv_lens, max_kv_len, Hq, Hkv, d, scale, out, workspace, variant):
+    _chk_dev(q, *kv, kv_lens)
+    B = q.shape[0]
+    rows, ckv = fmt.cache(kv, B, Hkv, d)
+    assert kv_lens.dtype == torch.int32 and max_kv_len <= rows
+    out = torch.empty((B, Hq * d), device=q.device, dtype=BF16) if out is None else out
+    ws = workspace
+    if ws is None:
+        ws = torch.zeros(int(_L().mm355_attn_decode_ws_floats(B, Hq, d, max_kv_len)), device=q.device, dtype=torch.float32)   # arrival counters start at 0
+    _, name = fmt.sym("attn_decode{}")
+    _lib.check(getattr(_L(), name + "_variant")(q.data_ptr(), q.stride(0), *ckv, kv_lens.data_ptr(), max_kv_len, out.data_ptr(), out.stride(0), B,
+                                                Hq, Hkv, d, scale, ws.data_ptr(), int(variant), _stream()), name)
+    return out
 
 
-# ------------------------------------------------------------------------------------------------ decode over a shared prompt cache
+def _cache_attn_args(q, lens, n, max_kv_len, rows, Hq, Hkv, d, out, workspace, ws_floats, shared_len=None, shared_rows=None, row_start=None):
+    """What the cache-attention wrappers below hand to the C side: n query rows per sequence (None: the decode forms, one row and no such
+    argument), lens the entry point's int32 [B] (past or kv_lens), ws_floats the name of its mm355_*_ws_floats, shared_len / shared_rows
+    where a prefix is stored once.  row_start (the ragged forms): int32 [B + 1] on the device next to lens, sequence b brings the rows
+    row_start[b] .. row_start[b + 1] - 1 of q, at most n >= 1 of them.  -> (B, q pointer, ld, out, its pointer, ld, workspace or None, its
+    floats)"""
+    B = lens.shape[0]
+    pq, R, W, ldq = _rows2d(q)
+    nn, sh = (() if n is None else (n,)), (() if shared_len is None else (shared_len,))      # what the entry point takes of the two
+    assert q.dtype == BF16 and (R == B * (n or 1) or row_start is not None) and W == Hq * d, (q.shape, B, *nn, Hq, d)
+    assert row_start is None or (n >= 1 and row_start.dtype == torch.int32 and row_start.dim() == 1 and row_start.shape[0] == B + 1 and
+                                 row_start.is_contiguous()), (n, row_start.dtype, row_start.shape, B)
+    assert lens.dtype == torch.int32 and (n is None or n <= max_kv_len) and max_kv_len <= rows and \
+        (shared_len is None or 0 <= shared_len <= max_kv_len and shared_len <= shared_rows), (*nn, *sh, max_kv_len, rows)
+    out = torch.empty((R, W), device=q.device, dtype=BF16) if out is None else out
+    po, Ro, Wo, ldo = _rows2d(out)
+    assert out.dtype == BF16 and (Ro, Wo) == (R, W)
+    n_ws = int(getattr(_L(), ws_floats)(B, *nn, Hq, Hkv, d, *sh, max_kv_len))
+    ws = workspace
+    if n_ws and (ws is None or ws.numel() < n_ws):
+        ws = torch.empty(n_ws, device=q.device, dtype=torch.float32)
+    return B, pq, ldq, out, po, ldo, ws, (0 if ws is None else ws.numel())
 
-def attn_decode_shared_supported(Hq, Hkv, d):
-    """the head shapes mm355_attn_decode_shared takes (else MM355_EUNSUPPORTED): d % 8 == 0, d <= 128, a GQA group of 1, 2, 4 or 8"""
-    return d % 8 == 0 and d <= 128 and Hq % Hkv == 0 and Hq // Hkv in (1, 2, 4, 8)
+
+def _kv_attn_extend(fmt, q, kv, past, n, max_kv_len, Hq, Hkv, d, scale, out, workspace):
+    _chk_dev(q, *kv, past, out)
+    rows, ckv = fmt.cache(kv, past.shape[0], Hkv, d)
+    B, pq, ldq, out, po, ldo, ws, n_ws = _cache_attn_args(q, past, n, max_kv_len, rows, Hq, Hkv, d, out, workspace, "mm355_attn_extend_ws_floats")
+    fn, name = fmt.sym("attn_extend{}")
+    _lib.check(fn(pq, ldq, *ckv, past.data_ptr(), n, max_kv_len, po, ldo, B, Hq, Hkv, d, scale, _p(ws), n_ws, _stream()),
+               f"{name} B={B} n={n} Hq={Hq} Hkv={Hkv} d={d}")
+    return out
+
+
+def _kv_attn_extend_ragged(fmt, q, kv, past, row_start, n_max, max_kv_len, Hq, Hkv, d, scale, out, workspace):
+    _chk_dev(q, *kv, past, row_start, out)
+    rows, ckv = fmt.cache(kv, past.shape[0], Hkv, d)
+    B, pq, ldq, out, po, ldo, ws, n_ws = _cache_attn_args(q, past, n_max, max_kv_len, rows, Hq, Hkv, d, out, workspace,
+                                                          "mm355_attn_extend_ragged_ws_floats", row_start=row_start)
+    R = q.shape[0]
+    fn, name = fmt.sym("attn_extend_ragged{}")
+    _lib.check(fn(pq, ldq, *ckv, past.data_ptr(), row_start.data_ptr(), n_max, R, max_kv_len, po, ldo, B, Hq, Hkv, d, scale, _p(ws), n_ws,
+                  _stream()), f"{name} B={B} n_max={n_max} rows={R} Hq={Hq} Hkv={Hkv} d={d}")
+    return out
 
 
 def _own_block(own_block, B):
@@ -891,6 +804,96 @@ def _own_block(own_block, B):
     assert own_block.dtype == torch.uint8 and own_block.dim() == 2 and own_block.stride(1) == 1 and own_block.shape[0] >= B and B <= 255
     assert own_block.shape[1] >= 1
     return own_block.data_ptr(), own_block.stride(0)
+
+
+def _kv_attn_shared(fmt, q, sh, kv, lens, n, shared_len, max_kv_len, Hq, Hkv, d, scale, out, workspace, own_block=None):
+    """attention over a prefix stored once (sh) and every sequence's own rows (kv): n None: the decode step, one row per sequence and lens
+    = kv_lens (mm355_attn_decode_shared, with own_block mm355_attn_decode_shared_idx); else n rows per sequence and lens = past
+    (mm355_attn_extend_shared)."""
+    _chk_dev(q, *sh, *kv, lens, out, own_block)
+    rows, ckv = fmt.cache(kv, lens.shape[0], Hkv, d)
+    shared_rows, csh = fmt.prefix(sh, Hkv, d)
+    op = "attn_decode_shared" if n is None else "attn_extend_shared"
+    B, pq, ldq, out, po, ldo, ws, n_ws = _cache_attn_args(q, lens, n, max_kv_len, rows, Hq, Hkv, d, out, workspace, f"mm355_{op}_ws_floats",
+                                                          shared_len, shared_rows)
+    nn, tbl = (() if n is None else (n,)), (() if own_block is None else _own_block(own_block, B))
+    fn, name = fmt.sym(op + ("_idx{}" if tbl else "{}"))
+    _lib.check(fn(pq, ldq, *csh, *ckv, lens.data_ptr(), *tbl, *nn, shared_len, max_kv_len, po, ldo, B, Hq, Hkv, d, scale, _p(ws), n_ws, _stream()),
+               f"{name} B={B}{''.join(f' n={v}' for v in nn)} Hq={Hq} Hkv={Hkv} d={d} shared_len={shared_len}")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ the KV-cache operations by name, per format
+
+def rope_kv_append_(qkv, Hq, Hkv, d, cos, sin, positions, k_cache, v_cache):
+    """qkv [B, (Hq+2Hkv)*d] new rows: rotate q (in place) and k at positions[b] (int32, device); k, v -> cache row positions[b]."""
+    return _kv_rope_append(_KV_BF16, qkv, Hq, Hkv, d, cos, sin, positions, (k_cache, v_cache))
+
+
+def rope_kv_append_f8_(qkv, Hq, Hkv, d, cos, sin, positions, k8, v8, k_scale, v_scale):
+    """rope_kv_append_() into an e4m3 cache: q rotated in place (the same bits), the rotated k row (rounded to bf16 as the bf16 cache would
+    hold it) and the v row quantised into row positions[b] of k8 / v8 [B, Lmax, Hkv*d] uint8 and k_scale / v_scale [B, Lmax, Hkv] f32."""
+    return _kv_rope_append(_KV_F8, qkv, Hq, Hkv, d, cos, sin, positions, (k8, v8, k_scale, v_scale))
+
+
+def rope_kv_append_rows_(qkv, Hq, Hkv, d, cos, sin, positions, blocks, k_cache, v_cache):
+    """rope_kv_append_() with a block per row (mm355_rope_kv_append_rows): qkv [R, (Hq+2Hkv)*d] new rows, any R: q (in place) and k rotated at
+    positions[r]; k, v -> row positions[r] of block blocks[r] of k_cache / v_cache [blocks, rows, Hkv*d] (int32 [R] each, on the device;
+    blocks None: block r).  Out-of-range entries are clamped into the cache."""
+    return _kv_rope_append_rows(_KV_BF16, qkv, Hq, Hkv, d, cos, sin, positions, blocks, (k_cache, v_cache))
+
+
+def rope_kv_append_rows_f8_(qkv, Hq, Hkv, d, cos, sin, positions, blocks, k8, v8, k_scale, v_scale):
+    """rope_kv_append_rows_() into an e4m3 cache (mm355_rope_kv_append_rows_f8): bytes and scales of row positions[r] of block blocks[r],
+    quantised as rope_kv_append_f8_() quantises them."""
+    return _kv_rope_append_rows(_KV_F8, qkv, Hq, Hkv, d, cos, sin, positions, blocks, (k8, v8, k_scale, v_scale))
+
+
+def attn_decode(q, k_cache, v_cache, kv_lens, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None, variant=0):
+    """q [B, Hq*d]; caches [B, Lmax, Hkv*d]; kv_lens int32 [B] on the device (valid rows incl. the current one)."""
+    return _kv_attn_decode(_KV_BF16, q, (k_cache, v_cache), kv_lens, max_kv_len, Hq, Hkv, d, scale, out, workspace, variant)
+
+
+def attn_decode_f8(q, k8, v8, k_scale, v_scale, kv_lens, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None, variant=0):
+    """attn_decode() over an e4m3 cache: k8 / v8 [B, Lmax, Hkv*d] uint8, k_scale / v_scale [B, Lmax, Hkv] f32 (variants 0 and 2)."""
+    return _kv_attn_decode(_KV_F8, q, (k8, v8, k_scale, v_scale), kv_lens, max_kv_len, Hq, Hkv, d, scale, out, workspace, variant)
+
+
+def attn_extend(q, k, v, past, n, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None):
+    """n new rows per sequence against a filled cache (mm355_attn_extend): q [B*n, Hq*d] bf16, already rotated, row (b, i) at b*n + i (may be
+    a column block of a wider tensor); k / v [B, rows, Hkv*d] bf16 already holding the chunk's own rows at past[b] .. past[b]+n-1; past int32
+    [B] on the device; max_kv_len a host bound with past[b] + n <= max_kv_len <= rows.  Row (b, i) attends the keys j <= past[b] + i."""
+    return _kv_attn_extend(_KV_BF16, q, (k, v), past, n, max_kv_len, Hq, Hkv, d, scale, out, workspace)
+
+
+def attn_extend_f8(q, k8, v8, k_scale, v_scale, past, n, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None):
+    """attn_extend() over an e4m3 cache: k8 / v8 [B, rows, Hkv*d] uint8, k_scale / v_scale [B, rows, Hkv] f32 (mm355_attn_extend_f8): equal to
+    attn_extend() on dequant_kv8() of the cache bit for bit."""
+    return _kv_attn_extend(_KV_F8, q, (k8, v8, k_scale, v_scale), past, n, max_kv_len, Hq, Hkv, d, scale, out, workspace)
+
+
+def attn_extend_ragged_supported(Hq, Hkv, d):
+    """the head shapes mm355_attn_extend_ragged takes (else MM355_EUNSUPPORTED): those of mm355_attn_extend"""
+    return d % 8 == 0 and d <= 128 and Hq % Hkv == 0 and Hq // Hkv in (1, 2, 4, 8)
+
+
+def attn_extend_ragged(q, k, v, past, row_start, n_max, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None):
+    """n_b = row_start[b+1] - row_start[b] new rows of sequence b against its cache (mm355_attn_extend_ragged): q [rows, Hq*d] bf16, already
+    rotated, the rows of sequence b packed at row_start[b] + i (may be a column block of a wider tensor); k / v [B, rows, Hkv*d] bf16 already
+    holding them at past[b] .. past[b]+n_b-1; past int32 [B], row_start int32 [B + 1] on the device; n_max >= every n_b and max_kv_len >= every
+    past[b] + n_b are host bounds.  Row (b, i) attends the keys j <= past[b] + i of block b; n_b == 0 and past[b] == 0 are right."""
+    return _kv_attn_extend_ragged(_KV_BF16, q, (k, v), past, row_start, n_max, max_kv_len, Hq, Hkv, d, scale, out, workspace)
+
+
+def attn_extend_ragged_f8(q, k8, v8, k_scale, v_scale, past, row_start, n_max, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None):
+    """attn_extend_ragged() over an e4m3 cache: k8 / v8 [B, rows, Hkv*d] uint8, k_scale / v_scale [B, rows, Hkv] f32
+    (mm355_attn_extend_ragged_f8): equal to attn_extend_ragged() on dequant_kv8() of the cache bit for bit."""
+    return _kv_attn_extend_ragged(_KV_F8, q, (k8, v8, k_scale, v_scale), past, row_start, n_max, max_kv_len, Hq, Hkv, d, scale, out, workspace)
+
+
+def attn_decode_shared_supported(Hq, Hkv, d):
+    """the head shapes mm355_attn_decode_shared takes (else MM355_EUNSUPPORTED): d % 8 == 0, d <= 128, a GQA group of 1, 2, 4 or 8"""
+    return d % 8 == 0 and d <= 128 and Hq % Hkv == 0 and Hq // Hkv in (1, 2, 4, 8)
 
 
 def attn_decode_shared(q, k_shared, v_shared, k_cache, v_cache, kv_lens, shared_len, max_kv_len, Hq, Hkv, d, scale, out=None, workspace=None,
@@ -901,22 +904,8 @@ def attn_decode_shared(q, k_shared, v_shared, k_cache, v_cache, kv_lens, shared_
     device, kv_lens[b] >= shared_len; shared_len and max_kv_len host bounds.  Rows [0, shared_len) of the own blocks are never read.
     own_block (uint8 [B, columns] on the device; the beams of a beam search): own row j of query b is row j of block own_block[b, j -
     shared_len] (mm355_attn_decode_shared_idx); None is the identity."""
-    _chk_dev(q, k_shared, v_shared, k_cache, v_cache, kv_lens, out, own_block)
-    rows, shared_rows = _bf16_cache(k_cache, v_cache, kv_lens.shape[0], Hkv, d), _shared_rows(k_shared, v_shared, Hkv, d)
-    B, pq, ldq, out, po, ldo, ws, n_ws = _cache_attn_args(q, kv_lens, None, max_kv_len, rows, Hq, Hkv, d, out, workspace,
-                                                          "mm355_attn_decode_shared_ws_floats", shared_len, shared_rows)
-    if own_block is not None:
-        pt, ldt = _own_block(own_block, B)
-        _lib.check(_L().mm355_attn_decode_shared_idx(pq, ldq, k_shared.data_ptr(), v_shared.data_ptr(), k_shared.stride(0), k_cache.data_ptr(),
-                                                     v_cache.data_ptr(), k_cache.stride(1), k_cache.stride(0), kv_lens.data_ptr(), pt, ldt,
-                                                     shared_len, max_kv_len, po, ldo, B, Hq, Hkv, d, scale, _p(ws), n_ws, _stream()),
-                   f"mm355_attn_decode_shared_idx B={B} Hq={Hq} Hkv={Hkv} d={d} shared_len={shared_len}")
-        return out
-    _lib.check(_L().mm355_attn_decode_shared(pq, ldq, k_shared.data_ptr(), v_shared.data_ptr(), k_shared.stride(0), k_cache.data_ptr(),
-                                             v_cache.data_ptr(), k_cache.stride(1), k_cache.stride(0), kv_lens.data_ptr(), shared_len, max_kv_len,
-                                             po, ldo, B, Hq, Hkv, d, scale, _p(ws), n_ws, _stream()),
-               f"mm355_attn_decode_shared B={B} Hq={Hq} Hkv={Hkv} d={d} shared_len={shared_len}")
-    return out
+    return _kv_attn_shared(_KV_BF16, q, (k_shared, v_shared), (k_cache, v_cache), kv_lens, None, shared_len, max_kv_len, Hq, Hkv, d, scale, out,
+                           workspace, own_block)
 
 
 def attn_decode_shared_f8(q, k_shared, v_shared, k_shared_scale, v_shared_scale, k8, v8, k_scale, v_scale, kv_lens, shared_len, max_kv_len, Hq,
@@ -924,29 +913,9 @@ def attn_decode_shared_f8(q, k_shared, v_shared, k_shared_scale, v_shared_scale,
     """attn_decode_shared() over e4m3 bytes: k_shared / v_shared [>= shared_len, Hkv*d] uint8 with scales [>= shared_len, Hkv] f32, k8 / v8 [B,
     rows, Hkv*d] uint8 with k_scale / v_scale [B, rows, Hkv] f32 (mm355_attn_decode_shared_f8): equal to attn_decode_shared() on dequant_kv8()
     of the same bytes bit for bit.  own_block: as for attn_decode_shared (mm355_attn_decode_shared_idx_f8), bytes and scales follow it."""
-    _chk_dev(q, k_shared, v_shared, k_shared_scale, v_shared_scale, k8, v8, k_scale, v_scale, kv_lens, out, own_block)
-    ldb, bsb, ldsc, bssc = _kv8_caches(k8, v8, k_scale, v_scale, kv_lens.shape[0], Hkv, d)
-    shared_rows = _shared_rows_f8(k_shared, v_shared, k_shared_scale, v_shared_scale, Hkv, d)
-    B, pq, ldq, out, po, ldo, ws, n_ws = _cache_attn_args(q, kv_lens, None, max_kv_len, k8.shape[1], Hq, Hkv, d, out, workspace,
-                                                          "mm355_attn_decode_shared_ws_floats", shared_len, shared_rows)
-    if own_block is not None:
-        pt, ldt = _own_block(own_block, B)
-        _lib.check(_L().mm355_attn_decode_shared_idx_f8(pq, ldq, k_shared.data_ptr(), v_shared.data_ptr(), k_shared.stride(0),
-                                                        k_shared_scale.data_ptr(), v_shared_scale.data_ptr(), k_shared_scale.stride(0),
-                                                        k8.data_ptr(), v8.data_ptr(), ldb, bsb, k_scale.data_ptr(), v_scale.data_ptr(), ldsc,
-                                                        bssc, KV8_E4M3, kv_lens.data_ptr(), pt, ldt, shared_len, max_kv_len, po, ldo, B, Hq,
-                                                        Hkv, d, scale, _p(ws), n_ws, _stream()),
-                   f"mm355_attn_decode_shared_idx_f8 B={B} Hq={Hq} Hkv={Hkv} d={d} shared_len={shared_len}")
-        return out
-    _lib.check(_L().mm355_attn_decode_shared_f8(pq, ldq, k_shared.data_ptr(), v_shared.data_ptr(), k_shared.stride(0), k_shared_scale.data_ptr(),
-                                                v_shared_scale.data_ptr(), k_shared_scale.stride(0), k8.data_ptr(), v8.data_ptr(), ldb, bsb,
-                                                k_scale.data_ptr(), v_scale.data_ptr(), ldsc, bssc, KV8_E4M3, kv_lens.data_ptr(), shared_len,
-                                                max_kv_len, po, ldo, B, Hq, Hkv, d, scale, _p(ws), n_ws, _stream()),
-               f"mm355_attn_decode_shared_f8 B={B} Hq={Hq} Hkv={Hkv} d={d} shared_len={shared_len}")
-    return out
+    return _kv_attn_shared(_KV_F8, q, (k_shared, v_shared, k_shared_scale, v_shared_scale), (k8, v8, k_scale, v_scale), kv_lens, None, shared_len,
+                           max_kv_len, Hq, Hkv, d, scale, out, workspace, own_block)
 
-
-# ------------------------------------------------------------------------------------------------ extending a shared-prefix cache by n rows
 
 def attn_extend_shared_supported(Hq, Hkv, d):
     """the head shapes mm355_attn_extend_shared takes (else MM355_EUNSUPPORTED): those of mm355_attn_decode_shared"""
@@ -959,15 +928,7 @@ def attn_extend_shared(q, k_shared, v_shared, k_cache, v_cache, past, n, shared_
     Hkv*d] bf16; k_cache / v_cache [B, rows, Hkv*d] bf16 already holding sequence b's new rows at past[b] .. past[b]+n-1; past int32 [B] on the
     device, past[b] >= shared_len; n, shared_len and max_kv_len host bounds.  Row (b, i) attends the shared rows and then rows [shared_len,
     past[b] + i] of block b.  Rows [0, shared_len) of the own blocks are never read."""
-    _chk_dev(q, k_shared, v_shared, k_cache, v_cache, past, out)
-    rows, shared_rows = _bf16_cache(k_cache, v_cache, past.shape[0], Hkv, d), _shared_rows(k_shared, v_shared, Hkv, d)
-    B, pq, ldq, out, po, ldo, ws, n_ws = _cache_attn_args(q, past, n, max_kv_len, rows, Hq, Hkv, d, out, workspace,
-                                                          "mm355_attn_extend_shared_ws_floats", shared_len, shared_rows)
-    _lib.check(_L().mm355_attn_extend_shared(pq, ldq, k_shared.data_ptr(), v_shared.data_ptr(), k_shared.stride(0), k_cache.data_ptr(),
-                                             v_cache.data_ptr(), k_cache.stride(1), k_cache.stride(0), past.data_ptr(), n, shared_len,
-                                             max_kv_len, po, ldo, B, Hq, Hkv, d, scale, _p(ws), n_ws, _stream()),
-               f"mm355_attn_extend_shared B={B} n={n} Hq={Hq} Hkv={Hkv} d={d} shared_len={shared_len}")
-    return out
+    return _kv_attn_shared(_KV_BF16, q, (k_shared, v_shared), (k_cache, v_cache), past, n, shared_len, max_kv_len, Hq, Hkv, d, scale, out, workspace)
 
 
 def attn_extend_shared_f8(q, k_shared, v_shared, k_shared_scale, v_shared_scale, k8, v8, k_scale, v_scale, past, n, shared_len, max_kv_len, Hq,
@@ -975,17 +936,8 @@ def attn_extend_shared_f8(q, k_shared, v_shared, k_shared_scale, v_shared_scale,
     """attn_extend_shared() over e4m3 bytes: k_shared / v_shared [>= shared_len, Hkv*d] uint8 with scales [>= shared_len, Hkv] f32, k8 / v8 [B,
     rows, Hkv*d] uint8 with k_scale / v_scale [B, rows, Hkv] f32 (mm355_attn_extend_shared_f8): equal to attn_extend_shared() on dequant_kv8()
     of the same bytes bit for bit."""
-    _chk_dev(q, k_shared, v_shared, k_shared_scale, v_shared_scale, k8, v8, k_scale, v_scale, past, out)
-    ldb, bsb, ldsc, bssc = _kv8_caches(k8, v8, k_scale, v_scale, past.shape[0], Hkv, d)
-    shared_rows = _shared_rows_f8(k_shared, v_shared, k_shared_scale, v_shared_scale, Hkv, d)
-    B, pq, ldq, out, po, ldo, ws, n_ws = _cache_attn_args(q, past, n, max_kv_len, k8.shape[1], Hq, Hkv, d, out, workspace,
-                                                          "mm355_attn_extend_shared_ws_floats", shared_len, shared_rows)
-    _lib.check(_L().mm355_attn_extend_shared_f8(pq, ldq, k_shared.data_ptr(), v_shared.data_ptr(), k_shared.stride(0), k_shared_scale.data_ptr(),
-                                                v_shared_scale.data_ptr(), k_shared_scale.stride(0), k8.data_ptr(), v8.data_ptr(), ldb, bsb,
-                                                k_scale.data_ptr(), v_scale.data_ptr(), ldsc, bssc, KV8_E4M3, past.data_ptr(), n, shared_len,
-                                                max_kv_len, po, ldo, B, Hq, Hkv, d, scale, _p(ws), n_ws, _stream()),
-               f"mm355_attn_extend_shared_f8 B={B} n={n} Hq={Hq} Hkv={Hkv} d={d} shared_len={shared_len}")
-    return out
+    return _kv_attn_shared(_KV_F8, q, (k_shared, v_shared, k_shared_scale, v_shared_scale), (k8, v8, k_scale, v_scale), past, n, shared_len,
+                           max_kv_len, Hq, Hkv, d, scale, out, workspace)
 
 
 def transpose(x, out=None, ld_out=None):
