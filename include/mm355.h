@@ -974,6 +974,57 @@ int mm355_beam_advance(const float* cand_val, const int32_t* cand_idx, int64_t K
                        int max_new_tokens, float length_penalty, int early_stopping, const int32_t* eos_ids, int n_eos, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Prompt-lookup speculative decoding in the greedy device loop (csrc/spec.hip, functional.SpecGreedyLoopGraph; HF's
+ * prompt_lookup_num_tokens).  A step carries n = K + 1 rows per sequence through the decoder, row (b, i) at b * n + i: row 0 is the
+ * sequence's real next input, rows 1 .. n_draft[b] the embeddings of guessed next ids, the rest dummies.  Row (b, i) is appended at cache
+ * row pos[b] + i and sees the rows before it (mm355_rope_kv_append_rows, mm355_attn_extend), so its argmax is the loop's next id whenever
+ * the guesses before it were right.  One workgroup per sequence in both kernels; no atomics but the decrement of live[0], which is
+ * mm355_greedy_advance's.
+ * ngram_draft_rows: the guesses.  hist [B, hist_cap] int32 holds what a sequence's drafts are looked up in -- its lookup ids (any int32:
+ *         the -200 image sentinel stays in) followed by the ids it has logged --, hist_len [B] how many.  The rule is
+ *         PromptLookupCandidateGenerator.get_candidates with no eos ids, no logits processor and no max_length:
+ *           for m = min(N, len - 1) .. 1: the pattern is the last m ids; among the indices idx < len - m where it occurs, the LOWEST whose
+ *           continuation hist[idx + m : min(idx + m + K, len)], cropped at the first id outside [0, C), is not empty gives the drafts
+ *           (the trailing occurrence has none; a match whose continuation begins outside [0, C) is skipped); the first m with such an
+ *           index wins; none: 0 drafts.  A sequence whose in_image is set gets 0 drafts; for one that is done only pos_rows is written (its rows
+ *           keep landing at and above its length; the loop's warm-up and capture run with every sequence done and must leave the first
+ *           step's drafts alone, and pos_rows is then what it was).
+ *         The scan is strided over the workgroup (any len), the minimum over the hits taken in fixed order.  Writes drafts [B, K] (-1
+ *         behind the drafts), n_draft [B], and the step's input: x_in row b * n + 1 + j = embed[drafts[b][j]] for j < n_draft[b] and a
+ *         row of zeros for the other j < K (row b * n is NOT written: it is the advance kernel's), pos_rows[b * n + i] = pos[b] + i,
+ *         mask_rows[b * n + i] = in_image[b] for i == 0, else 0 (the head's row select).  Writes none of the loop's state.
+ *         The host model: functional.prompt_lookup_host.
+ * spec_verify_advance: tok [B * n] = the argmax of every row.  For i = 0, 1, ... ONE iteration of mm355_greedy_advance's transition
+ *         (functional.greedy_advance_host) with tok[b * n + i], fed / pred_z taken from row b * n + i, the logs and caps as there.  The
+ *         iteration is counted, and the walk ends at the first of: it logged nothing (a full log: the sequence is set done); the
+ *         sequence is now done; it was an image row (the next input is a fed row, not an id's embedding); the sequence is now in image
+ *         mode (the next row's head mask differs); i == n_draft[b]; tok != drafts[b][i].  With a iterations counted: the logged ids are
+ *         appended to hist (hist_len advances; a full hist is left as it is), x_in row b * n becomes what mm355_greedy_advance would
+ *         write after the last logging iteration, and, count_step != 0: pos[b] += a, len[b] += a (the cache's write position and
+ *         visible length: rows pos .. pos + a - 1 of this step were right inputs), acc_log[b][n_steps[b]++] = a (acc_log [B, acc_cap]; a
+ *         full log row is left).  count_step == 0: the loop's first iteration, run on the prompt's last hidden row without a decoder
+ *         step -- no cache row was appended, pos / len / acc_log / n_steps are not touched (and may be NULL).  A sequence that is done
+ *         on entry writes NOTHING: a finished sequence's cache length stands still.  live[0] is decremented when a sequence finishes.
+ *         eos_ids: HOST memory.  The host model: functional.spec_advance_host, a loop over greedy_advance_host.
+ * MM355_EINVAL before any launch: a null pointer, K outside [1, MM355_SPEC_MAX_DRAFT], N outside [1, MM355_SPEC_MAX_NGRAM], B < 1, C < 1
+ * or > embed_rows, hist_cap < 1, h % 8 or Dz % 8 != 0, rows that are not 16-byte vectors, more than MM355_GREEDY_MAX_EOS eos ids.
+ * ------------------------------------------------------------------------------------------------ */
+#define MM355_SPEC_MAX_DRAFT 15
+#define MM355_SPEC_MAX_NGRAM 8
+int mm355_ngram_draft_rows(const int32_t* hist, int64_t hist_cap, const int32_t* hist_len, const int32_t* done, const int32_t* in_image,
+                           const int32_t* pos, int64_t B, int K, int N, int64_t C, const mm355_bf16* embed, int64_t ld_embed,
+                           int64_t embed_rows, int32_t* drafts, int32_t* n_draft, mm355_bf16* x_in, int64_t ld_x, int64_t h,
+                           int32_t* pos_rows, int32_t* mask_rows, void* stream);
+int mm355_spec_verify_advance(const int32_t* tok, const int32_t* drafts, const int32_t* n_draft, int64_t B, int K, int64_t C,
+                              int32_t* in_image, int32_t* n_img, int32_t* total_out, int32_t* done, int32_t* n_tokens, int32_t* n_z,
+                              int32_t* live, const mm355_bf16* embed, int64_t ld_embed, int64_t embed_rows, const mm355_bf16* fed,
+                              int64_t ld_fed, const mm355_bf16* pred_z, int64_t ld_z, mm355_bf16* x_in, int64_t ld_x, int64_t h,
+                              int64_t Dz, int32_t* tok_log, int64_t token_cap, mm355_bf16* z_log, int64_t z_cap, int32_t* hist,
+                              int64_t hist_cap, int32_t* hist_len, int32_t* pos, int32_t* len, int32_t* acc_log, int64_t acc_cap,
+                              int32_t* n_steps, int count_step, int start_id, int end_id, int num_image_tokens, int max_new_tokens,
+                              const int32_t* eos_ids, int n_eos, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * ZeRO-2 shard update (replaces DeepSpeed zero2.json + HF adamw_torch, train.py:82): AdamW on the
  * rank's fp32 master shard, writes the updated bf16 parameters.  grad_scale_dev (nullable) is a device
  * scalar multiplied into the gradient (1/world, clip coefficient).

@@ -1530,12 +1530,65 @@ def _decode_rows16(x, layers, meta, cache, cos, sin, kv_bound):
             act = rec.gemv_swiglu(n2, *rec.gu, meta.I, norm_w=layer.post_attention_layernorm.weight if fold else None, eps=meta.eps)
             x = rec.gemv(act, *rec.down, residual=x2)
             continue
-        n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
-        o = _append_attend(rec.gemv(n1, *rec.qkv), rows, meta, cache, cos, sin, kv_bound)
-        x2 = rec.gemv(o, *rec.o, residual=x)
-        n2 = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
-        act = ops.swiglu_fwd(rec.gemv(n2, *rec.gu), meta.I)
-        x = rec.gemv(act, *rec.down, residual=x2)
+        x = _rows16_unfused(x, layer, rec, meta, lambda qkv: _append_attend(qkv, rows, meta, cache, cos, sin, kv_bound))
+    return x
+
+
+def _rows16_unfused(x, layer, rec, meta, append_attend):
+    """One layer of the 16-row GEMV route with every norm, the attention step and SwiGLU as launches of their own (nine and more per
+    layer); rec: the layer's W8Layer record or _bf16_rows16(layer); append_attend(qkv) -> o is the caller's attention step."""
+    n1 = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, meta.eps)
+    o = append_attend(rec.gemv(n1, *rec.qkv))
+    x2 = rec.gemv(o, *rec.o, residual=x)
+    n2 = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, meta.eps)
+    act = ops.swiglu_fwd(rec.gemv(n2, *rec.gu), meta.I)
+    return rec.gemv(act, *rec.down, residual=x2)
+
+
+def verify_rows_supported(meta):
+    """the head shapes decoder_verify_rows takes: those of mm355_attn_extend with d % 16 == 0 (mm355_rope_kv_append_rows)"""
+    return ops.attn_extend_supported(meta.Hq, meta.Hkv, meta.d) and meta.d % 16 == 0
+
+
+def decoder_verify_rows(x, layers, meta, cache, n, pos_rows, blocks, kv_bound):
+    """n rows PER SEQUENCE against the cache in one pass over the weights, positions read from the device: x [B * n, h], row (b, i) at b * n
+    + i -> hidden rows [B * n, h] (pre final norm).  Row (b, i) is rotated at pos_rows[b * n + i] and appended there in block blocks[b * n +
+    i] (int32 device tables; the caller keeps pos_rows[b * n + i] = cache.pos_dev[b] + i and blocks = r // n), then attends the keys j <=
+    cache.pos_dev[b] + i of its sequence: the attention step of a layer is the plain q|k|v projection, ONE mm355_rope_kv_append_rows launch
+    and ONE mm355_attn_extend call with past = cache.pos_dev, on a bf16 or an fp8_e4m3 cache alike (read back quantised, as n decode steps
+    read it).  Row (b, i) therefore gets what decoder_decode_row would give it as the i-th of n successive steps -- the step of prompt-lookup
+    speculation (SpecGreedyLoopGraph): rows 1.. are guesses, and whoever verifies them decides how many rows count.  The function changes
+    NO length (cache.pos_dev / len_dev / lengths): rows above a sequence's length are not visible to a later step and are overwritten.
+    kv_bound: the host bound of the attention launch, every pos + n <= kv_bound <= cache.max_len.  Up to 16 rows: the GEMV route of
+    _decode_rows16 in its unfused form (a quantised layer on its bytes); more: _fused_walk with the decode step's gate|up rule.  No host
+    value enters a launch but the shapes: capturable once."""
+    R = x.shape[0]
+    if R != cache.batch * n or n < 1:
+        raise ValueError(f"decoder_verify_rows: {R} rows for {cache.batch} sequences of n = {n} rows")
+    if cache.shared_len > 0:
+        raise ValueError(f"decoder_verify_rows on a cache with a shared prefix of {cache.shared_len} rows is not built")
+    if not verify_rows_supported(meta):
+        raise ValueError(f"decoder_verify_rows: no kernel for Hq={meta.Hq} Hkv={meta.Hkv} d={meta.d} (ops.attn_extend_supported, d % 16 == 0)")
+    if not n <= kv_bound <= cache.max_len:
+        raise ValueError(f"decoder_verify_rows: attention bound {kv_bound} for n = {n} rows on a cache of {cache.max_len} rows")
+    H = (meta.Hq, meta.Hkv, meta.d)
+    nq = meta.Hq * meta.d
+    n_ws = int(ops._L().mm355_attn_extend_ws_floats(cache.batch, n, *H, kv_bound))
+    ws = torch.empty(max(n_ws, 4), device=x.device, dtype=torch.float32)
+
+    def append_attend(qkv, i):
+        rows = cache.rows[i]
+        rows.rope_append_rows_(qkv, *H, meta.cos, meta.sin, pos_rows, blocks)
+        return rows.attn_extend(qkv[:, :nq], cache.pos_dev, n, kv_bound, *H, meta.scale, workspace=ws)
+
+    if R > 16:
+        return _fused_walk(x, layers, meta, lambda qkv, i: append_attend(qkv("gemm", ops.gemm_splitk), i), prompt=False)
+    for i, layer in enumerate(layers):
+        rec = getattr(layer, "w8", None)
+        if rec is None:
+            params_ready(layer)
+            rec = _bf16_rows16(layer)
+        x = _rows16_unfused(x, layer, rec, meta, lambda qkv: append_attend(qkv, i))
     return x
 
 
@@ -2190,6 +2243,178 @@ class GreedyLoopGraph(_CapturedStep):
         if self.processors is not None and self.processors.want_logprobs:
             out += ([self.logp_log[b, :n_tok[b]].clone() for b in range(len(n_tok))],)
         return out
+
+
+SPEC_MAX_DRAFT, SPEC_MAX_NGRAM = ops.SPEC_MAX_DRAFT, ops.SPEC_MAX_NGRAM      # MM355_SPEC_MAX_DRAFT, MM355_SPEC_MAX_NGRAM
+
+
+def prompt_lookup_host(hist, K, N, C):
+    """The drafts of ONE sequence on plain ints: the specification of mm355_ngram_draft_rows, equal to HF's
+    PromptLookupCandidateGenerator.get_candidates (num_output_tokens = K, max_matching_ngram_size = N, no eos ids, no logits processor,
+    unbounded max_length) wherever every id lies in [0, C).  hist: the lookup ids followed by the ids logged so far.  For m = min(N, len -
+    1) down to 1 the last m ids are the pattern; the LOWEST index where it occurs and whose continuation hist[idx + m : idx + m + K],
+    cropped at the first id outside [0, C), is not empty gives the drafts (the trailing occurrence has no continuation; a match whose
+    continuation starts with such an id is skipped).  Returns the list of drafts, [] if no m has a match."""
+    hist = [int(t) for t in hist]
+    L = len(hist)
+    for m in range(min(int(N), L - 1), 0, -1):
+        pat = hist[L - m:]
+        for idx in range(L - m):
+            if hist[idx] == pat[0] and hist[idx:idx + m] == pat:
+                out = []
+                for t in hist[idx + m:idx + m + int(K)]:
+                    if not 0 <= t < C:
+                        break
+                    out.append(t)
+                if out:
+                    return out
+    return []
+
+
+def spec_advance_host(state, toks, drafts, start_id, end_id, num_image_tokens, max_new_tokens, eos_ids, token_cap=None, z_cap=None):
+    """One step of prompt-lookup speculation for ONE sequence on plain ints: the specification of mm355_spec_verify_advance, a loop over
+    greedy_advance_host.  toks: the argmax of the step's rows (row 0: the real next input, row i: the input drafts[i - 1]), at least
+    len(drafts) + 1 of them.  Iteration i runs greedy_advance_host with toks[i]; the walk ends after the first iteration that logged
+    nothing (a full log), finished the sequence, was an image row (the next input is a fed row), left the sequence in image mode (the next
+    row's head mask differs), was the last row with a draft behind it (i == len(drafts)) or whose id is not the draft the next row was fed
+    (toks[i] != drafts[i]).  state is updated in place.  Returns the iterations run as greedy_advance_host's (log, next_row) pairs -- []
+    for a sequence that was done on entry; their number is what the cache's length advances by."""
+    out = []
+    if state["done"]:
+        return out
+    for i, tok in enumerate(toks):
+        log, nxt = greedy_advance_host(state, int(tok), start_id, end_id, num_image_tokens, max_new_tokens, eos_ids, token_cap=token_cap,
+                                       z_cap=z_cap)
+        out.append((log, nxt))
+        if log is None or state["done"] or log == "z" or state["in_image"] or i >= len(drafts) or int(tok) != int(drafts[i]):
+            break
+    return out
+
+
+class SpecGreedyLoopGraph(_CapturedStep):
+    """GreedyLoopGraph with prompt-lookup speculation (HF's prompt_lookup_num_tokens; no second model): a step carries n = K + 1 rows per
+    sequence -- its real next input and up to K ids guessed from its own text -- and emits up to n ids.  One step is decoder_verify_rows
+    (B * n rows, one pass over the weights) -> `head` on all rows with the per-row mode mask -> mm355_argmax_rows_f32 over B * n rows ->
+    mm355_spec_verify_advance (the reference's branch, greedy_advance_host, over the rows of a sequence while its guesses hold; advances
+    the cache's pos_dev / len_dev by the iterations run) -> mm355_ngram_draft_rows (the next step's guesses and input rows): the step reads
+    no host value and its shape is fixed, so it is ONE hipGraph on one stream, captured for one attention bound, the cache's capacity.
+    Every emitted id is the argmax of a row computed on the correct prefix -- the loop is the sequential greedy loop run on a subset of the
+    step's rows; rejected and dummy rows land above a sequence's length, are never read and are overwritten by the next step.  A finished
+    sequence advances by 0 (the kernels write no state for it; its rows keep landing at its length, where nobody reads them), so max(L_b) + max_new_tokens + 2 + K cache rows suffice; the host keeps an
+    upper bound of the lengths, refuses a cache that cannot hold another n rows, and sets cache.lengths from len_dev after the run.
+    lookup_ids: one id list per sequence, the text its drafts are looked up in (with what it emits appended); ids outside [0, C) are kept:
+    they match nothing the loop emits and end a draft.  head(x [B * n, h], mask int32 [B * n], logits_out f32 [B * n, C]) -> (fed, pred_z).
+    After run(): `steps`, `host_reads`, `emitted` (loop iterations per sequence) and `acc_log` (per sequence the iterations each of its
+    steps advanced, the first iteration -- run on the prompt's last row without a step -- not among them)."""
+    label = "speculative greedy"
+
+    def __init__(self, layers, meta, cache, cos, sin, h, device, head, embed, C, Dz, start_id, end_id, num_image_tokens, max_new_tokens,
+                 eos_ids, lookup_ids, num_draft, max_ngram=2, poll=8):
+        K, N = int(num_draft), int(max_ngram)
+        if not 1 <= K <= SPEC_MAX_DRAFT or not 1 <= N <= SPEC_MAX_NGRAM:
+            raise ValueError(f"speculative loop: {K} drafts (1 .. {SPEC_MAX_DRAFT}) from n-grams of up to {N} ids (1 .. {SPEC_MAX_NGRAM})")
+        if len(eos_ids) > ops.GREEDY_MAX_EOS:
+            raise ValueError(f"{len(eos_ids)} eos ids: the device loop takes up to {ops.GREEDY_MAX_EOS}")
+        if C > embed.shape[0]:
+            raise ValueError(f"{C} logits over an embedding of {embed.shape[0]} rows: an argmax id would be no row of it")
+        if int(poll) < 1:
+            raise ValueError(f"mm355_greedy_poll_steps = {poll}: the live counter is read every poll >= 1 steps")
+        B = cache.batch
+        if len(lookup_ids) != B:
+            raise ValueError(f"{len(lookup_ids)} lists of lookup ids for {B} sequences")
+        if not verify_rows_supported(meta):
+            raise ValueError(f"speculative loop: no kernel for Hq={meta.Hq} Hkv={meta.Hkv} d={meta.d} (ops.attn_extend_supported, d % 16 == 0)")
+        if meta.cos is not cos or meta.sin is not sin:
+            raise ValueError("speculative loop: meta.cos / meta.sin must be the RoPE tables cos / sin (decoder_verify_rows reads them from meta)")
+        super().__init__(layers, meta, cache, cos, sin)
+        self.head, self.embed, self.C = head, embed, int(C)
+        self.K, self.N, self.n = K, N, K + 1
+        n, R = self.n, B * (K + 1)
+        self.max_new_tokens, self.poll = int(max_new_tokens), int(poll)
+        self.scalars = (int(start_id), int(end_id), int(num_image_tokens), self.max_new_tokens, sorted(int(e) for e in eos_ids))
+        cap = self.max_new_tokens + 1                        # iterations of the loop: total_out > max_new_tokens ends it
+        i32 = dict(device=device, dtype=torch.int32)
+        self.x_in = torch.zeros((R, h), device=device, dtype=BF16)
+        self.state = torch.zeros((len(GREEDY_STATE), B), **i32)
+        self.live = torch.full((1,), B, **i32)
+        self.logits = torch.empty((R, self.C), device=device, dtype=torch.float32)
+        self.tok = torch.zeros(R, **i32)
+        self.arg_ws = ops.argmax_rows_ws(R, self.C, device)
+        self.tok_log = torch.zeros((B, cap), **i32)
+        self.z_log = torch.zeros((B, cap, Dz), device=device, dtype=BF16)
+        look = [[int(t) for t in ids] for ids in lookup_ids]
+        hist = np.zeros((B, max(len(ids) for ids in look) + cap), dtype=np.int32)
+        for b, ids in enumerate(look):
+            hist[b, :len(ids)] = ids
+        self.hist = torch.from_numpy(hist).to(device)
+        self.hist_len = torch.tensor([len(ids) for ids in look], dtype=torch.int32).to(device)
+        self.drafts = torch.full((B, K), -1, **i32)
+        self.n_draft = torch.zeros(B, **i32)
+        self.pos_rows = torch.zeros(R, **i32)
+        self.mask_rows = torch.zeros(R, **i32)
+        self.blocks = (torch.arange(R, dtype=torch.int32) // n).to(device)
+        self.acc = torch.zeros((B, cap), **i32)
+        self.n_steps = torch.zeros(B, **i32)
+        self.prompt_lengths = list(cache.lengths)
+        self._len_cap = max(cache.lengths) + cap             # no sequence grows beyond it: it is done after `cap` iterations
+        self._upper = max(cache.lengths)                     # upper bound of the device-resident lengths
+        self.host_reads = 0
+        self.steps = 0
+        self.emitted, self.acc_log = None, None
+
+    def _launches(self, bound=None):
+        layers, meta, cache, _, _ = self.args
+        return self._tail(decoder_verify_rows(self.x_in, layers, meta, cache, self.n, self.pos_rows, self.blocks,
+                                              cache.max_len if bound is None else bound))
+
+    def _tail(self, x, count_step=True):
+        fed, pred_z = self.head(x, self.mask_rows, self.logits)
+        ops.argmax_rows(self.logits, out=self.tok, ws=self.arg_ws)
+        cache = self.cache
+        ops.spec_verify_advance(self.tok, self.drafts, self.n_draft, self.C, self.state, self.live, self.embed, fed, pred_z, self.x_in,
+                                self.tok_log, self.z_log, self.hist, self.hist_len, cache.pos_dev, cache.len_dev, self.acc, self.n_steps,
+                                *self.scalars, count_step=count_step)
+        ops.ngram_draft_rows(self.hist, self.hist_len, self.state, cache.pos_dev, self.K, self.N, self.C, self.embed, self.drafts,
+                             self.n_draft, self.x_in, self.pos_rows, self.mask_rows)
+
+    def _quiet(self):
+        return self.state[3], 1                              # with every sequence done the kernels write no state (pos_rows: what it was)
+
+    def _captured(self):
+        """the one (graph, output), captured at the first step -- the device lengths still equal the host's then, which _capture restores
+        around its warm-up --; None: eager launches.  Refuses a cache that cannot hold another n rows of the longest possible sequence."""
+        cache = self.cache
+        if self._upper + self.n > cache.max_len:
+            raise ValueError(f"KV cache of {cache.max_len} rows cannot hold another {self.n} rows behind up to {self._upper}")
+        if self.capture_ok and cache.max_len not in self.graphs:
+            self._capture(cache.max_len)
+        return self.graphs[cache.max_len] if self.capture_ok else None
+
+    def _replay(self, entry):
+        entry[0].replay()                                    # (the lengths move on the device alone)
+        return entry[1]
+
+    def _step(self):
+        super()._step()
+        self._upper = min(self._upper + self.n, self._len_cap)
+
+    def run(self, x0):
+        """x0 [B, h]: the prompt pass's last hidden row of every sequence (pre final norm).  The first iteration runs the step's tail on
+        them, placed in rows (b, 0) with no drafts and without a decoder step; then up to max_new_tokens steps.  Returns (ids, pred_z) as
+        GreedyLoopGraph.run does."""
+        B, n = self.cache.batch, self.n
+        x = torch.zeros_like(self.x_in)
+        x[0::n] = x0
+        self._tail(x, count_step=False)
+        self._poll_loop(self.max_new_tokens)
+        st, n_steps, acc, lens = self.state.cpu(), self.n_steps.tolist(), self.acc.cpu(), self.cache.len_dev.tolist()
+        if not bool(st[3].all()):                               # pragma: no cover - max_new_tokens steps finish every sequence by construction
+            raise RuntimeError(f"speculative greedy loop: sequences still live after {self.steps} steps (state {st.tolist()})")
+        self.cache.lengths = [m - 1 for m in lens]
+        self.acc_log = [acc[b, :n_steps[b]].tolist() for b in range(B)]
+        self.emitted = st[2].tolist()
+        n_tok, n_z = st[4].tolist(), st[5].tolist()
+        return [self.tok_log[b, :n_tok[b]].clone() for b in range(B)], [self.z_log[b, :n_z[b]].clone() for b in range(B)]
 
 
 BEAM_STATE = ("running", "fin_score", "fin_flag", "fin_end", "scal", "live", "tok", "parent", "tok_log", "parent_log", "own_block")

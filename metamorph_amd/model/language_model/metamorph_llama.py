@@ -38,6 +38,7 @@ from ..metamorph_arch import MetaMorphMetaForCausalLM, MetaMorphMetaModel, uploa
 from ..modules import HipEmbedding, HipGELU, HipLinear, HipRMSNorm
 
 BF16 = torch.bfloat16
+MM355_SPEC_MAX_DRAFT = F.SPEC_MAX_DRAFT                      # greedy_decode(prompt_lookup_num_tokens=K): K <= 15 guessed tokens per step
 
 
 class MetaMorphConfig(LlamaConfig):
@@ -551,7 +552,8 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
                       end_image_token_id=DEFAULT_IMAGE_END_ID, eos_token_id=(128001, 128009), do_sample=None,
                       temperature=None, top_p=None, num_beams=None, max_new_tokens=1024, use_cache=None, output_image=False,
                       top_k=None, seed=None, stream_ids=None, num_return_sequences=None, repetition_penalty=None, min_new_tokens=None,
-                      suppress_tokens=None, output_logprobs=False, repetition_penalty_ids=None, shared_prefix_rows=None):
+                      suppress_tokens=None, output_logprobs=False, repetition_penalty_ids=None, shared_prefix_rows=None,
+                      prompt_lookup_num_tokens=None, max_matching_ngram_size=None, prompt_lookup_ids=None):
         """Token mode / continuous 'image mode' greedy loop.  use_cache=False re-runs the prefix every step exactly like
         the reference (which forces use_cache=False, O(L^2)); the default keeps a KV cache and feeds one row per step
         through the decode-shape kernels -- same state machine, same outputs.
@@ -599,7 +601,48 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         decoder_extend one sequence after the other and the step is the batch's.  The sampler, the logits processors, log-probabilities,
         quantised weights and the fp8 cache work as without it.  One prompt: the argument is validated and the call is the one without
         it.  Refused by name before any device work: use_cache=False, num_return_sequences > 1, an S that is negative, no integer and not
-        "auto", or above min L_b - 1 (every sequence keeps at least one own row).  None (the default): as without the argument."""
+        "auto", or above min L_b - 1 (every sequence keeps at least one own row).  None (the default): as without the argument.
+        prompt_lookup_num_tokens = K (an integer in [1, MM355_SPEC_MAX_DRAFT = 15]; None / 0: as without the argument): prompt-lookup
+        speculative decoding, HF's option of that name, in the device loop (functional.SpecGreedyLoopGraph).  Every step carries a
+        sequence's next input and up to K ids guessed from its own text through the decoder in one pass over the weights and emits up
+        to K + 1 ids; the guesses are the continuation of the earliest earlier occurrence of the sequence's last max_matching_ngram_size
+        = N ids (1 .. 8; None: 2, HF's default), shorter n-grams tried after longer ones (mm355_ngram_draft_rows: HF's
+        PromptLookupCandidateGenerator).  prompt_lookup_ids is the text looked up in, with what the sequence emits appended: one id list,
+        one list per sequence, or a [B, n] integer tensor read with the attention mask (left-padding entries dropped); it may be empty,
+        and ids outside the vocabulary (the -200 image sentinel) stay in: they match nothing emitted and end a draft.  greedy_decode
+        receives embeddings, hence the ids as an argument of their own; generate() passes its `inputs`.  Every emitted id is the argmax
+        of a row computed on the correct prefix: the ids and image rows are those of the loop without the argument wherever its decision
+        is no near tie (another row count takes another GEMV / GEMM route through the same weights).  The return shapes are the device
+        loop's; one sequence goes through the device loop too.  Works with batches, left padding, the fp8 KV cache and quantised
+        weights.  Refused by name before any device work: K or N out of range or no integer, prompt_lookup_ids with the wrong number of
+        lists, K together with an active sampler, num_return_sequences > 1, a logits processor or output_logprobs, shared_prefix_rows,
+        use_cache=False or num_beams > 1, and a head shape the row kernels do not take (functional.verify_rows_supported)."""
+        spec = self._prompt_lookup_arg(prompt_lookup_num_tokens, max_matching_ngram_size)
+        if spec is not None:
+            B0 = inputs_embeds.shape[0]
+            lookup = self._prompt_lookup_ids(prompt_lookup_ids, attention_mask, B0)
+            copies = self._copies_of(num_return_sequences)
+            V0 = self.w8_lm_head[0].shape[0] if self.w8_lm_head is not None else self.lm_head.weight.shape[0]
+            clash = [what for what, on in (
+                ("an active sampler (do_sample=True and temperature > 0): a draft is verified against the argmax, not against a draw",
+                 bool(do_sample) and temperature is not None and float(temperature) > 0),
+                (f"num_return_sequences={copies}: greedy continuations of one prompt are all the same sequence", copies > 1),
+                ("repetition_penalty / min_new_tokens / suppress_tokens / output_logprobs: the processors see one row per sequence and step",
+                 self._processors_of(repetition_penalty, min_new_tokens, suppress_tokens, output_logprobs, repetition_penalty_ids,
+                                     max_new_tokens, V0, B0) is not None),
+                (f"shared_prefix_rows={shared_prefix_rows!r}: the speculative step attends every sequence's own rows only",
+                 shared_prefix_rows is not None),
+                ("use_cache=False: the drafts are verified against the KV cache (use_cache=True)", not (use_cache is None or use_cache)),
+                (f"num_beams={num_beams}: beam search is not part of the speculative loop", num_beams not in (None, 1)),
+            ) if on]
+            if clash:
+                raise ValueError(f"greedy_decode(prompt_lookup_num_tokens={spec[0]}) does not go with {clash[0]}")
+            _, m0 = self._decode_meta(1)
+            if not F.verify_rows_supported(m0):
+                raise ValueError(f"greedy_decode(prompt_lookup_num_tokens={spec[0]}): no kernel for Hq={m0.Hq} Hkv={m0.Hkv} d={m0.d} "
+                                 "(ops.attn_extend_supported with d % 16 == 0)")
+            return self._greedy_decode_loop(inputs_embeds, attention_mask, start_image_token_id, end_image_token_id, eos_token_id,
+                                            max_new_tokens, output_image, spec=(*spec, lookup))
         copies = self._copies_of(num_return_sequences)
         shared_rows = None
         if shared_prefix_rows is not None:
@@ -923,6 +966,59 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         return n
 
     @staticmethod
+    def _prompt_lookup_arg(prompt_lookup_num_tokens, max_matching_ngram_size):
+        """greedy_decode's prompt_lookup_num_tokens / max_matching_ngram_size -> (K, N), or None for the call without them (K None or 0);
+        anything but integers in [1, MM355_SPEC_MAX_DRAFT] and [1, functional.SPEC_MAX_NGRAM] (N None: 2) is refused by name."""
+        def integer(v):
+            if isinstance(v, (bool, str)):
+                raise TypeError
+            return operator.index(v)
+        try:
+            K = 0 if prompt_lookup_num_tokens is None else integer(prompt_lookup_num_tokens)
+        except TypeError:
+            K = -1
+        if not 0 <= K <= MM355_SPEC_MAX_DRAFT:
+            raise ValueError(f"greedy_decode: prompt_lookup_num_tokens = {prompt_lookup_num_tokens!r} must be an integer in [1, "
+                             f"{MM355_SPEC_MAX_DRAFT}] (None or 0: off): a step carries the next input and that many guessed tokens")
+        try:
+            N = 2 if max_matching_ngram_size is None else integer(max_matching_ngram_size)
+        except TypeError:
+            N = -1
+        if not 1 <= N <= F.SPEC_MAX_NGRAM:
+            raise ValueError(f"greedy_decode: max_matching_ngram_size = {max_matching_ngram_size!r} must be an integer in [1, "
+                             f"{F.SPEC_MAX_NGRAM}] (None: 2)")
+        return (K, N) if K else None
+
+    @staticmethod
+    def _prompt_lookup_ids(prompt_lookup_ids, attention_mask, B):
+        """greedy_decode's prompt_lookup_ids -> one list of ints per sequence: None is B empty lists, one flat list serves every sequence,
+        a [B, n] integer tensor is read with the attention mask (entries under a 0 are dropped); anything else is refused by name."""
+        ids = prompt_lookup_ids
+        if ids is None:
+            return [[] for _ in range(B)]
+        if torch.is_tensor(ids):
+            if ids.dim() != 2 or ids.shape[0] != B or ids.is_floating_point():
+                raise ValueError(f"greedy_decode: prompt_lookup_ids {tuple(ids.shape)} {ids.dtype} must be a [{B}, n] integer tensor")
+            keep = torch.ones_like(ids, dtype=torch.bool) if attention_mask is None else attention_mask.to(torch.bool)
+            if tuple(keep.shape) != tuple(ids.shape):
+                raise ValueError(f"greedy_decode: prompt_lookup_ids {tuple(ids.shape)} does not match the attention mask {tuple(keep.shape)}")
+            ids = [[t for t, k in zip(row, m) if k] for row, m in zip(ids.cpu().tolist(), keep.cpu().tolist())]
+        try:
+            lists = list(ids)
+            if not (lists and isinstance(lists[0], (list, tuple))):
+                lists = [lists] * B
+            lists = [[operator.index(t) for t in row] for row in lists]
+        except TypeError:
+            raise ValueError("greedy_decode: prompt_lookup_ids must be a list of integer ids, one such list per sequence or a [B, n] "
+                             "integer tensor") from None
+        if len(lists) != B:
+            raise ValueError(f"greedy_decode: prompt_lookup_ids holds {len(lists)} lists for {B} sequences (one list for all, or one per "
+                             "sequence)")
+        if any(not -2**31 <= t < 2**31 for row in lists for t in row):
+            raise ValueError("greedy_decode: prompt_lookup_ids holds ids that are no int32")
+        return lists
+
+    @staticmethod
     def _shared_prefix_arg(shared_prefix_rows):
         """greedy_decode's shared_prefix_rows -> "auto" or a non-negative int; anything else is refused by name."""
         if isinstance(shared_prefix_rows, str) and shared_prefix_rows == "auto":
@@ -1055,7 +1151,7 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
                     marks=marks)
 
     def _greedy_decode_loop(self, inputs_embeds, attention_mask, start_image_token_id, end_image_token_id, eos_token_id, max_new_tokens,
-                            output_image, sampler=None, copies=1, processors=None, shared_rows=None):
+                            output_image, sampler=None, copies=1, processors=None, shared_rows=None, spec=None):
         """greedy_decode of B sequences: the prompt pass of _prefill_batch (same-length prompts as one batch, ragged ones one after the
         other), then functional.GreedyLoopGraph -- one pass over the weights per step for all sequences, head, argmax and the reference's
         mode state machine on the device.  The host reads the live counter every config.mm355_greedy_poll_steps steps (default 8: at most
@@ -1063,7 +1159,8 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         copies > 1 (one prompt): `copies` continuations of it, the prompt pass of _prefill_shared; sampler=None then walks the greedy loop
         `copies` times over (tests).  processors: _processors_of's dict (its marks one list per prompt: a prompt's list marks every one of
         its continuations); with want_logprobs the log-probabilities are returned last.  shared_rows = S (_shared_prefix_of: B > 1 prompts
-        whose first S stripped rows are the same rows): the prompt pass of _prefill_shared_batch."""
+        whose first S stripped rows are the same rows): the prompt pass of _prefill_shared_batch.  spec = (K, N, lookup ids per sequence):
+        prompt-lookup speculation -- functional.SpecGreedyLoopGraph in place of the loop, K more cache rows, nothing else differs."""
         if inputs_embeds.dtype != BF16:
             raise TypeError(f"inputs_embeds must be bf16, got {inputs_embeds.dtype}")
         dev = inputs_embeds.device
@@ -1072,7 +1169,7 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         F.params_ready(None)
         max_new_tokens = int(max_new_tokens)
         seqs = [inputs_embeds[b, pads[b]:].reshape(n - pads[b], h) for b in range(B)]
-        cache = HipKVCache(capacity=max(x.shape[0] for x in seqs) + max_new_tokens + 2)
+        cache = HipKVCache(capacity=max(x.shape[0] for x in seqs) + max_new_tokens + 2 + (spec[0] if spec else 0))
         if copies > 1:
             if B != 1:
                 raise ValueError(f"{copies} continuations take one prompt, got {B}")
@@ -1091,10 +1188,14 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
             proc = F.LogitsProcessors(processors["repetition_penalty"], processors["min_new_tokens"],
                                       torch.tensor(sup, dtype=torch.int32).to(dev) if sup else None, processors["want_logprobs"],
                                       None if marks is None else [marks[b // copies] for b in range(B * copies)])
-        loop = F.GreedyLoopGraph(self.model.layers, cache.meta, cache.kv, cache.meta.cos, cache.meta.sin, h, dev, self._head_rows_device,
-                                 embed, V, self._vision_head_out, start_image_token_id, end_image_token_id,
-                                 self.get_model().vision_tower.image_token_len, max_new_tokens, set(eos_token_id),
-                                 poll=getattr(self.config, "mm355_greedy_poll_steps", 8), sampler=sampler, processors=proc)
+        loop_args = (self.model.layers, cache.meta, cache.kv, cache.meta.cos, cache.meta.sin, h, dev, self._head_rows_device, embed, V,
+                     self._vision_head_out, start_image_token_id, end_image_token_id, self.get_model().vision_tower.image_token_len,
+                     max_new_tokens, set(eos_token_id))
+        poll = getattr(self.config, "mm355_greedy_poll_steps", 8)
+        if spec:
+            loop = F.SpecGreedyLoopGraph(*loop_args, lookup_ids=spec[2], num_draft=spec[0], max_ngram=spec[1], poll=poll)
+        else:
+            loop = F.GreedyLoopGraph(*loop_args, poll=poll, sampler=sampler, processors=proc)
         self._greedy_loop = loop                              # (tools / tests: steps, host_reads, the static logits of the last step)
         ids, embs, *logp = loop.run(x0)
         if B == 1 and copies == 1:                            # one sequence: the return shapes of _greedy_decode_cached
@@ -1419,6 +1520,18 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
             raise ValueError(f"generate(shared_prefix_rows={kwargs['shared_prefix_rows']!r}) runs in greedy_decode's device loop: not with "
                              + ("device_beam_search=True (the beams of one prompt share its rows already)" if device_beam_search else
                                 "use_customize_greedy=False (HF's generate path drives forward() and knows no shared prefix)"))
+        if use_customize_greedy or device_beam_search:
+            # prompt-lookup speculation is a route of greedy_decode's device loop, which looks the drafts up in `inputs`; with
+            # use_customize_greedy=False the arguments go on to HF untouched, which has the option itself
+            if self._prompt_lookup_arg(kwargs.get("prompt_lookup_num_tokens"), kwargs.get("max_matching_ngram_size")) is None:
+                for name in ("prompt_lookup_num_tokens", "max_matching_ngram_size", "prompt_lookup_ids"):
+                    kwargs.pop(name, None)                       # (None / 0 is the call without the arguments)
+            elif device_beam_search:
+                raise ValueError(f"generate(prompt_lookup_num_tokens={kwargs['prompt_lookup_num_tokens']!r}) runs in greedy_decode's device "
+                                 "loop: not with device_beam_search=True (a draft is verified against the argmax, not against a beam)")
+            elif kwargs.get("prompt_lookup_ids") is None and inputs is not None:
+                # (read here, with the mask of the ids: the prompt's rows, and with them the mask, grow where an image is spliced in)
+                kwargs["prompt_lookup_ids"] = self._prompt_lookup_ids(inputs, attention_mask, inputs.shape[0])
         if images is not None or image_embeds is not None:
             (_, position_ids, attention_mask, _, inputs_embeds, _, _, _) = self.prepare_inputs_labels_for_multimodal(
                 inputs, position_ids, attention_mask, None, None, images, image_sizes=image_sizes, image_embeds=image_embeds)

@@ -872,6 +872,11 @@ def attn_extend_f8(q, k8, v8, k_scale, v_scale, past, n, max_kv_len, Hq, Hkv, d,
     return _kv_attn_extend(_KV_F8, q, (k8, v8, k_scale, v_scale), past, n, max_kv_len, Hq, Hkv, d, scale, out, workspace)
 
 
+def attn_extend_supported(Hq, Hkv, d):
+    """the head shapes mm355_attn_extend takes (else MM355_EUNSUPPORTED): d % 8 == 0, d <= 128, a GQA group of 1, 2, 4 or 8"""
+    return d % 8 == 0 and d <= 128 and Hq % Hkv == 0 and Hq // Hkv in (1, 2, 4, 8)
+
+
 def attn_extend_ragged_supported(Hq, Hkv, d):
     """the head shapes mm355_attn_extend_ragged takes (else MM355_EUNSUPPORTED): those of mm355_attn_extend"""
     return d % 8 == 0 and d <= 128 and Hq % Hkv == 0 and Hq // Hkv in (1, 2, 4, 8)
@@ -1521,6 +1526,67 @@ def greedy_advance(tok, C, state, live, embed, fed, pred_z, x_in, tok_log, z_log
                                          tok_log.data_ptr(), tok_log.shape[1], z_log.data_ptr(), z_log.shape[1], int(start_id), int(end_id),
                                          int(num_image_tokens), int(max_new_tokens), _lib.ctypes.addressof(arr), len(eos), _stream()),
                f"mm355_greedy_advance B={B} C={C} eos={len(eos)}")
+
+
+# ------------------------------------------------------------------------------------------------ prompt-lookup speculation (csrc/spec.hip)
+
+SPEC_MAX_DRAFT = 15                                          # MM355_SPEC_MAX_DRAFT
+SPEC_MAX_NGRAM = 8                                           # MM355_SPEC_MAX_NGRAM
+
+
+def _i32(*ts):
+    assert all(t.dtype == torch.int32 and t.is_contiguous() for t in ts), [(t.dtype, t.shape) for t in ts]
+
+
+def ngram_draft_rows(hist, hist_len, state, pos, K, N, C, embed, drafts, n_draft, x_in, pos_rows, mask_rows):
+    """The drafts of every sequence and the next step's input rows (mm355_ngram_draft_rows; the model of it is
+    functional.prompt_lookup_host).  hist [B, hist_cap] / hist_len [B] int32: the ids the drafts are looked up in; state: the greedy loop's
+    int32 [6, B] (done and in_image are read); pos [B]: the cache's write positions.  Writes drafts [B, K], n_draft [B], rows b * (K + 1) + 1
+    .. of x_in [B * (K + 1), h] (embed rows of the drafts, zero rows behind them), pos_rows and mask_rows [B * (K + 1)]."""
+    _chk_dev(hist, hist_len, state, pos, embed, drafts, n_draft, x_in, pos_rows, mask_rows)
+    B, n = hist.shape[0], int(K) + 1
+    _i32(hist, hist_len, state, pos, drafts, n_draft, pos_rows, mask_rows)
+    assert hist.dim() == 2 and tuple(state.shape) == (6, B) and hist_len.numel() == B and pos.numel() == B and n_draft.numel() == B
+    assert tuple(drafts.shape) == (B, K) and pos_rows.numel() == B * n and mask_rows.numel() == B * n
+    pe, rows, h, lde = _rows2d(embed)
+    px, Rx, hx, ldx = _rows2d(x_in)
+    assert (Rx, hx) == (B * n, h) and embed.dtype == BF16 and x_in.dtype == BF16
+    _lib.check(_L().mm355_ngram_draft_rows(hist.data_ptr(), hist.shape[1], hist_len.data_ptr(), state[3].data_ptr(), state[0].data_ptr(),
+                                           pos.data_ptr(), B, int(K), int(N), int(C), pe, lde, rows, drafts.data_ptr(), n_draft.data_ptr(), px, ldx,
+                                           h, pos_rows.data_ptr(), mask_rows.data_ptr(), _stream()),
+               f"mm355_ngram_draft_rows B={B} K={K} N={N} C={C}")
+
+
+def spec_verify_advance(tok, drafts, n_draft, C, state, live, embed, fed, pred_z, x_in, tok_log, z_log, hist, hist_len, pos, length, acc_log,
+                        n_steps, start_id, end_id, num_image_tokens, max_new_tokens, eos_ids, count_step=True):
+    """greedy_advance over the n = K + 1 rows of every sequence for as long as its drafts hold (mm355_spec_verify_advance; the model of it is
+    functional.spec_advance_host).  tok [B * n]: the argmax of every row; drafts [B, K] / n_draft [B] as ngram_draft_rows wrote them; fed
+    [B * n, h] / pred_z [B * n, Dz]; state, live, embed, tok_log, z_log as greedy_advance takes them; hist / hist_len receive the logged ids;
+    pos / length: the cache's pos_dev / len_dev, advanced by the iterations run; acc_log [B, cap] / n_steps [B] log that count per step.
+    count_step=False: the first iteration on the prompt's last row -- pos, length, acc_log and n_steps are left alone.  Writes row b * n of
+    x_in [B * n, h]."""
+    _chk_dev(tok, drafts, n_draft, state, live, embed, fed, pred_z, x_in, tok_log, z_log, hist, hist_len, pos, length, acc_log, n_steps)
+    B, K = drafts.shape
+    n = K + 1
+    _i32(tok, drafts, n_draft, state, live, tok_log, hist, hist_len, pos, length, acc_log, n_steps)
+    assert tok.numel() == B * n and tuple(state.shape) == (6, B) and z_log.is_contiguous() and z_log.dtype == BF16
+    pe, rows, h, lde = _rows2d(embed)
+    pf, _, _, ldf = _rows2d(fed)
+    pz, _, Dz, ldz = _rows2d(pred_z)
+    px, _, _, ldx = _rows2d(x_in)
+    assert fed.shape == x_in.shape == (B * n, h) and pred_z.shape[0] == B * n and tok_log.shape[0] == B and z_log.shape[0] == B
+    assert z_log.shape[2] == Dz and hist.shape[0] == B and acc_log.shape[0] == B and n_draft.numel() == hist_len.numel() == B
+    assert pos.numel() == length.numel() == n_steps.numel() == B
+    eos = [int(e) for e in eos_ids]
+    arr = (_lib.ctypes.c_int32 * max(len(eos), 1))(*eos)
+    s = [state[i].data_ptr() for i in range(6)]
+    _lib.check(_L().mm355_spec_verify_advance(tok.data_ptr(), drafts.data_ptr(), n_draft.data_ptr(), B, K, int(C), *s, live.data_ptr(), pe, lde,
+                                              rows, pf, ldf, pz, ldz, px, ldx, h, Dz, tok_log.data_ptr(), tok_log.shape[1], z_log.data_ptr(),
+                                              z_log.shape[1], hist.data_ptr(), hist.shape[1], hist_len.data_ptr(), pos.data_ptr(),
+                                              length.data_ptr(), acc_log.data_ptr(), acc_log.shape[1], n_steps.data_ptr(), int(bool(count_step)),
+                                              int(start_id), int(end_id), int(num_image_tokens), int(max_new_tokens),
+                                              _lib.ctypes.addressof(arr), len(eos), _stream()),
+               f"mm355_spec_verify_advance B={B} K={K} C={C} eos={len(eos)}")
 
 
 # ------------------------------------------------------------------------------------------------ beam search in the device loop (csrc/beam.hip)
