@@ -1807,6 +1807,20 @@ def greedy_advance_host(state, tok, start_id, end_id, num_image_tokens, max_new_
     return ("z", "fed") if image_row else ("tok", "embed")
 
 
+def greedy_host_loop(head, feed, start_id, end_id, num_image_tokens, max_new_tokens, eos_ids):
+    """The reference's greedy loop (metamorph_llama.py:502-597) of ONE sequence, token loop on the host: greedy_advance_host per iteration.
+    head(in_image) -> (tok, fed_row, pred_z): the argmax id of the current row's logits, the row the lm_head saw, the image head's row;
+    feed(tok, row): the next input, `row` the fed row after an image row, None for embed_tokens[tok].  Returns (ids, pred_z rows) as logged."""
+    state, eos, logs = dict.fromkeys(GREEDY_STATE, 0), set(eos_ids), {"tok": [], "z": []}
+    while True:
+        tok, fed_row, pred_z = head(bool(state["in_image"]))
+        log, next_row = greedy_advance_host(state, tok, start_id, end_id, num_image_tokens, max_new_tokens, eos)
+        logs[log].append(tok if log == "tok" else pred_z)      # (no log caps: every iteration of a live sequence logs)
+        if state["done"]:
+            return logs["tok"], logs["z"]
+        feed(tok, fed_row if next_row == "fed" else None)
+
+
 BEAM_MAX = 8                                                 # MM355_BEAM_MAX
 BEAM_EARLY_STOPPING = {False: 0, True: 1, "never": 2}        # mm355_beam_advance's early_stopping
 
@@ -2119,7 +2133,57 @@ class LogitsProcessors:
         return self.edits or bool(self.want_logprobs)
 
 
-class GreedyLoopGraph(_CapturedStep):
+def _refuse_loop_args(n_eos, C, embed, poll, an_id="an argmax id", beams=None):
+    """what every device token loop refuses before it allocates anything, in this order (`beams`: the beam loop's count of them)"""
+    if n_eos > ops.GREEDY_MAX_EOS:
+        raise ValueError(f"{n_eos} eos ids: the device loop takes up to {ops.GREEDY_MAX_EOS}")
+    if beams is not None and not 1 <= beams <= BEAM_MAX:
+        raise ValueError(f"{beams} beams: the device beam loop takes 1 .. {BEAM_MAX}")
+    if C > embed.shape[0]:
+        raise ValueError(f"{C} logits over an embedding of {embed.shape[0]} rows: {an_id} would be no row of it")
+    if int(poll) < 1:
+        raise ValueError(f"mm355_greedy_poll_steps = {poll}: the live counter is read every poll >= 1 steps")
+
+
+class _GreedyLoopBase(_CapturedStep):
+    """What the greedy device loops share: the refusals, the scalars, the static buffers of a step of `rows` rows per sequence (`x_in`,
+    `logits`, `tok`), `state` (GREEDY_STATE) and `live`, the logs `tok_log` / `z_log` of max_new_tokens + 1 iterations, `steps` / `host_reads`
+    and the read-out after the last step.  A subclass supplies _tail and, allocated between `tok` and the logs, what its pick needs."""
+
+    def __init__(self, layers, meta, cache, cos, sin, h, device, head, embed, C, Dz, start_id, end_id, num_image_tokens, max_new_tokens,
+                 eos_ids, poll, rows=1):
+        _refuse_loop_args(len(eos_ids), C, embed, poll)
+        super().__init__(layers, meta, cache, cos, sin)
+        B, R = cache.batch, cache.batch * rows
+        self.head, self.embed, self.C, self.max_new_tokens, self.poll = head, embed, int(C), int(max_new_tokens), int(poll)
+        self.scalars = (int(start_id), int(end_id), int(num_image_tokens), self.max_new_tokens, sorted(int(e) for e in eos_ids))
+        cap = self.max_new_tokens + 1                        # iterations of the loop: total_out > max_new_tokens ends it
+        self.x_in = torch.zeros((R, h), device=device, dtype=BF16)
+        self.state = torch.zeros((len(GREEDY_STATE), B), device=device, dtype=torch.int32)
+        self.live = torch.full((1,), B, device=device, dtype=torch.int32)
+        self.logits = torch.empty((R, self.C), device=device, dtype=torch.float32)
+        self.tok = torch.zeros(R, device=device, dtype=torch.int32)
+        self._alloc_pick(R, device)
+        self.tok_log = torch.zeros((B, cap), device=device, dtype=torch.int32)
+        self.z_log = torch.zeros((B, cap, Dz), device=device, dtype=BF16)
+        self.host_reads, self.steps = 0, 0
+
+    def _alloc_pick(self, R, device):
+        self.arg_ws = ops.argmax_rows_ws(R, self.C, device)
+
+    def _quiet(self):
+        return self.state[3], 1                              # with every sequence done the kernels log, feed and write no state
+
+    def _results(self):
+        """(state on the host, per sequence its int32 ids, per sequence its [n_b, Dz] bf16 image rows) once every sequence is done"""
+        st = self.state.cpu()
+        if not bool(st[3].all()):                               # pragma: no cover - max_new_tokens steps finish every sequence by construction
+            raise RuntimeError(f"{self.label} loop: sequences still live after {self.steps} steps (state {st.tolist()})")
+        n_tok, n_z = st[4].tolist(), st[5].tolist()
+        return st, [self.tok_log[b, :n].clone() for b, n in enumerate(n_tok)], [self.z_log[b, :n].clone() for b, n in enumerate(n_z)]
+
+
+class GreedyLoopGraph(_GreedyLoopBase):
     """The greedy text-and-image loop (reference metamorph_llama.py:502-597) of a batch with the token loop on the device.  One step is
     decoder_decode_row (all rows, whatever route the batch size takes) -> `head` (the model's final norm, image head for ALL rows, row select
     by the device-resident mode, lm_head into the static fp32 `logits`) -> mm355_argmax_rows_f32 -> mm355_greedy_advance, which runs the
@@ -2145,42 +2209,23 @@ class GreedyLoopGraph(_CapturedStep):
 
     def __init__(self, layers, meta, cache, cos, sin, h, device, head, embed, C, Dz, start_id, end_id, num_image_tokens, max_new_tokens,
                  eos_ids, poll=8, sampler=None, processors=None):
-        if len(eos_ids) > ops.GREEDY_MAX_EOS:
-            raise ValueError(f"{len(eos_ids)} eos ids: the device loop takes up to {ops.GREEDY_MAX_EOS}")
-        if C > embed.shape[0]:
-            raise ValueError(f"{C} logits over an embedding of {embed.shape[0]} rows: an argmax id would be no row of it")
-        if int(poll) < 1:
-            raise ValueError(f"mm355_greedy_poll_steps = {poll}: the live counter is read every poll >= 1 steps")
-        super().__init__(layers, meta, cache, cos, sin)
-        B = cache.batch
-        self.head, self.embed, self.C = head, embed, int(C)
-        self.max_new_tokens, self.poll = int(max_new_tokens), int(poll)
-        self.scalars = (int(start_id), int(end_id), int(num_image_tokens), self.max_new_tokens, sorted(int(e) for e in eos_ids))
-        cap = self.max_new_tokens + 1                        # iterations of the loop: total_out > max_new_tokens ends it
-        self.x_in = torch.zeros((B, h), device=device, dtype=BF16)
-        self.state = torch.zeros((len(GREEDY_STATE), B), device=device, dtype=torch.int32)
-        self.live = torch.full((1,), B, device=device, dtype=torch.int32)
-        self.logits = torch.empty((B, self.C), device=device, dtype=torch.float32)
-        self.tok = torch.zeros(B, device=device, dtype=torch.int32)
-        self.sampler, self.seed = None, None
-        if sampler is None:
-            self.arg_ws = ops.argmax_rows_ws(B, self.C, device)
-        else:
-            inv_t, top_k, top_p, seed, stream_ids = sampler
-            if len(stream_ids) != B:
-                raise ValueError(f"{len(stream_ids)} stream ids for {B} sequences")
-            self.sampler = (float(inv_t), int(top_k), float(top_p))
-            self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-            self.stream_ids = torch.tensor([int(i) for i in stream_ids], dtype=torch.int32).to(device)
-            self.u = torch.zeros(B, device=device, dtype=torch.float32)
-            self.smp_ws = ops.sample_rows_ws(B, self.C, device)
-        self.tok_log = torch.zeros((B, cap), device=device, dtype=torch.int32)
-        self.z_log = torch.zeros((B, cap, Dz), device=device, dtype=BF16)
+        self.sampler, self.seed, self._draw = None, None, sampler
+        super().__init__(layers, meta, cache, cos, sin, h, device, head, embed, C, Dz, start_id, end_id, num_image_tokens, max_new_tokens,
+                         eos_ids, poll)
         self.processors = processors if processors is not None and processors.active else None
         if self.processors is not None:
-            self._init_processors(B, cap, device)
-        self.host_reads = 0
-        self.steps = 0
+            self._init_processors(cache.batch, self.max_new_tokens + 1, device)
+
+    def _alloc_pick(self, B, device):
+        if self._draw is None:
+            return super()._alloc_pick(B, device)
+        inv_t, top_k, top_p, seed, stream_ids = self._draw
+        if len(stream_ids) != B:
+            raise ValueError(f"{len(stream_ids)} stream ids for {B} sequences")
+        self.sampler, self.seed = (float(inv_t), int(top_k), float(top_p)), int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.stream_ids = torch.tensor([int(i) for i in stream_ids], dtype=torch.int32).to(device)
+        self.u = torch.zeros(B, device=device, dtype=torch.float32)
+        self.smp_ws = ops.sample_rows_ws(B, self.C, device)
 
     def _init_processors(self, B, cap, device):
         p = self.processors
@@ -2226,23 +2271,16 @@ class GreedyLoopGraph(_CapturedStep):
         ops.greedy_advance(self.tok, self.C, self.state, self.live, self.embed, fed, pred_z, self.x_in, self.tok_log, self.z_log,
                            *self.scalars)
 
-    def _quiet(self):
-        return self.state[3], 1                              # with every sequence done the warm-up logs and feeds nothing
-
     def run(self, x0):
         """x0 [B, h]: the prompt pass's last hidden row of every sequence (pre final norm).  The first iteration's head and advance run on
         it without a decoder step; then up to max_new_tokens steps.  Returns (ids, pred_z): per sequence its int32 ids and its [n_b, Dz]
         bf16 image rows; with processors.want_logprobs (ids, pred_z, logprobs): per sequence the fp32 log-probabilities of its ids."""
         self._tail(x0.contiguous())
         self._poll_loop(self.max_new_tokens)
-        st = self.state.cpu()
-        if not bool(st[3].all()):                               # pragma: no cover - max_new_tokens steps finish every sequence by construction
-            raise RuntimeError(f"greedy loop: sequences still live after {self.steps} steps (state {st.tolist()})")
-        n_tok, n_z = st[4].tolist(), st[5].tolist()
-        out = ([self.tok_log[b, :n_tok[b]].clone() for b in range(len(n_tok))], [self.z_log[b, :n_z[b]].clone() for b in range(len(n_z))])
+        st, *out = self._results()
         if self.processors is not None and self.processors.want_logprobs:
-            out += ([self.logp_log[b, :n_tok[b]].clone() for b in range(len(n_tok))],)
-        return out
+            out.append([self.logp_log[b, :n].clone() for b, n in enumerate(st[4].tolist())])
+        return tuple(out)
 
 
 SPEC_MAX_DRAFT, SPEC_MAX_NGRAM = ops.SPEC_MAX_DRAFT, ops.SPEC_MAX_NGRAM      # MM355_SPEC_MAX_DRAFT, MM355_SPEC_MAX_NGRAM
@@ -2291,7 +2329,7 @@ def spec_advance_host(state, toks, drafts, start_id, end_id, num_image_tokens, m
     return out
 
 
-class SpecGreedyLoopGraph(_CapturedStep):
+class SpecGreedyLoopGraph(_GreedyLoopBase):
     """GreedyLoopGraph with prompt-lookup speculation (HF's prompt_lookup_num_tokens; no second model): a step carries n = K + 1 rows per
     sequence -- its real next input and up to K ids guessed from its own text -- and emits up to n ids.  One step is decoder_verify_rows
     (B * n rows, one pass over the weights) -> `head` on all rows with the per-row mode mask -> mm355_argmax_rows_f32 over B * n rows ->
@@ -2313,12 +2351,7 @@ class SpecGreedyLoopGraph(_CapturedStep):
         K, N = int(num_draft), int(max_ngram)
         if not 1 <= K <= SPEC_MAX_DRAFT or not 1 <= N <= SPEC_MAX_NGRAM:
             raise ValueError(f"speculative loop: {K} drafts (1 .. {SPEC_MAX_DRAFT}) from n-grams of up to {N} ids (1 .. {SPEC_MAX_NGRAM})")
-        if len(eos_ids) > ops.GREEDY_MAX_EOS:
-            raise ValueError(f"{len(eos_ids)} eos ids: the device loop takes up to {ops.GREEDY_MAX_EOS}")
-        if C > embed.shape[0]:
-            raise ValueError(f"{C} logits over an embedding of {embed.shape[0]} rows: an argmax id would be no row of it")
-        if int(poll) < 1:
-            raise ValueError(f"mm355_greedy_poll_steps = {poll}: the live counter is read every poll >= 1 steps")
+        _refuse_loop_args(len(eos_ids), C, embed, poll)       # (the shared refusals come before the loop's own)
         B = cache.batch
         if len(lookup_ids) != B:
             raise ValueError(f"{len(lookup_ids)} lists of lookup ids for {B} sequences")
@@ -2326,22 +2359,11 @@ class SpecGreedyLoopGraph(_CapturedStep):
             raise ValueError(f"speculative loop: no kernel for Hq={meta.Hq} Hkv={meta.Hkv} d={meta.d} (ops.attn_extend_supported, d % 16 == 0)")
         if meta.cos is not cos or meta.sin is not sin:
             raise ValueError("speculative loop: meta.cos / meta.sin must be the RoPE tables cos / sin (decoder_verify_rows reads them from meta)")
-        super().__init__(layers, meta, cache, cos, sin)
-        self.head, self.embed, self.C = head, embed, int(C)
+        super().__init__(layers, meta, cache, cos, sin, h, device, head, embed, C, Dz, start_id, end_id, num_image_tokens, max_new_tokens,
+                         eos_ids, poll, rows=K + 1)
         self.K, self.N, self.n = K, N, K + 1
-        n, R = self.n, B * (K + 1)
-        self.max_new_tokens, self.poll = int(max_new_tokens), int(poll)
-        self.scalars = (int(start_id), int(end_id), int(num_image_tokens), self.max_new_tokens, sorted(int(e) for e in eos_ids))
-        cap = self.max_new_tokens + 1                        # iterations of the loop: total_out > max_new_tokens ends it
+        n, R, cap = self.n, B * (K + 1), self.max_new_tokens + 1
         i32 = dict(device=device, dtype=torch.int32)
-        self.x_in = torch.zeros((R, h), device=device, dtype=BF16)
-        self.state = torch.zeros((len(GREEDY_STATE), B), **i32)
-        self.live = torch.full((1,), B, **i32)
-        self.logits = torch.empty((R, self.C), device=device, dtype=torch.float32)
-        self.tok = torch.zeros(R, **i32)
-        self.arg_ws = ops.argmax_rows_ws(R, self.C, device)
-        self.tok_log = torch.zeros((B, cap), **i32)
-        self.z_log = torch.zeros((B, cap, Dz), device=device, dtype=BF16)
         look = [[int(t) for t in ids] for ids in lookup_ids]
         hist = np.zeros((B, max(len(ids) for ids in look) + cap), dtype=np.int32)
         for b, ids in enumerate(look):
@@ -2358,8 +2380,6 @@ class SpecGreedyLoopGraph(_CapturedStep):
         self.prompt_lengths = list(cache.lengths)
         self._len_cap = max(cache.lengths) + cap             # no sequence grows beyond it: it is done after `cap` iterations
         self._upper = max(cache.lengths)                     # upper bound of the device-resident lengths
-        self.host_reads = 0
-        self.steps = 0
         self.emitted, self.acc_log = None, None
 
     def _launches(self, bound=None):
@@ -2376,9 +2396,6 @@ class SpecGreedyLoopGraph(_CapturedStep):
                                 *self.scalars, count_step=count_step)
         ops.ngram_draft_rows(self.hist, self.hist_len, self.state, cache.pos_dev, self.K, self.N, self.C, self.embed, self.drafts,
                              self.n_draft, self.x_in, self.pos_rows, self.mask_rows)
-
-    def _quiet(self):
-        return self.state[3], 1                              # with every sequence done the kernels write no state (pos_rows: what it was)
 
     def _captured(self):
         """the one (graph, output), captured at the first step -- the device lengths still equal the host's then, which _capture restores
@@ -2407,14 +2424,11 @@ class SpecGreedyLoopGraph(_CapturedStep):
         x[0::n] = x0
         self._tail(x, count_step=False)
         self._poll_loop(self.max_new_tokens)
-        st, n_steps, acc, lens = self.state.cpu(), self.n_steps.tolist(), self.acc.cpu(), self.cache.len_dev.tolist()
-        if not bool(st[3].all()):                               # pragma: no cover - max_new_tokens steps finish every sequence by construction
-            raise RuntimeError(f"speculative greedy loop: sequences still live after {self.steps} steps (state {st.tolist()})")
-        self.cache.lengths = [m - 1 for m in lens]
-        self.acc_log = [acc[b, :n_steps[b]].tolist() for b in range(B)]
-        self.emitted = st[2].tolist()
-        n_tok, n_z = st[4].tolist(), st[5].tolist()
-        return [self.tok_log[b, :n_tok[b]].clone() for b in range(B)], [self.z_log[b, :n_z[b]].clone() for b in range(B)]
+        st, ids, pred_z = self._results()
+        n_steps, acc = self.n_steps.tolist(), self.acc.cpu()
+        self.cache.lengths = [m - 1 for m in self.cache.len_dev.tolist()]
+        self.emitted, self.acc_log = st[2].tolist(), [acc[b, :n_steps[b]].tolist() for b in range(B)]
+        return ids, pred_z
 
 
 BEAM_STATE = ("running", "fin_score", "fin_flag", "fin_end", "scal", "live", "tok", "parent", "tok_log", "parent_log", "own_block")
@@ -2437,15 +2451,8 @@ class BeamLoopGraph(_CapturedStep):
     def __init__(self, layers, meta, cache, cos, sin, h, device, head, embed, C, max_new_tokens, eos_ids, length_penalty=1.0,
                  early_stopping=False, poll=8):
         eos = sorted(set(int(e) for e in eos_ids))
-        if len(eos) > ops.GREEDY_MAX_EOS:
-            raise ValueError(f"{len(eos)} eos ids: the device loop takes up to {ops.GREEDY_MAX_EOS}")
         K = cache.batch
-        if not 1 <= K <= BEAM_MAX:
-            raise ValueError(f"{K} beams: the device beam loop takes 1 .. {BEAM_MAX}")
-        if C > embed.shape[0]:
-            raise ValueError(f"{C} logits over an embedding of {embed.shape[0]} rows: a candidate id would be no row of it")
-        if int(poll) < 1:
-            raise ValueError(f"mm355_greedy_poll_steps = {poll}: the live counter is read every poll >= 1 steps")
+        _refuse_loop_args(len(eos), C, embed, poll, an_id="a candidate id", beams=K)
         if early_stopping not in BEAM_EARLY_STOPPING or (isinstance(early_stopping, (int, float)) and not isinstance(early_stopping, bool)):
             raise ValueError(f"early_stopping = {early_stopping!r}: one of False, True, 'never'")
         self.max_new_tokens, self.poll, self.C = int(max_new_tokens), int(poll), int(C)

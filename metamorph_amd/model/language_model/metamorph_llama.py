@@ -617,22 +617,22 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         weights.  Refused by name before any device work: K or N out of range or no integer, prompt_lookup_ids with the wrong number of
         lists, K together with an active sampler, num_return_sequences > 1, a logits processor or output_logprobs, shared_prefix_rows,
         use_cache=False or num_beams > 1, and a head shape the row kernels do not take (functional.verify_rows_supported)."""
+        cached = use_cache is None or use_cache
         spec = self._prompt_lookup_arg(prompt_lookup_num_tokens, max_matching_ngram_size)
         if spec is not None:
             B0 = inputs_embeds.shape[0]
             lookup = self._prompt_lookup_ids(prompt_lookup_ids, attention_mask, B0)
             copies = self._copies_of(num_return_sequences)
-            V0 = self.w8_lm_head[0].shape[0] if self.w8_lm_head is not None else self.lm_head.weight.shape[0]
             clash = [what for what, on in (
                 ("an active sampler (do_sample=True and temperature > 0): a draft is verified against the argmax, not against a draw",
                  bool(do_sample) and temperature is not None and float(temperature) > 0),
                 (f"num_return_sequences={copies}: greedy continuations of one prompt are all the same sequence", copies > 1),
                 ("repetition_penalty / min_new_tokens / suppress_tokens / output_logprobs: the processors see one row per sequence and step",
                  self._processors_of(repetition_penalty, min_new_tokens, suppress_tokens, output_logprobs, repetition_penalty_ids,
-                                     max_new_tokens, V0, B0) is not None),
+                                     max_new_tokens, self._vocab_rows, B0) is not None),
                 (f"shared_prefix_rows={shared_prefix_rows!r}: the speculative step attends every sequence's own rows only",
                  shared_prefix_rows is not None),
-                ("use_cache=False: the drafts are verified against the KV cache (use_cache=True)", not (use_cache is None or use_cache)),
+                ("use_cache=False: the drafts are verified against the KV cache (use_cache=True)", not cached),
                 (f"num_beams={num_beams}: beam search is not part of the speculative loop", num_beams not in (None, 1)),
             ) if on]
             if clash:
@@ -647,7 +647,7 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         shared_rows = None
         if shared_prefix_rows is not None:
             want = self._shared_prefix_arg(shared_prefix_rows)
-            if not (use_cache is None or use_cache):
+            if not cached:
                 raise ValueError(f"greedy_decode(shared_prefix_rows={shared_prefix_rows!r}, use_cache=False): the sequences share the prefix's "
                                  "KV cache rows (use_cache=True)")
             if copies > 1:
@@ -655,14 +655,13 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
                                  "several prompts over one prefix are not built; repeat the prompts instead")
             B0, n0 = inputs_embeds.shape[:2]
             shared_rows = self._shared_prefix_of(want, inputs_embeds, self._left_pads(attention_mask, B0, n0))
-        V = self.w8_lm_head[0].shape[0] if self.w8_lm_head is not None else self.lm_head.weight.shape[0]
         processors = self._processors_of(repetition_penalty, min_new_tokens, suppress_tokens, output_logprobs, repetition_penalty_ids,
-                                         max_new_tokens, V, inputs_embeds.shape[0])
-        if processors is not None and not (use_cache is None or use_cache):
+                                         max_new_tokens, self._vocab_rows, inputs_embeds.shape[0])
+        if processors is not None and not cached:
             raise NotImplementedError("greedy_decode(repetition_penalty / min_new_tokens / suppress_tokens / output_logprobs, use_cache=False): "
                                       "the logits processors run in the device loop on the KV cache (use_cache=True)")
         if copies > 1:
-            if not (use_cache is None or use_cache):
+            if not cached:
                 raise ValueError(f"greedy_decode(num_return_sequences={copies}, use_cache=False): the continuations share the prompt's KV "
                                  "cache rows (use_cache=True)")
             if inputs_embeds.shape[0] != 1:
@@ -674,10 +673,10 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
             return self._greedy_decode_loop(inputs_embeds, attention_mask, start_image_token_id, end_image_token_id, eos_token_id,
                                             max_new_tokens, output_image, sampler=sampler, copies=copies, processors=processors)
         sampler = self._sampler_of(do_sample, temperature, top_k, top_p, num_beams, seed, stream_ids, inputs_embeds.shape[0])
-        if sampler is not None and not (use_cache is None or use_cache):
+        if sampler is not None and not cached:
             raise NotImplementedError("greedy_decode(do_sample=True, use_cache=False): sampling runs in the device loop on the KV cache "
                                       "(use_cache=True)")
-        if use_cache is None or use_cache:
+        if cached:
             if inputs_embeds.shape[0] != 1 or F.VARIANTS["greedy_loop_b1"] or sampler is not None or processors is not None:
                 return self._greedy_decode_loop(inputs_embeds, attention_mask, start_image_token_id, end_image_token_id, eos_token_id,
                                                 max_new_tokens, output_image, sampler=sampler, processors=processors, shared_rows=shared_rows)
@@ -686,42 +685,20 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         if inputs_embeds.shape[0] != 1:
             raise NotImplementedError(f"greedy_decode(use_cache=False) handles one sequence (as the reference's loop does), got "
                                       f"{inputs_embeds.shape[0]}; a batch runs on the KV cache (use_cache=True)")
-        in_image_mode = False
-        generated, image_embeds = [], []
-        total_image_tokens = 0
-        total_out = 0
-        num_image_tokens = self.get_model().vision_tower.image_token_len
-        eos = set(eos_token_id)
-        while True:
-            out = self.llm_forward(inputs_embeds=inputs_embeds, attention_mask=None, return_dict=True, decoding=in_image_mode)
-            image_embed = out.loss
-            next_token = int(torch.argmax(out.logits[:, -1, :], dim=-1)[0])
-            next_embed = out.hidden_states[:, -1, :].unsqueeze(0)
-            tok_embed = self.model.embed_tokens(torch.tensor([[next_token]], device=inputs_embeds.device))
-            if (not in_image_mode) and next_token == start_image_token_id:
-                in_image_mode = True
-                generated.append(next_token)
-                inputs_embeds = torch.cat((inputs_embeds, tok_embed), dim=1)
-            elif in_image_mode and total_image_tokens < num_image_tokens:
-                total_image_tokens += 1
-                image_embeds.append(image_embed)
-                inputs_embeds = torch.cat((inputs_embeds, next_embed), dim=1)
-                if total_image_tokens == num_image_tokens:
-                    in_image_mode = False
-            elif next_token == end_image_token_id:
-                in_image_mode = False
-                total_image_tokens = 0
-                generated.append(next_token)
-                inputs_embeds = torch.cat((inputs_embeds, tok_embed), dim=1)
-            else:
-                inputs_embeds = torch.cat((inputs_embeds, tok_embed), dim=1)
-                generated.append(next_token)
-            total_out += 1
-            if next_token in eos or total_out > max_new_tokens:
-                break
-        emb = torch.cat(image_embeds, dim=0) if image_embeds else torch.tensor([], dtype=torch.float32, device=inputs_embeds.device)
-        output = [torch.tensor(generated, dtype=torch.int32, device=inputs_embeds.device)]
-        return (output, emb) if output_image else output
+        dev = inputs_embeds.device
+
+        def head(in_image):                                   # the whole prefix again, as the reference runs it
+            out = self.llm_forward(inputs_embeds=inputs_embeds, attention_mask=None, return_dict=True, decoding=in_image)
+            return int(torch.argmax(out.logits[:, -1, :], dim=-1)[0]), out.hidden_states[:, -1, :].unsqueeze(0), out.loss
+
+        def feed(tok, row):
+            nonlocal inputs_embeds
+            if row is None:
+                row = self.model.embed_tokens(torch.tensor([[tok]], device=dev))
+            inputs_embeds = torch.cat((inputs_embeds, row), dim=1)
+        return self._one_sequence(F.greedy_host_loop(head, feed, start_image_token_id, end_image_token_id,
+                                                     self.get_model().vision_tower.image_token_len, max_new_tokens, eos_token_id),
+                                  dev, output_image)
 
     # ------------------------------------------------------------------ weight-only FP8 decode (reference builder.py:13-25, load_8bit=True)
     w8_format = None                                         # set by quantize_decoder_
@@ -783,16 +760,43 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
                                "were released (save before quantising, or pass keep_bf16=True)")
         return super().state_dict(*args, **kwargs)
 
-    def _lm_head_w8(self, hid):
-        """fp32 logits of the normed rows on the quantised lm_head: up to 16 rows mm355_gemv_w8, more rows mm355_gemm_w8 (one slice, fp32
-        output); beyond its limits (more than 4096 rows, a hidden size that is no multiple of 64) the bf16 GEMM on the dequantised weight, a
-        temporary of the lm_head's size."""
-        q, scale = self.w8_lm_head
-        if hid.shape[0] <= 16:
-            return ops.gemv_w8(hid, q, scale, out=torch.empty((hid.shape[0], q.shape[0]), device=hid.device, dtype=torch.float32))
-        if F.VARIANTS["w8_gemm"] and ops.gemm_w8_supported(hid.shape[0], hid.shape[1]):
-            return ops.gemm_w8(hid, q, scale, out_f32=True)
-        return ops.gemm(hid, ops.dequant_w8(q, scale), out_f32=True)
+    # ------------------------------------------------------------------ the heads of cached generation
+    @property
+    def _vocab_rows(self):
+        """the width of the logits: the rows of the lm_head, quantised or not"""
+        return self.w8_lm_head[0].shape[0] if self.w8_lm_head is not None else self.lm_head.weight.shape[0]
+
+    def _lm_head(self, hid, out=None):
+        """fp32 logits of the normed rows `hid` [n, h], into `out` [n, V] if given: the lm_head dispatch of cached generation.  A quantised
+        lm_head: up to 16 rows mm355_gemv_w8, more rows mm355_gemm_w8 (one slice, fp32 output); with VARIANTS["w8_gemm"] off or beyond its
+        limits (more than 4096 rows, a hidden size that is no multiple of 64) the bf16 GEMM on the dequantised weight, a temporary of the
+        lm_head's size.  A bf16 lm_head: up to 32 rows mm355_gemv_bf16 where it takes them (17 .. 32 rows: wide weights only -- the lm_head
+        is one), else the GEMM."""
+        n = hid.shape[0]
+        if out is None:
+            out = torch.empty((n, self._vocab_rows), device=hid.device, dtype=torch.float32)
+        if self.w8_lm_head is not None:
+            q, scale = self.w8_lm_head
+            if n <= 16:
+                return ops.gemv_w8(hid, q, scale, out=out)
+            if F.VARIANTS["w8_gemm"] and ops.gemm_w8_supported(n, hid.shape[1]):
+                return ops.gemm_w8(hid, q, scale, out=out)
+            return ops.gemm(hid, ops.dequant_w8(q, scale), out=out)
+        w = self.lm_head.weight.data
+        if n <= 32 and ops.gemv_supported(hid, w):
+            return ops.gemv(hid, w, out=out)
+        return ops.gemm(hid, w, out=out)
+
+    def _image_head(self, hid):
+        """The image head on the normed rows `hid` [n, h] (reference metamorph_llama.py:363-377): vision_head -> L2 normalisation if
+        normalize_vision -> softmax(. / 0.07) if apply_softmax -> mm_projector.  Returns (pred_z [n, Dz], the projected rows [n, h])."""
+        n = hid.shape[0]
+        pred_z = self.vision_head(hid)
+        if self.normalize_vision:
+            pred_z = ops.bilinear_l2norm(pred_z.view(n, 1, -1).contiguous(), 1, 1, True).view(n, -1)
+        if self.apply_softmax:
+            pred_z = ops.softmax_rows(pred_z.contiguous(), 0.07)
+        return pred_z, self.model.mm_projector(pred_z)
 
     # ------------------------------------------------------------------ cached decode (row N1)
     def _decode_meta(self, L):
@@ -802,23 +806,13 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
 
     @torch.no_grad()
     def _head_row(self, x, in_image_mode):
-        """Final norm + (image mode: vision_head -> normalize -> mm_projector) + fp32 logits of ONE hidden row
-        (reference metamorph_llama.py:363-377, 398-399).  Returns (logits [1,V] f32, row fed back in image mode, pred_z)."""
+        """Final norm + (image mode: _image_head) + fp32 logits of ONE hidden row (reference metamorph_llama.py:363-377, 398-399).
+        Returns (logits [1,V] f32, row fed back in image mode, pred_z)."""
         hid = self.model.norm(x)
         pred_z = None
         if in_image_mode:
-            pred_z = self.vision_head(hid)
-            if self.normalize_vision:
-                pred_z = ops.bilinear_l2norm(pred_z.view(1, 1, -1).contiguous(), 1, 1, True).view(1, -1)
-            if self.apply_softmax:
-                pred_z = ops.softmax_rows(pred_z.contiguous(), 0.07)
-            hid = self.model.mm_projector(pred_z)
-        if self.w8_lm_head is not None:
-            logits = self._lm_head_w8(hid.contiguous())
-        else:
-            logits = ops.gemv(hid.contiguous(), self.lm_head.weight.data, out=torch.empty((1, self.lm_head.weight.shape[0]), device=x.device,
-                                                                                        dtype=torch.float32))
-        return logits, hid, pred_z
+            pred_z, hid = self._image_head(hid)
+        return self._lm_head(hid.contiguous()), hid, pred_z
 
     @torch.no_grad()
     def _kv_cache_format(self, fmt=None):
@@ -865,73 +859,37 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         x = F.decoder_prefill_chunked(inputs_embeds.reshape(L0, h).contiguous(), self.model.layers, meta, cache,
                                       self._prefill_chunk_rows())[-1:].contiguous()
         stepper = F.DecodeStepGraph(self.model.layers, meta, cache, cos, sin, h, dev)
-        in_image_mode = False
-        generated, image_embeds = [], []
-        total_image_tokens = 0
-        total_out = 0
-        eos = set(eos_token_id)
-        while True:
-            logits, fed_back, pred_z = self._head_row(x, in_image_mode)
-            next_token = int(torch.argmax(logits[0], dim=-1))
-            if (not in_image_mode) and next_token == start_image_token_id:
-                in_image_mode = True
-                generated.append(next_token)
-                row = None
-            elif in_image_mode and total_image_tokens < num_image_tokens:
-                total_image_tokens += 1
-                image_embeds.append(pred_z)
-                row = fed_back
-                if total_image_tokens == num_image_tokens:
-                    in_image_mode = False
-            elif next_token == end_image_token_id:
-                in_image_mode = False
-                total_image_tokens = 0
-                generated.append(next_token)
-                row = None
-            else:
-                generated.append(next_token)
-                row = None
-            total_out += 1
-            if next_token in eos or total_out > max_new_tokens:
-                break
+
+        def head(in_image):
+            logits, fed_back, pred_z = self._head_row(x, in_image)
+            return int(torch.argmax(logits[0], dim=-1)), fed_back, pred_z
+
+        def feed(tok, row):
+            nonlocal x
             if row is None:
-                row = self.model.embed_tokens(torch.tensor([[next_token]], device=dev)).view(1, h)
+                row = self.model.embed_tokens(torch.tensor([[tok]], device=dev)).view(1, h)
             x = stepper.step(row)
-        emb = torch.cat(image_embeds, dim=0) if image_embeds else torch.tensor([], dtype=torch.float32, device=dev)
-        output = [torch.tensor(generated, dtype=torch.int32, device=dev)]
+        return self._one_sequence(F.greedy_host_loop(head, feed, start_image_token_id, end_image_token_id, num_image_tokens, max_new_tokens,
+                                                     eos_token_id), dev, output_image)
+
+    @staticmethod
+    def _one_sequence(logged, dev, output_image):
+        """functional.greedy_host_loop's (ids, pred_z rows) in greedy_decode's return shapes for one sequence"""
+        ids, z_rows = logged
+        emb = torch.cat(z_rows, dim=0) if z_rows else torch.tensor([], dtype=torch.float32, device=dev)
+        output = [torch.tensor(ids, dtype=torch.int32, device=dev)]
         return (output, emb) if output_image else output
 
     # ------------------------------------------------------------------ the greedy loop of a batch, token loop on the device
-    def _lm_head_into(self, hid, out):
-        """fp32 logits of the rows `hid` into `out` [n, V]: the dispatch of _rows_logits / _lm_head_w8."""
-        n = hid.shape[0]
-        if self.w8_lm_head is not None:
-            q, scale = self.w8_lm_head
-            if n <= 16:
-                return ops.gemv_w8(hid, q, scale, out=out)
-            if F.VARIANTS["w8_gemm"] and ops.gemm_w8_supported(n, hid.shape[1]):
-                return ops.gemm_w8(hid, q, scale, out=out)
-            return ops.gemm(hid, ops.dequant_w8(q, scale), out=out)
-        w = self.lm_head.weight.data
-        if n <= 32 and ops.gemv_supported(hid, w):
-            return ops.gemv(hid, w, out=out)
-        return ops.gemm(hid, w, out=out)
-
     def _head_rows_device(self, x, in_image, logits_out):
-        """_head_row for every sequence with the mode on the device: final norm, the image head (vision_head -> normalize -> mm_projector,
-        reference :363-377) for ALL rows, mm355_rows_select_bf16 by `in_image` (int32 [B]), fp32 logits into `logits_out`.  The launch
-        sequence does not depend on the modes.  Returns (the rows the lm_head saw, pred_z)."""
-        B = x.shape[0]
+        """_head_row for every sequence with the mode on the device: final norm, _image_head for ALL rows, mm355_rows_select_bf16 by
+        `in_image` (int32 [B]), fp32 logits into `logits_out`.  The launch sequence does not depend on the modes.  Returns (the rows the
+        lm_head saw, pred_z)."""
         hid = self.model.norm(x).contiguous()
-        pred_z = self.vision_head(hid)
-        if self.normalize_vision:
-            pred_z = ops.bilinear_l2norm(pred_z.view(B, 1, -1).contiguous(), 1, 1, True).view(B, -1)
-        if self.apply_softmax:
-            pred_z = ops.softmax_rows(pred_z.contiguous(), 0.07)
-        pred_z = pred_z.contiguous()
-        fed = ops.rows_select(in_image, self.model.mm_projector(pred_z).contiguous(), hid)
-        self._lm_head_into(fed, logits_out)
-        return fed, pred_z
+        pred_z, projected = self._image_head(hid)
+        fed = ops.rows_select(in_image, projected.contiguous(), hid)
+        self._lm_head(fed, logits_out)
+        return fed, pred_z.contiguous()
 
     @staticmethod
     def _left_pads(attention_mask, B, n):
@@ -1180,7 +1138,6 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
             outs = self._prefill_batch(seqs, cache, stepper=False, chunk=self._prefill_chunk_rows())
             x0 = torch.stack([o[-1] for o in outs], 0)
         embed = self.model.embed_tokens.weight.data
-        V = self.w8_lm_head[0].shape[0] if self.w8_lm_head is not None else self.lm_head.weight.shape[0]
         proc = None
         if processors is not None:
             sup = processors["suppress"]
@@ -1188,10 +1145,10 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
             proc = F.LogitsProcessors(processors["repetition_penalty"], processors["min_new_tokens"],
                                       torch.tensor(sup, dtype=torch.int32).to(dev) if sup else None, processors["want_logprobs"],
                                       None if marks is None else [marks[b // copies] for b in range(B * copies)])
-        loop_args = (self.model.layers, cache.meta, cache.kv, cache.meta.cos, cache.meta.sin, h, dev, self._head_rows_device, embed, V,
-                     self._vision_head_out, start_image_token_id, end_image_token_id, self.get_model().vision_tower.image_token_len,
-                     max_new_tokens, set(eos_token_id))
-        poll = getattr(self.config, "mm355_greedy_poll_steps", 8)
+        loop_args = (self.model.layers, cache.meta, cache.kv, cache.meta.cos, cache.meta.sin, h, dev, self._head_rows_device, embed,
+                     self._vocab_rows, self._vision_head_out, start_image_token_id, end_image_token_id,
+                     self.get_model().vision_tower.image_token_len, max_new_tokens, set(eos_token_id))
+        poll = self._poll_steps()
         if spec:
             loop = F.SpecGreedyLoopGraph(*loop_args, lookup_ids=spec[2], num_draft=spec[0], max_ngram=spec[1], poll=poll)
         else:
@@ -1207,7 +1164,11 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
     # ------------------------------------------------------------------ beam search, token loop on the device
     def _head_text_rows(self, x, logits_out):
         """final norm + lm_head -> fp32 logits into `logits_out`: the text-only head of the beam loop (no image head is run)"""
-        self._lm_head_into(self.model.norm(x).contiguous(), logits_out)
+        self._lm_head(self.model.norm(x).contiguous(), logits_out)
+
+    def _poll_steps(self):
+        """steps between two host reads of a device loop's live counter: config.mm355_greedy_poll_steps (absent: 8)"""
+        return getattr(self.config, "mm355_greedy_poll_steps", 8)
 
     @torch.no_grad()
     def beam_decode(self, position_ids, attention_mask, inputs_embeds, num_beams, eos_token_id=(128001, 128009), max_new_tokens=1024,
@@ -1254,7 +1215,7 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
             raise ValueError(f"beam_decode: early_stopping = {early_stopping!r} must be False, True or 'never'")
         if isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int) or max_new_tokens < 1:
             raise ValueError(f"beam_decode: max_new_tokens = {max_new_tokens!r} must be an integer >= 1")
-        V = self.w8_lm_head[0].shape[0] if self.w8_lm_head is not None else self.lm_head.weight.shape[0]
+        V = self._vocab_rows
         M = F.beam_candidates(K, len(eos))
         if V < M:
             raise ValueError(f"beam_decode: {V} logits are fewer than the {M} candidates a step of {K} beams with {len(eos)} eos ids keeps")
@@ -1287,7 +1248,7 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
         x0 = self._prefill_shared(x2d, cache, K, chunk=self._prefill_chunk_rows(), own_rows=max_new_tokens + 1)
         loop = F.BeamLoopGraph(self.model.layers, cache.meta, cache.kv, cache.meta.cos, cache.meta.sin, h, dev, self._head_text_rows,
                                self.model.embed_tokens.weight.data, V, max_new_tokens, eos, length_penalty, early_stopping,
-                               poll=getattr(self.config, "mm355_greedy_poll_steps", 8))
+                               poll=self._poll_steps())
         self._beam_loop = loop                                # (tools / tests: steps, host_reads, the final state)
         ids, scores, _ = loop.run(x0)
         out = [torch.from_numpy(i).to(dev) for i in ids[:n_ret]]
@@ -1424,14 +1385,7 @@ class MetaMorphLlamaForCausalLM(PreTrainedModel, GenerationMixin, MetaMorphMetaF
     def _rows_logits(self, rows, return_hidden=False):
         """final norm + lm_head -> fp32 logits [n, V] (reference :349-359 final norm, :393-399); return_hidden: (logits, normed rows)."""
         hid = self.model.norm(rows)
-        if self.w8_lm_head is not None:
-            logits = self._lm_head_w8(hid.contiguous())
-            return (logits, hid) if return_hidden else logits
-        if hid.shape[0] <= 32 and ops.gemv_supported(hid, self.lm_head.weight.data):     # (17 .. 32 rows: wide weights only -- the lm_head is one)
-            logits = ops.gemv(hid.contiguous(), self.lm_head.weight.data,
-                              out=torch.empty((hid.shape[0], self.lm_head.weight.shape[0]), device=rows.device, dtype=torch.float32))
-        else:
-            logits = ops.gemm(hid, self.lm_head.weight.data, out_f32=True)
+        logits = self._lm_head(hid.contiguous())
         return (logits, hid) if return_hidden else logits
 
     @torch.no_grad()

@@ -72,6 +72,45 @@ def test_host_model_unrecorded_branches():
     assert F.greedy_advance_host(st, 5, 100, 101, 4, 12, {9}) == (None, None) and st == keep
 
 
+def _host_loop(stream, N, max_new, start=START, end=END, eos=EOS):
+    """functional.greedy_host_loop -- the loop greedy_decode runs for one sequence -- with a head that reads the argmax stream:
+    (ids, pred_z rows, head calls).  Call i hands out the rows ("fed", i) and ("z", i); what is logged and fed back is checked here."""
+    from metamorph_amd import functional as F
+    todo, modes, fed = iter(stream), [], []
+
+    def head(in_image):
+        modes.append(in_image)
+        return next(todo), ("fed", len(modes) - 1), ("z", len(modes) - 1)
+    ids, z_rows = F.greedy_host_loop(head, lambda tok, row: fed.append((tok, row)), start, end, N, max_new, eos)
+    assert len(fed) == len(modes) - 1                            # every iteration but the last one feeds the next
+    assert all(modes[i] for _, i in z_rows)                      # an image row comes from a head call in image mode
+    for i, (tok, row) in enumerate(fed):
+        assert tok == stream[i] and row == (("fed", i) if ("z", i) in z_rows else None)
+    return ids, len(z_rows), len(modes)
+
+
+@pytest.mark.parametrize("name", ["text", "image_prompt", "image_prompt_rope31"])
+def test_host_loop_walks_the_reference_recorded_streams(name):
+    g = np.load(os.path.join(GOLDEN, f"n1_decode_{name}.npz"))
+    stream = g["step_argmax"].tolist()
+    for mn in (int(g["max_new_tokens"]), 2, 6):
+        assert _host_loop(stream, 4, mn) == _walk(stream, 4, mn)[:3]
+    assert _host_loop(stream, 4, int(g["max_new_tokens"])) == (g["tokens"].tolist(), 4, 9)
+    for mn in (2, 6):
+        assert _host_loop(stream, 4, mn) == (g[f"tokens_max{mn}"].tolist(), int(g[f"n_pred_z_max{mn}"]), int(g[f"iterations_max{mn}"]))
+
+
+def test_host_loop_unrecorded_branches():
+    # (the streams of test_host_model_unrecorded_branches that run without log caps; where _walk stops because its stream ends, the
+    # budget ends the loop at the same iteration)
+    assert _host_loop([100, 5, 9, 5, 5], 4, 12, start=100, end=101, eos=(9,)) == ([100], 2, 3)
+    stream = [100, 7, 7, 7, 7, 100, 8, 101, 3]
+    assert _walk(stream[:7], 4, 12, start=100, end=101, eos=(9,))[:3] == ([100, 100, 8], 4, 7)
+    assert _host_loop(stream[:7], 4, 6, start=100, end=101, eos=(9,)) == ([100, 100, 8], 4, 7)
+    assert _walk(stream, 4, 12, start=100, end=101, eos=(9,))[:3] == ([100, 100, 8, 101, 3], 4, 9)
+    assert _host_loop(stream, 4, 8, start=100, end=101, eos=(9,)) == ([100, 100, 8, 101, 3], 4, 9)
+
+
 def test_greedy_symbols_and_validation_without_a_gpu():
     from metamorph_amd import lib
     names = lib.exported_symbols()
