@@ -11,7 +11,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libmm355.so")
 SOURCES = ["gemm_bf16.hip", "rowwise.hip", "elementwise.hip", "attn.hip", "attn2.hip", "attn4.hip", "attn4_bwd.hip", "decode.hip", "attn_decode.hip", "decode_w8.hip", "decode_w4.hip", "decode_kv8.hip", "attn_extend.hip", "attn_extend_shared.hip", "gemm_w8.hip", "gemm_w4.hip", "greedy.hip", "spec.hip", "sample.hip", "logits.hip", "beam.hip", "losses.hip", "linear_ce.hip"]
-HEADERS = ["mm355_common.h", "gemm_common.h", "splitk.h", "gemm_wq.h", "decode_wq.h", "attn2.h", "attn_tile.h", "rowsum.h", "argrows.h"] + sorted(
+HEADERS = ["mm355_common.h", "gemm_common.h", "splitk.h", "gemm_wq.h", "decode_gemv.h", "attn2.h", "attn_tile.h", "rowsum.h", "argrows.h"] + sorted(
     os.path.join(d, f) for d in ("attn4_gen", "attn4_bwd_gen")
     for f in os.listdir(os.path.join(CSRC, d)) if f.endswith(".inc"))   # tools/gen_attn4*.py output
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]

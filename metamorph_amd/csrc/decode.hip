@@ -5,19 +5,36 @@
 //                      wave in flight, fp32 accumulation, the usual bias / GELU / residual epilogue (or SwiGLU / RoPE + cache append)
 //   * rope_kv_append   RoPE on the new q / k row at a device-side position, k and v written into their cache row
 // (the attention of the step, one query row per sample and head against the cache: attn_decode.hip)
-#include "mm355_common.h"
+#include "decode_gemv.h"
 
 namespace {
 
-constexpr int NT = 256;
+// The operands of every bf16 GEMV kernel below; unit_rows / unit_live / plain_store / fused_store (decode_gemv.h) read them by name.
+struct GemvArgs {
+    const uint16_t* x; int64_t ldx;
+    const uint16_t* W; int64_t ldw;
+    int M, N, K;                                             // N = weight rows
+    const uint16_t* norm_w; float eps;                       // PRENORM
+    uint16_t* out; int64_t ld_out;                           // MODE 1: act [M][I]; MODE 2: qkv row buffer [M][N]
+    int I;                                                   // MODE 1
+    int Hq, Hkv, d;                                          // MODE 2
+    const uint16_t* cos_t; const uint16_t* sin_t; const int32_t* positions;
+    uint16_t* kc; uint16_t* vc; int64_t ld_kv, bs_kv;
+    void* y; int64_t ldy;                                    // MODE 0
+    const uint16_t* bias; const uint16_t* res; int64_t ldr; uint32_t flags;
+    int ks;                                                  // MFMA form: waves per unit group (1, 2, 4)
+    int xs_stride;                                           // MFMA form, PRENORM: LDS row stride of the normalised x rows, bytes
+};
 
 // ------------------------------------------------------------------------------------------------ GEMV
 // KS = 1: a wave owns R = 4 weight rows over the whole K.  KS = 2 / 4 (small N): the 4 waves of a workgroup form 4 / KS row
 // groups x KS K-slices, partial sums meet in LDS -- 2x / 4x more waves in flight for the same N.
 template <int MR, int KS>
-__global__ __launch_bounds__(NT) void gemv_kernel(const uint16_t* __restrict__ x, int64_t ldx, const uint16_t* __restrict__ W, int64_t ldw,
-                                                  void* __restrict__ y, int64_t ldy, int M, int N, int K, const uint16_t* __restrict__ bias,
-                                                  const uint16_t* __restrict__ res, int64_t ldr, uint32_t flags) {
+__global__ __launch_bounds__(NT) void gemv_kernel(GemvArgs a) {
+    const uint16_t* __restrict__ x = a.x;
+    const uint16_t* __restrict__ W = a.W;
+    const int64_t ldx = a.ldx, ldw = a.ldw;
+    const int M = a.M, N = a.N, K = a.K;
     constexpr int R = 4;                                     // weight rows per wave
     constexpr int RG = (NT / 64) / KS;                       // row groups per workgroup
     __shared__ float part[NT / 64][MR * R];
@@ -110,12 +127,7 @@ __global__ __launch_bounds__(NT) void gemv_kernel(const uint16_t* __restrict__ x
 #pragma unroll
                 for (int rr = 0; rr < R; ++rr)
                     if (mm == m && rr == r) v = acc[mm][rr];
-            if (flags & MM355_GEMM_BIAS) v += bf2f(bias[n]);
-            if (flags & MM355_GEMM_GELU_ERF) v = gelu_erf_f(v);
-            if (flags & MM355_GEMM_GELU_TANH) v = gelu_tanh_f(v);
-            if (flags & MM355_GEMM_RESIDUAL) v += bf2f(res[(int64_t)m * ldr + n]);
-            if (flags & MM355_GEMM_OUT_F32) ((float*)y)[(int64_t)m * ldy + n] = v;
-            else ((uint16_t*)y)[(int64_t)m * ldy + n] = f2bf(v);
+            plain_store(a, m, n, v);
         }
     }
 }
@@ -127,22 +139,13 @@ __global__ __launch_bounds__(NT) void gemv_kernel(const uint16_t* __restrict__ x
 //            L2-resident) while its first weight loads are in flight, and forms bf16(w * bf16(x * rstd)) -- rmsnorm_fwd_kernel's
 //            arithmetic and reduction order, bit for bit -- as the x operand;
 //   MODE 1   SiLU(gate) * up in the epilogue: a wave owns gate rows c, c + 1 AND up rows I + c, I + 1 + c of the fused weight, rounds
-//            both to bf16 as the unfused GEMV would have stored them and applies swiglu_fwd_kernel's arithmetic; gu never exists;
+//            both to bf16 as the unfused GEMV would have stored them and applies swiglu_f (mm355_common.h), as swiglu_fwd_kernel
+//            does; gu never exists;
 //   MODE 2   RoPE + KV-cache append in the epilogue: a wave owns the rotation partners j, j + 1, j + d/2, j + 1 + d/2 of one head (v rows:
-//            four neighbours), rotates the bf16-rounded q / k values at the DEVICE-side position as rope_kv_append_kernel does and
-//            writes q to the row buffer, k / v to the cache row.
-// One or two rows: gemv_deep_kernel; 3 .. 16: gemv_mfma_kernel (both below; the modes are template parameters of either).
-struct GemvFusedArgs {
-    const uint16_t* x; int64_t ldx;
-    const uint16_t* W; int64_t ldw;
-    int M, N, K;                                             // N = weight rows
-    const uint16_t* norm_w; float eps;                       // PRENORM
-    uint16_t* out; int64_t ld_out;                           // MODE 1: act [M][I]; MODE 2: qkv row buffer [M][N]
-    int I;                                                   // MODE 1
-    int Hq, Hkv, d;                                          // MODE 2
-    const uint16_t* cos_t; const uint16_t* sin_t; const int32_t* positions;
-    uint16_t* kc; uint16_t* vc; int64_t ld_kv, bs_kv;
-};
+//            four neighbours), rotates the bf16-rounded q / k values at the DEVICE-side position with rope_lo / rope_hi, as
+//            rope_kv_append_kernel does, and writes q to the row buffer, k / v to the cache row.
+// One or two rows: gemv_deep_kernel; 3 .. 16: gemv_mfma_kernel (both below; the modes are template parameters of either).  The row units
+// and the epilogues of all of them, and of the quantised twins, are decode_gemv.h's.
 
 // ------------------------------------------------------------------------------------------------ 5 .. 16 rows: the same GEMVs on MFMA
 // Round 5 (batched decode: all rows of a batch / all beams go through the layers in ONE pass).  The vector-ALU form (gemv_deep_kernel below)
@@ -164,43 +167,15 @@ struct GemvFusedArgs {
 //     epilogues of the kernels above take (bias / GELU / residual; SiLU(g) u; RoPE + cache append);
 //   * K is split over KS = 1 / 2 / 4 waves of a workgroup by the number of units (>= ~1000 waves in flight), partial tiles meet in LDS in
 //     a fixed order.  KS depends on (weight rows, K) only, so a fused kernel and the launch sequence it replaces see the same sums.
-struct GemvMfmaArgs {
-    GemvFusedArgs f;                                         // x, W, M, N, K, norm_w / eps, out (MODE 1 / 2) and the MODE fields
-    void* y; int64_t ldy;                                    // MODE 0
-    const uint16_t* bias; const uint16_t* res; int64_t ldr; uint32_t flags;
-    int ks;                                                  // waves per unit group (1, 2, 4)
-    int xs_stride;                                           // PRENORM: LDS row stride of the normalised x rows, bytes
-};
-
-template <int MODE>
-MM_DEV void unit_rows(const GemvFusedArgs& a, int unit, int (&rows)[4]) {
-    if constexpr (MODE == 0) {
-        rows[0] = unit * 4; rows[1] = rows[0] + 1; rows[2] = rows[0] + 2; rows[3] = rows[0] + 3;
-    } else if constexpr (MODE == 1) {
-        const int c = unit * 2;
-        rows[0] = c; rows[1] = c + 1; rows[2] = a.I + c; rows[3] = a.I + c + 1;
-    } else {
-        const int upd = a.d / 4, nrot = (a.Hq + a.Hkv) * upd;
-        if (unit < nrot) {
-            const int hd = unit / upd, j = (unit % upd) * 2;
-            rows[0] = hd * a.d + j; rows[1] = rows[0] + 1; rows[2] = rows[0] + a.d / 2; rows[3] = rows[2] + 1;
-        } else {
-            const int b0 = (a.Hq + a.Hkv) * a.d + (unit - nrot) * 4;
-            rows[0] = b0; rows[1] = b0 + 1; rows[2] = b0 + 2; rows[3] = b0 + 3;
-        }
-    }
-}
-
 // RG = 2 (round 6, 17 .. 32 x rows on the shapes whose waves share one K range, XK == 1: gate|up, lm_head): a SECOND group of 16 x rows rides
 // on the same weight fragments -- every fragment read back from the re-layout buffer feeds two MFMAs, the x windows hold 32 rows (35 KB),
 // the weights are streamed once.  (Sharing weights between WORKGROUPS through L2 was measured and lost: profiles/r6_gemv_row_groups.log.)
 // Each x row's column of D is computed exactly as in a 16-row call: the bits of the 16-row calls on the row slices.
 template <int MODE, bool PRENORM, int GR, bool WLDS = false, int XK = 0, int RG = 1>
-__global__ __launch_bounds__(NT) void gemv_mfma_kernel(GemvMfmaArgs g) {
+__global__ __launch_bounds__(NT) void gemv_mfma_kernel(GemvArgs a) {
     static_assert(!WLDS || GR == 1, "the LDS re-layout is written for one group of 16 rows per wave");
     static_assert(XK == 0 || (WLDS && !PRENORM), "x windows come with the coalesced weight stream");
     static_assert(RG == 1 || (RG == 2 && XK == 1 && GR == 1), "two x row groups: one K range per workgroup, x windows in LDS");
-    const GemvFusedArgs& a = g.f;
     constexpr int WROW = 512 + 32;                           // WLDS: bytes per weight row of a 256-column block in LDS (+ 32: every 16-lane group the hardware services together
                                                              // reads 16 different 16-byte slots of the 256-byte bank row; + 16 leaves two-way conflicts: tests/test_host_logic.py)
     __shared__ __attribute__((aligned(16))) unsigned char wl[WLDS ? NT / 64 : 1][WLDS ? 16 * WROW : 16];
@@ -210,7 +185,7 @@ __global__ __launch_bounds__(NT) void gemv_mfma_kernel(GemvMfmaArgs g) {
     __shared__ float rstd_s[16];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int fr = lane & 15, fq = lane >> 4;
-    const int K = a.K, M = a.M, KS = XK ? XK : g.ks;
+    const int K = a.K, M = a.M, KS = XK ? XK : a.ks;
     // a wave owns GR groups of 16 weight rows (= 4 GR units) over its K slice: one x fragment feeds GR MFMAs
     const int grp0 = (blockIdx.x * ((NT / 64) / KS) + wave / KS) * GR, ks = wave % KS;
     int rows[4];
@@ -246,7 +221,6 @@ __global__ __launch_bounds__(NT) void gemv_mfma_kernel(GemvMfmaArgs g) {
     // skip the prefetch behind the last block (a branch around a prefetch makes hipcc wait for it at the merge: no pipelining)
     const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)a.W, 0, (uint32_t)((uint64_t)(a.N - 1) * a.ldw * 2 + (uint64_t)K * 2), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, (uint32_t)((uint64_t)(M - 1) * a.ldx * 2 + (uint64_t)K * 2), 0x00020000);
-    const uint32_t OOB = 0xf0000000u;
     const int nst = (K + 31) >> 5;                            // k-steps of 32
     const int s0 = (nst * ks) / KS, s1 = (nst * (ks + 1)) / KS;
     constexpr int U = 8 / GR;                                // k-steps per block: GR x U = 8 weight fragments per buffer, two buffers
@@ -273,7 +247,7 @@ __global__ __launch_bounds__(NT) void gemv_mfma_kernel(GemvMfmaArgs g) {
     auto loadx = [&](u32x4 (&xv)[U], int s, uint32_t skip) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            if constexpr (PRENORM) xv[u] = *(const u32x4*)(xs + min(fr, M - 1) * g.xs_stride + (min(s + u, nst - 1) * 32 + fq * 8) * 2);
+            if constexpr (PRENORM) xv[u] = *(const u32x4*)(xs + min(fr, M - 1) * a.xs_stride + (min(s + u, nst - 1) * 32 + fq * 8) * 2);
             else xv[u] = __builtin_amdgcn_raw_buffer_load_b128(rsX, (xo + (uint32_t)(s + u) * 64u) | skip, 0, 0);
         }
     };
@@ -346,13 +320,13 @@ __global__ __launch_bounds__(NT) void gemv_mfma_kernel(GemvMfmaArgs g) {
             const float rs = rstd_s[m];
 #pragma unroll
             for (int e = 0; e < 8; ++e) xv[e] = nw[e] * round_bf(xv[e] * rs);
-            *(u32x4*)(xs + (int64_t)m * g.xs_stride + v * 16) = pack8(xv);
+            *(u32x4*)(xs + (int64_t)m * a.xs_stride + v * 16) = pack8(xv);
         }
         // the columns between K and the end of its last 32-column step: a prefetched block behind the slice reads them against zero
         // weights, and 0 x (whatever the previous kernel left in LDS) may be NaN
         const int npad = ((K + 31) >> 5) * 4 - nv;
         for (int i = threadIdx.x; i < M * npad; i += NT)
-            *(u32x4*)(xs + (int64_t)(i / npad) * g.xs_stride + (nv + i % npad) * 16) = u32x4{0u, 0u, 0u, 0u};
+            *(u32x4*)(xs + (int64_t)(i / npad) * a.xs_stride + (nv + i % npad) * 16) = u32x4{0u, 0u, 0u, 0u};
         __syncthreads();
     }
     f32x4 acc[GR][2], acc1[2];                               // acc1: the second x row group (RG == 2)
@@ -431,7 +405,7 @@ __global__ __launch_bounds__(NT) void gemv_mfma_kernel(GemvMfmaArgs g) {
         const bool in = st * 32 + fq * 8 < K;
         const int off = in ? st * 32 : 0;
         u32x4 xv;
-        if constexpr (PRENORM) xv = *(const u32x4*)(xs + min(fr, M - 1) * g.xs_stride + (off + fq * 8) * 2);
+        if constexpr (PRENORM) xv = *(const u32x4*)(xs + min(fr, M - 1) * a.xs_stride + (off + fq * 8) * 2);
         else xv = *(const u32x4*)(xp + off);
         xv = in ? xv : z4;
 #pragma unroll
@@ -473,50 +447,15 @@ __global__ __launch_bounds__(NT) void gemv_mfma_kernel(GemvMfmaArgs g) {
         const f32x4 d = rg == 0 ? dd[gi] : acc1[0] + acc1[1];
         unit_rows<MODE>(a, (grp0 + gi) * 4 + fq, rows);
         if constexpr (MODE == 0) {
-            const uint32_t flags = g.flags;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int n = rows[r];
-                if (n >= a.N) continue;
-                float v = d[r];
-                if (flags & MM355_GEMM_BIAS) v += bf2f(g.bias[n]);
-                if (flags & MM355_GEMM_GELU_ERF) v = gelu_erf_f(v);
-                if (flags & MM355_GEMM_GELU_TANH) v = gelu_tanh_f(v);
-                if (flags & MM355_GEMM_RESIDUAL) v += bf2f(g.res[(int64_t)m * g.ldr + n]);
-                if (flags & MM355_GEMM_OUT_F32) ((float*)g.y)[(int64_t)m * g.ldy + n] = v;
-                else ((uint16_t*)g.y)[(int64_t)m * g.ldy + n] = f2bf(v);
-            }
+            for (int r = 0; r < 4; ++r)
+                if (rows[r] < a.N) plain_store(a, m, rows[r], d[r]);
         } else {
-            if (rows[3] >= a.N || (MODE == 1 && rows[1] >= a.I)) continue;
+            if (!unit_live<MODE>(a, rows)) continue;
             float v4[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) v4[r] = round_bf(d[r]);  // what the unfused GEMV stores
-            if constexpr (MODE == 1) {
-                float o[2];
-#pragma unroll
-                for (int e = 0; e < 2; ++e) o[e] = round_bf(v4[e] / (1.0f + __expf(-v4[e]))) * v4[2 + e];
-                *(uint32_t*)(a.out + (int64_t)m * a.ld_out + rows[0]) = pack2bf(o[0], o[1]);
-            } else {
-                const int nqk = (a.Hq + a.Hkv) * a.d;
-                const int pos = a.positions[m];
-                if (rows[0] < nqk) {
-                    const int hd = rows[0] / a.d, j = rows[0] % a.d;
-                    float y1[2], y2[2];
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        const float c = bf2f(a.cos_t[(int64_t)pos * a.d + j + e]), sn = bf2f(a.sin_t[(int64_t)pos * a.d + j + e]);
-                        y1[e] = round_bf(v4[e] * c) + round_bf(-v4[2 + e] * sn);
-                        y2[e] = round_bf(v4[2 + e] * c) + round_bf(v4[e] * sn);
-                    }
-                    uint16_t* dst = hd < a.Hq ? a.out + (int64_t)m * a.ld_out + rows[0]
-                                              : a.kc + (int64_t)m * a.bs_kv + (int64_t)pos * a.ld_kv + (int64_t)(hd - a.Hq) * a.d + j;
-                    *(uint32_t*)dst = pack2bf(y1[0], y1[1]);
-                    *(uint32_t*)(dst + a.d / 2) = pack2bf(y2[0], y2[1]);
-                } else {
-                    uint16_t* dst = a.vc + (int64_t)m * a.bs_kv + (int64_t)pos * a.ld_kv + (rows[0] - nqk);
-                    *(u32x2*)dst = u32x2{pack2bf(v4[0], v4[1]), pack2bf(v4[2], v4[3])};
-                }
-            }
+            fused_store<MODE>(a, rows, m, v4);
         }
     }
     }
@@ -534,14 +473,14 @@ void gemv_mfma_shape(int64_t units, int& gr, int& ks) {
 }
 
 template <int MODE, int GR>
-int launch_gemv_mfma_gr(GemvMfmaArgs& g, int64_t units, bool prenorm, hipStream_t s) {
+int launch_gemv_mfma_gr(GemvArgs& g, int64_t units, bool prenorm, hipStream_t s) {
     const int64_t blocks = ((units + 3) / 4 + GR - 1) / GR;
     const int bpw = (NT / 64) / g.ks;
     const unsigned grid = (unsigned)((blocks + bpw - 1) / bpw);
     if (prenorm) {
-        if (g.f.M > 16) return MM355_EUNSUPPORTED;
-        g.xs_stride = (((g.f.K + 31) >> 5) * 32 + 8) * 2;    // whole 32-column steps + 16 B per row: the 16 x rows of a fragment read fall on different banks
-        const int lds = g.f.M * g.xs_stride;
+        if (g.M > 16) return MM355_EUNSUPPORTED;
+        g.xs_stride = (((g.K + 31) >> 5) * 32 + 8) * 2;    // whole 32-column steps + 16 B per row: the 16 x rows of a fragment read fall on different banks
+        const int lds = g.M * g.xs_stride;
         if (lds > 140 * 1024) return MM355_EUNSUPPORTED;
         static std::atomic<uint64_t> ok{0};                  // (one opt-in per device, to the largest size any call may ask for)
         if (mm_ensure_dynamic_lds((const void*)gemv_mfma_kernel<MODE, true, GR>, 140 * 1024, ok) != MM355_OK) return MM355_ELAUNCH;
@@ -551,10 +490,10 @@ int launch_gemv_mfma_gr(GemvMfmaArgs& g, int64_t units, bool prenorm, hipStream_
             // measured (profiles/r5_gemv_rows.log): the windows win wherever the waves of a workgroup share one K range (wide weights:
             // gate|up 47 -> 42 us at 8 rows, 53 -> 42 at 16, lm_head 208 -> 174) and, with K split over the waves, from nine rows on
             // (down 26.8 -> 23.6 at 16); below that the per-block barriers of four slices cost more than the L2 reads they replace
-            if (g.f.M > 16) {                                // 17 .. 32 rows: two x row groups per workgroup, shapes with one K range per workgroup only
+            if (g.M > 16) {                                // 17 .. 32 rows: two x row groups per workgroup, shapes with one K range per workgroup only
                 if constexpr (MODE == 2) return MM355_EUNSUPPORTED;
                 else {
-                    if (g.ks != 1 || g.f.M > 32) return MM355_EUNSUPPORTED;
+                    if (g.ks != 1 || g.M > 32) return MM355_EUNSUPPORTED;
                     static std::atomic<uint64_t> ok2{0};
                     constexpr int XL2 = 2 * 1 * 16 * 2 * 544;
                     if (mm_ensure_dynamic_lds((const void*)gemv_mfma_kernel<MODE, false, 1, true, 1, 2>, XL2, ok2) != MM355_OK) return MM355_ELAUNCH;
@@ -562,7 +501,7 @@ int launch_gemv_mfma_gr(GemvMfmaArgs& g, int64_t units, bool prenorm, hipStream_
                     return mm_launch_status();
                 }
             }
-            if (g.ks > 1 && g.f.M <= 8) { hipLaunchKernelGGL((gemv_mfma_kernel<MODE, false, 1, true>), dim3(grid), dim3(NT), 0, s, g); return mm_launch_status(); }
+            if (g.ks > 1 && g.M <= 8) { hipLaunchKernelGGL((gemv_mfma_kernel<MODE, false, 1, true>), dim3(grid), dim3(NT), 0, s, g); return mm_launch_status(); }
             const int xlds = 2 * g.ks * 16 * 544;
 #define GX(KSC) do { static std::atomic<uint64_t> okx{0};                                                                                      \
                 if (mm_ensure_dynamic_lds((const void*)gemv_mfma_kernel<MODE, false, 1, true, KSC>, 2 * 4 * 16 * 544, okx) != MM355_OK) return MM355_ELAUNCH; \
@@ -582,7 +521,7 @@ bool gemv_mfma_addressable(int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t
 }
 
 template <int MODE>
-int launch_gemv_mfma(GemvMfmaArgs& g, int64_t units, bool prenorm, hipStream_t s) {
+int launch_gemv_mfma(GemvArgs& g, int64_t units, bool prenorm, hipStream_t s) {
     int gr;
     gemv_mfma_shape(units, gr, g.ks);                        // (gr is 1: two / four groups of 16 rows per wave were measured and bought nothing; the kernel keeps the parameter)
     return launch_gemv_mfma_gr<MODE, 1>(g, units, prenorm, s);
@@ -610,8 +549,7 @@ int launch_gemv_mfma(GemvMfmaArgs& g, int64_t units, bool prenorm, hipStream_t s
 // waves), lm_head 155 (was 170): 2.89 ms per token = 5.2 TB/s of weights; ring depth 1 .. 4 is within noise of it (the in-order x loads
 // were the stall, not the depth).  Four rows: gate|up 41 us (5.7 TB/s).
 template <int MR, int MODE, bool PRENORM, bool WINDOWS, int WT = 4>
-__global__ __launch_bounds__(NT) void gemv_deep_kernel(GemvMfmaArgs g) {
-    const GemvFusedArgs& a = g.f;
+__global__ __launch_bounds__(NT) void gemv_deep_kernel(GemvArgs a) {
     constexpr int R = 4;
     constexpr bool DOT2 = MR > 2;                            // (the fma chain at four / eight rows: gate|up 48.8 / 89.7 us against 42.0 / 63.9)
     constexpr int NB = 2;                                    // trips in the register ring (measured at one row, 1 .. 4: 2.87 / 2.89 / 3.08 / 3.00 ms per token)
@@ -628,14 +566,10 @@ __global__ __launch_bounds__(NT) void gemv_deep_kernel(GemvMfmaArgs g) {
     const int wk = min(ntrip, WT) << 10;                     // elements per window row in LDS
     int rows[R];
     unit_rows<MODE>(a, unit, rows);
-    bool live;
-    if constexpr (MODE == 0) live = rows[0] < a.N;
-    else if constexpr (MODE == 1) live = rows[1] < a.I;
-    else live = rows[3] < a.N;
+    const bool live = unit_live<MODE>(a, rows);
     const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)a.W, 0, (uint32_t)((uint64_t)(a.N - 1) * a.ldw * 2 + (uint64_t)K * 2), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, (uint32_t)((uint64_t)(M - 1) * a.ldx * 2 + (uint64_t)K * 2), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsN = __builtin_amdgcn_make_buffer_rsrc((void*)(PRENORM ? a.norm_w : a.x), 0, (uint32_t)K * 2u, 0x00020000);
-    const uint32_t OOB = 0xf0000000u;
     uint32_t wo[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) wo[r] = (uint32_t)min(rows[r], a.N - 1) * (uint32_t)a.ldw * 2u;
@@ -817,7 +751,7 @@ __global__ __launch_bounds__(NT) void gemv_deep_kernel(GemvMfmaArgs g) {
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[m][r] = wave_sum(acc[m][r]);
     if (!live) return;
-    if constexpr (MODE == 0) {                               // gemv_kernel's epilogue: lane (m * R + r) finishes output (m, rows[r])
+    if constexpr (MODE == 0) {                               // lane (m * R + r) finishes output (m, rows[r])
         if (lane < MR * R) {
             const int m = lane / R, r = lane % R, n = rows[0] + r;
             if (m < M && n < a.N) {
@@ -827,16 +761,9 @@ __global__ __launch_bounds__(NT) void gemv_deep_kernel(GemvMfmaArgs g) {
 #pragma unroll
                     for (int rr = 0; rr < R; ++rr)
                         if (mm == m && rr == r) v = acc[mm][rr];
-                const uint32_t flags = g.flags;
-                if (flags & MM355_GEMM_BIAS) v += bf2f(g.bias[n]);
-                if (flags & MM355_GEMM_GELU_ERF) v = gelu_erf_f(v);
-                if (flags & MM355_GEMM_GELU_TANH) v = gelu_tanh_f(v);
-                if (flags & MM355_GEMM_RESIDUAL) v += bf2f(g.res[(int64_t)m * g.ldr + n]);
-                if (flags & MM355_GEMM_OUT_F32) ((float*)g.y)[(int64_t)m * g.ldy + n] = v;
-                else ((uint16_t*)g.y)[(int64_t)m * g.ldy + n] = f2bf(v);
+                plain_store(a, m, n, v);
             }
         }
-        return;
     } else {
         if (lane >= M) return;                               // the fused epilogues: lane m finishes the unit's outputs of row m
         float v4[R];
@@ -848,33 +775,7 @@ __global__ __launch_bounds__(NT) void gemv_deep_kernel(GemvMfmaArgs g) {
                 if (mm == lane) t = acc[mm][r];
             v4[r] = round_bf(t);                             // what the unfused GEMV stores
         }
-        const int m = lane;
-        if constexpr (MODE == 1) {
-            float o[2];
-#pragma unroll
-            for (int e = 0; e < 2; ++e) o[e] = round_bf(v4[e] / (1.0f + __expf(-v4[e]))) * v4[2 + e];
-            *(uint32_t*)(a.out + (int64_t)m * a.ld_out + rows[0]) = pack2bf(o[0], o[1]);
-        } else {
-            const int nqk = (a.Hq + a.Hkv) * a.d;
-            const int pos = a.positions[m];
-            if (rows[0] < nqk) {
-                const int hd = rows[0] / a.d, j = rows[0] % a.d;
-                float y1[2], y2[2];
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const float c = bf2f(a.cos_t[(int64_t)pos * a.d + j + e]), sn = bf2f(a.sin_t[(int64_t)pos * a.d + j + e]);
-                    y1[e] = round_bf(v4[e] * c) + round_bf(-v4[2 + e] * sn);
-                    y2[e] = round_bf(v4[2 + e] * c) + round_bf(v4[e] * sn);
-                }
-                uint16_t* dst = hd < a.Hq ? a.out + (int64_t)m * a.ld_out + rows[0]
-                                          : a.kc + (int64_t)m * a.bs_kv + (int64_t)pos * a.ld_kv + (int64_t)(hd - a.Hq) * a.d + j;
-                *(uint32_t*)dst = pack2bf(y1[0], y1[1]);
-                *(uint32_t*)(dst + a.d / 2) = pack2bf(y2[0], y2[1]);
-            } else {
-                uint16_t* dst = a.vc + (int64_t)m * a.bs_kv + (int64_t)pos * a.ld_kv + (rows[0] - nqk);
-                *(u32x2*)dst = u32x2{pack2bf(v4[0], v4[1]), pack2bf(v4[2], v4[3])};
-            }
-        }
+        fused_store<MODE>(a, rows, lane, v4);
     }
 }
 
@@ -883,10 +784,10 @@ bool gemv_deep_applies(int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldw
 }
 
 template <int MODE>
-int launch_gemv_deep(GemvMfmaArgs& g, int64_t units, bool prenorm, hipStream_t s) {
+int launch_gemv_deep(GemvArgs& g, int64_t units, bool prenorm, hipStream_t s) {
     const unsigned grid = (unsigned)((units + NT / 64 - 1) / (NT / 64));
-    const int ntrip = (g.f.K + 1023) >> 10;
-    const int mr = g.f.M == 1 ? 1 : (g.f.M == 2 ? 2 : 4);
+    const int ntrip = (g.K + 1023) >> 10;
+    const int mr = g.M == 1 ? 1 : (g.M == 2 ? 2 : 4);
     const int wt = (MODE == 0 && !prenorm && ntrip > 4 && ntrip <= 16) ? 16 : 4;   // trips per x window (gemv_deep_kernel: WT)
     const int lds = (ntrip > wt ? 2 : 1) * mr * (ntrip < wt ? ntrip : wt) * 1024 * 2;    // <= 64 KiB unless two rows are longer than 16384 columns
 #define GD4(MR, PN, WN) do { if (lds > 65536) { static std::atomic<uint64_t> ok{0};                                                            \
@@ -907,7 +808,7 @@ int launch_gemv_deep(GemvMfmaArgs& g, int64_t units, bool prenorm, hipStream_t s
 }
 
 // ------------------------------------------------------------------------------------------------ RoPE + cache append
-// One new qkv row per sample: rotate q and k at position positions[b] (HF rounding order, as rope_qk_kernel), leave q in
+// One new qkv row per sample: rotate q and k at position positions[b] (HF rounding order: rope_lo / rope_hi), leave q in
 // place and write the rotated k and the v row into cache row positions[b].  Positions come from DEVICE memory so that the
 // whole per-token step is replayable as a hipGraph.
 // The items [i0, i0 + istep, ..) of one row: `row` rotated at `pos`, q in place, k -> krow, v -> vrow (the two cache rows of the row).
@@ -928,8 +829,8 @@ MM_DEV void rope_kv_append_row(uint16_t* __restrict__ row, int pos, int Hq, int 
             unpack8(*(const u32x4*)(sin_t + (int64_t)pos * d + v * 8), sn);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                y1[e] = round_bf(x1[e] * c[e]) + round_bf(-x2[e] * sn[e]);
-                y2[e] = round_bf(x2[e] * c[e]) + round_bf(x1[e] * sn[e]);
+                y1[e] = rope_lo(x1[e], x2[e], c[e], sn[e]);
+                y2[e] = rope_hi(x2[e], x1[e], c[e], sn[e]);
             }
             const u32x4 o1 = pack8(y1), o2 = pack8(y2);
             if (hd < Hq) { *(u32x4*)p1 = o1; *(u32x4*)p2 = o2; }
@@ -982,25 +883,20 @@ extern "C" int mm355_gemv_bf16(const mm355_bf16* x, int64_t ldx, const mm355_bf1
     if (flags & MM355_GEMM_ACCUMULATE) return MM355_EUNSUPPORTED;
     if (N > 0x7fffffff || K > 0x7fffffff) return MM355_EINVAL;
     hipStream_t s = (hipStream_t)stream;
+    GemvArgs g = {};
+    g.x = x; g.ldx = ldx; g.W = W; g.ldw = ldw; g.M = (int)M; g.N = (int)N; g.K = (int)K;
+    g.y = y; g.ldy = ldy; g.bias = bias; g.res = residual; g.ldr = ldr; g.flags = flags;
     if (M > 4) {                                             // 5 .. 16 rows: the MFMA form (up to four rows: the VALU kernels below)
         if (!gemv_mfma_addressable(M, N, K, ldx, ldw)) return MM355_EUNSUPPORTED;
-        GemvMfmaArgs g = {};
-        g.f.x = x; g.f.ldx = ldx; g.f.W = W; g.f.ldw = ldw; g.f.M = (int)M; g.f.N = (int)N; g.f.K = (int)K;
-        g.y = y; g.ldy = ldy; g.bias = bias; g.res = residual; g.ldr = ldr; g.flags = flags;
         return launch_gemv_mfma<0>(g, (N + 3) / 4, false, s);
     }
-    if (gemv_deep_applies(M, N, K, ldx, ldw)) {
-        GemvMfmaArgs g = {};
-        g.f.x = x; g.f.ldx = ldx; g.f.W = W; g.f.ldw = ldw; g.f.M = (int)M; g.f.N = (int)N; g.f.K = (int)K;
-        g.y = y; g.ldy = ldy; g.bias = bias; g.res = residual; g.ldr = ldr; g.flags = flags;
-        return launch_gemv_deep<0>(g, (N + 3) / 4, false, s);
-    }
+    if (gemv_deep_applies(M, N, K, ldx, ldw)) return launch_gemv_deep<0>(g, (N + 3) / 4, false, s);
     // a weight beyond 32-bit byte offsets: the plain stream (x re-read from L2 per chunk); few rows of a long K split K over the waves
     // of a workgroup
     const int ksplit = (N <= 8192 && K >= 8192) ? 4 : 1;
     const int rows_per_wg = 16 / ksplit;
     const unsigned grid = (unsigned)((N + rows_per_wg - 1) / rows_per_wg);
-#define GV2(MR, KSV) hipLaunchKernelGGL((gemv_kernel<MR, KSV>), dim3(grid), dim3(NT), 0, s, x, ldx, W, ldw, y, ldy, (int)M, (int)N, (int)K, bias, residual, ldr, flags)
+#define GV2(MR, KSV) hipLaunchKernelGGL((gemv_kernel<MR, KSV>), dim3(grid), dim3(NT), 0, s, g)
 #define GV(MR) do { if (ksplit == 4) GV2(MR, 4); else if (ksplit == 2) GV2(MR, 2); else GV2(MR, 1); } while (0)
     if (M == 1) GV(1);
     else if (M == 2) GV(2);
@@ -1039,9 +935,6 @@ extern "C" int mm355_rope_kv_append_rows(mm355_bf16* qkv, int64_t ld, int64_t R,
     return mm_launch_status();
 }
 
-namespace {
-}  // namespace
-
 extern "C" int mm355_gemv_swiglu_bf16(const mm355_bf16* x, int64_t ldx, const mm355_bf16* Wgu, int64_t ldw, mm355_bf16* act, int64_t ld_act,
                                       int64_t M, int64_t I, int64_t K, const mm355_bf16* norm_w, float eps, void* stream) {
     (void)hipGetLastError();
@@ -1050,20 +943,14 @@ extern "C" int mm355_gemv_swiglu_bf16(const mm355_bf16* x, int64_t ldx, const mm
     if ((K & 7) || (ldx & 7) || (ldw & 7) || (ld_act & 1) || !mm_aligned16(x) || !mm_aligned16(Wgu) || (((uintptr_t)act) & 3u)) return MM355_EINVAL;
     if (norm_w && !mm_aligned16(norm_w)) return MM355_EINVAL;
     if (I > 0x3fffffff || K > 0x7fffffff) return MM355_EINVAL;
-    GemvFusedArgs a = {};
-    a.x = x; a.ldx = ldx; a.W = Wgu; a.ldw = ldw; a.M = (int)M; a.N = (int)(2 * I); a.K = (int)K; a.norm_w = norm_w; a.eps = eps;
-    a.out = act; a.ld_out = ld_act; a.I = (int)I;
+    GemvArgs g = {};
+    g.x = x; g.ldx = ldx; g.W = Wgu; g.ldw = ldw; g.M = (int)M; g.N = (int)(2 * I); g.K = (int)K; g.norm_w = norm_w; g.eps = eps;
+    g.out = act; g.ld_out = ld_act; g.I = (int)I;
     if (M > 4) {
         if (!gemv_mfma_addressable(M, 2 * I, K, ldx, ldw)) return MM355_EUNSUPPORTED;
-        GemvMfmaArgs g = {};
-        g.f = a;
         return launch_gemv_mfma<1>(g, I / 2, norm_w != nullptr, (hipStream_t)stream);
     }
-    if (gemv_deep_applies(M, 2 * I, K, ldx, ldw)) {
-        GemvMfmaArgs g = {};
-        g.f = a;
-        return launch_gemv_deep<1>(g, I / 2, norm_w != nullptr, (hipStream_t)stream);
-    }
+    if (gemv_deep_applies(M, 2 * I, K, ldx, ldw)) return launch_gemv_deep<1>(g, I / 2, norm_w != nullptr, (hipStream_t)stream);
     return MM355_EUNSUPPORTED;                               // a weight beyond 32-bit byte offsets: the unfused launch sequence
 }
 
@@ -1081,20 +968,14 @@ extern "C" int mm355_gemv_rope_append_bf16(const mm355_bf16* x, int64_t ldx, con
     if (norm_w && !mm_aligned16(norm_w)) return MM355_EINVAL;
     const int64_t N = (Hq + 2 * Hkv) * d;
     if (N > 0x7fffffff || K > 0x7fffffff) return MM355_EINVAL;
-    GemvFusedArgs a = {};
-    a.x = x; a.ldx = ldx; a.W = Wqkv; a.ldw = ldw; a.M = (int)M; a.N = (int)N; a.K = (int)K; a.norm_w = norm_w; a.eps = eps;
-    a.out = qkv; a.ld_out = ld_qkv; a.Hq = (int)Hq; a.Hkv = (int)Hkv; a.d = (int)d;
-    a.cos_t = cos_t; a.sin_t = sin_t; a.positions = positions; a.kc = k_cache; a.vc = v_cache; a.ld_kv = ld_kv; a.bs_kv = batch_stride_kv;
+    GemvArgs g = {};
+    g.x = x; g.ldx = ldx; g.W = Wqkv; g.ldw = ldw; g.M = (int)M; g.N = (int)N; g.K = (int)K; g.norm_w = norm_w; g.eps = eps;
+    g.out = qkv; g.ld_out = ld_qkv; g.Hq = (int)Hq; g.Hkv = (int)Hkv; g.d = (int)d;
+    g.cos_t = cos_t; g.sin_t = sin_t; g.positions = positions; g.kc = k_cache; g.vc = v_cache; g.ld_kv = ld_kv; g.bs_kv = batch_stride_kv;
     if (M > 4) {
         if (!gemv_mfma_addressable(M, N, K, ldx, ldw)) return MM355_EUNSUPPORTED;
-        GemvMfmaArgs g = {};
-        g.f = a;
         return launch_gemv_mfma<2>(g, N / 4, norm_w != nullptr, (hipStream_t)stream);
     }
-    if (gemv_deep_applies(M, N, K, ldx, ldw)) {
-        GemvMfmaArgs g = {};
-        g.f = a;
-        return launch_gemv_deep<2>(g, N / 4, norm_w != nullptr, (hipStream_t)stream);
-    }
+    if (gemv_deep_applies(M, N, K, ldx, ldw)) return launch_gemv_deep<2>(g, N / 4, norm_w != nullptr, (hipStream_t)stream);
     return MM355_EUNSUPPORTED;                               // a weight beyond 32-bit byte offsets: the unfused launch sequence
 }

@@ -1,6 +1,7 @@
-// What the decode GEMVs over quantised weights share (decode_w8.hip: e4m3 bytes + a scale per row; decode_w4.hip: MXFP4 nibbles + a scale
-// byte per 32 columns): the kernel operands, the four weight rows of a unit in each mode and the epilogues (those of decode.hip).  The two
-// files differ in how a 16-byte load becomes packed bf16 pairs and in where the scale enters; everything behind the sum is this header.
+// What the decode GEMVs share (decode.hip: bf16 weights; decode_w8.hip: e4m3 bytes + a scale per row; decode_w4.hip: MXFP4 nibbles + a
+// scale byte per 32 columns): the four weight rows of a unit in each mode and the epilogues, templated on the kernel's operand struct (A:
+// WqArgs below, GemvArgs in decode.hip), and the operands of the quantised kernels.  The files differ in how a 16-byte load becomes packed
+// bf16 pairs and in where the scale enters; everything behind the sum is this header.
 #pragma once
 
 #include "mm355_common.h"
@@ -27,10 +28,10 @@ struct WqArgs {
     int ks;                                                  // MFMA form: waves that share one group of 16 weight rows (1, 4)
 };
 
-// the four weight rows of a unit (decode.hip: unit_rows): plain = 4u .. 4u+3; SwiGLU = gate rows c, c+1 and up rows I+c, I+c+1; RoPE = the
+// the four weight rows of a unit: plain = 4u .. 4u+3; SwiGLU = gate rows c, c+1 and up rows I+c, I+c+1; RoPE = the
 // rotation partners j, j+1, j+d/2, j+1+d/2 of one head (v rows: four neighbours)
-template <int MODE>
-MM_DEV void unit_rows(const WqArgs& a, int unit, int (&rows)[4]) {
+template <int MODE, class A>
+MM_DEV void unit_rows(const A& a, int unit, int (&rows)[4]) {
     if constexpr (MODE == 0) {
         rows[0] = unit * 4; rows[1] = rows[0] + 1; rows[2] = rows[0] + 2; rows[3] = rows[0] + 3;
     } else if constexpr (MODE == 1) {
@@ -47,15 +48,16 @@ MM_DEV void unit_rows(const WqArgs& a, int unit, int (&rows)[4]) {
         }
     }
 }
-template <int MODE>
-MM_DEV bool unit_live(const WqArgs& a, const int (&rows)[4]) {
+template <int MODE, class A>
+MM_DEV bool unit_live(const A& a, const int (&rows)[4]) {
     if constexpr (MODE == 0) return rows[0] < a.N;
     else if constexpr (MODE == 1) return rows[1] < a.I;
     else return rows[3] < a.N;
 }
 
-// MODE 0: output (m, n) of the finished sum v (w8: scale[n] * sum) -- gemv_kernel's epilogue
-MM_DEV void plain_store(const WqArgs& a, int m, int n, float v) {
+// MODE 0: output (m, n) of the finished sum v (w8: scale[n] * sum): + bias, GELU, + residual, fp32 or bf16
+template <class A>
+MM_DEV void plain_store(const A& a, int m, int n, float v) {
     const uint32_t flags = a.flags;
     if (flags & MM355_GEMM_BIAS) v += bf2f(a.bias[n]);
     if (flags & MM355_GEMM_GELU_ERF) v = gelu_erf_f(v);
@@ -65,14 +67,14 @@ MM_DEV void plain_store(const WqArgs& a, int m, int n, float v) {
     else ((uint16_t*)a.y)[(int64_t)m * a.ldy + n] = f2bf(v);
 }
 
-// MODE 1 / 2: the four outputs of one unit for x row m, already rounded to bf16 (what the unfused GEMV stores): swiglu_fwd_kernel's /
-// rope_kv_append_kernel's arithmetic, as in gemv_deep_kernel
-template <int MODE>
-MM_DEV void fused_store(const WqArgs& a, const int (&rows)[4], int m, const float (&v4)[4]) {
+// MODE 1 / 2: the four outputs of one unit for x row m, already rounded to bf16 (what the unfused GEMV stores), through swiglu_f /
+// rope_lo and rope_hi (mm355_common.h) as swiglu_fwd_kernel / rope_kv_append_kernel would take them
+template <int MODE, class A>
+MM_DEV void fused_store(const A& a, const int (&rows)[4], int m, const float (&v4)[4]) {
     if constexpr (MODE == 1) {
         float o[2];
 #pragma unroll
-        for (int e = 0; e < 2; ++e) o[e] = round_bf(v4[e] / (1.0f + __expf(-v4[e]))) * v4[2 + e];
+        for (int e = 0; e < 2; ++e) o[e] = swiglu_f(v4[e], v4[2 + e]);
         *(uint32_t*)(a.out + (int64_t)m * a.ld_out + rows[0]) = pack2bf(o[0], o[1]);
     } else {
         const int nqk = (a.Hq + a.Hkv) * a.d;
@@ -83,8 +85,8 @@ MM_DEV void fused_store(const WqArgs& a, const int (&rows)[4], int m, const floa
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const float c = bf2f(a.cos_t[(int64_t)pos * a.d + j + e]), sn = bf2f(a.sin_t[(int64_t)pos * a.d + j + e]);
-                y1[e] = round_bf(v4[e] * c) + round_bf(-v4[2 + e] * sn);
-                y2[e] = round_bf(v4[2 + e] * c) + round_bf(v4[e] * sn);
+                y1[e] = rope_lo(v4[e], v4[2 + e], c, sn);
+                y2[e] = rope_hi(v4[2 + e], v4[e], c, sn);
             }
             uint16_t* dst = hd < a.Hq ? a.out + (int64_t)m * a.ld_out + rows[0]
                                       : a.kc + (int64_t)m * a.bs_kv + (int64_t)pos * a.ld_kv + (int64_t)(hd - a.Hq) * a.d + j;

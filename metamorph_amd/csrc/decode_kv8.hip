@@ -72,8 +72,8 @@ MM_DEV void rope_kv_append_f8_row(uint16_t* __restrict__ row, int pos, int Hq, i
         unpack8(*(const u32x4*)(sin_t + (int64_t)pos * d + v * 8), sn);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            y1[e] = round_bf(x1[e] * c[e]) + round_bf(-x2[e] * sn[e]);
-            y2[e] = round_bf(x2[e] * c[e]) + round_bf(x1[e] * sn[e]);
+            y1[e] = rope_lo(x1[e], x2[e], c[e], sn[e]);
+            y2[e] = rope_hi(x2[e], x1[e], c[e], sn[e]);
         }
         *(u32x4*)p1 = pack8(y1);
         *(u32x4*)p2 = pack8(y2);
@@ -98,7 +98,7 @@ MM_DEV void rope_kv_append_f8_row(uint16_t* __restrict__ row, int pos, int Hq, i
         unpack8(*(const u32x4*)(sin_t + (int64_t)pos * d + v8), sn);
 #pragma unroll
         for (int e = 0; e < 8; ++e)
-            y[e] = lo ? round_bf(x[e] * c[e]) + round_bf(-xp[e] * sn[e]) : round_bf(x[e] * c[e]) + round_bf(xp[e] * sn[e]);
+            y[e] = lo ? rope_lo(x[e], xp[e], c[e], sn[e]) : rope_hi(x[e], xp[e], c[e], sn[e]);
         unpack8(pack8(y), x);                                // the bf16 row the bf16 kernel would have cached
     }
     if (!on) {

@@ -11,9 +11,9 @@
 //   * v_cvt_scalef32_pk_bf16_fp4 turns one byte (two e2m1 values) and the group scale (an fp32 whose exponent field is S) into the packed
 //     bf16 pair that v_dot2c_f32_bf16 (up to four rows) and v_mfma_f32_16x16x32_bf16 (5 .. 16 rows) take: ONE widening instruction per
 //     two weights, nothing is multiplied after the sum.  x stays bf16.
-//   * the epilogues (bias / GELU / residual; SiLU(g) u; RoPE + cache append) are decode_wq.h's, shared with decode_w8.hip; a fused form
+//   * the epilogues (bias / GELU / residual; SiLU(g) u; RoPE + cache append) are decode_gemv.h's, shared with decode_w8.hip; a fused form
 //     and the launch sequence it replaces run the same stream in the same order: the same bits.
-#include "decode_wq.h"
+#include "decode_gemv.h"
 
 namespace {
 

@@ -10,9 +10,9 @@
 //     memory access, no branch around a prefetch);
 //   * e4m3 -> fp32 is exact and its upper 16 bits ARE the bf16 value: v_cvt_pk_f32_fp8 + one v_perm_b32 per pair of weights gives the
 //     packed bf16 pair that v_dot2c_f32_bf16 (up to four rows) and v_mfma_f32_16x16x32_bf16 (5 .. 16 rows) take.  x stays bf16.
-//   * the epilogues (bias / GELU / residual; SiLU(g) u; RoPE + cache append) are those of decode.hip, applied to scale[n] * sum; a fused
-//     form and the launch sequence it replaces run the same stream in the same order: the same bits.
-#include "decode_wq.h"
+//   * the epilogues (bias / GELU / residual; SiLU(g) u; RoPE + cache append) are decode_gemv.h's, shared with decode.hip, applied to
+//     scale[n] * sum; a fused form and the launch sequence it replaces run the same stream in the same order: the same bits.
+#include "decode_gemv.h"
 
 namespace {
 

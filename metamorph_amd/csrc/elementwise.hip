@@ -66,11 +66,11 @@ __global__ __launch_bounds__(NT) void rope_qk_kernel(uint16_t* __restrict__ qkv,
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             if (!inverse) {
-                y1[e] = round_bf(x1[e] * c[e]) + round_bf(-x2[e] * s[e]);
-                y2[e] = round_bf(x2[e] * c[e]) + round_bf(x1[e] * s[e]);
+                y1[e] = rope_lo(x1[e], x2[e], c[e], s[e]);
+                y2[e] = rope_hi(x2[e], x1[e], c[e], s[e]);
             } else {
-                y1[e] = x1[e] * c[e] + x2[e] * s[e];
-                y2[e] = x2[e] * c[e] - x1[e] * s[e];
+                y1[e] = rope_inv_lo(x1[e], x2[e], c[e], s[e]);
+                y2[e] = rope_inv_hi(x2[e], x1[e], c[e], s[e]);
             }
         }
         *(u32x4*)p1 = pack8(y1);
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(NT) void swiglu_fwd_kernel(const uint16_t* __restri
         unpack8(*(const u32x4*)(gu + row * 2 * I + v * 8), g);
         unpack8(*(const u32x4*)(gu + row * 2 * I + I + v * 8), u);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = round_bf(g[e] / (1.0f + __expf(-g[e]))) * u[e];
+        for (int e = 0; e < 8; ++e) o[e] = swiglu_f(g[e], u[e]);
         *(u32x4*)(act + row * I + v * 8) = pack8(o);
     }
 }
@@ -103,13 +103,7 @@ __global__ __launch_bounds__(NT) void swiglu_bwd_kernel(const uint16_t* __restri
         unpack8(*(const u32x4*)(gu + row * 2 * I + I + v * 8), u);
         unpack8(*(const u32x4*)(dact + row * I + v * 8), da);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float sg = 1.0f / (1.0f + __expf(-g[e]));
-            const float silu = g[e] * sg;
-            a[e] = round_bf(silu) * u[e];
-            du[e] = da[e] * round_bf(silu);
-            dg[e] = da[e] * u[e] * (sg * (1.0f + g[e] * (1.0f - sg)));
-        }
+        for (int e = 0; e < 8; ++e) swiglu_bwd_f(g[e], u[e], da[e], dg[e], du[e], a[e]);
         *(u32x4*)(dgu + row * 2 * I + v * 8) = pack8(dg);
         *(u32x4*)(dgu + row * 2 * I + I + v * 8) = pack8(du);
         if (act) *(u32x4*)(act + row * I + v * 8) = pack8(a);
@@ -133,13 +127,7 @@ __global__ __launch_bounds__(256) void swiglu_bwd_t_kernel(const uint16_t* __res
         unpack8(*(const u32x4*)(gu + row * 2 * I + I + c0 + c), u);
         unpack8(*(const u32x4*)(dact + row * I + c0 + c), da);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float sg = 1.0f / (1.0f + __expf(-g[e]));
-            const float silu = g[e] * sg;
-            a[e] = round_bf(silu) * u[e];
-            du[e] = da[e] * round_bf(silu);
-            dg[e] = da[e] * u[e] * (sg * (1.0f + g[e] * (1.0f - sg)));
-        }
+        for (int e = 0; e < 8; ++e) swiglu_bwd_f(g[e], u[e], da[e], dg[e], du[e], a[e]);
         const u32x4 pg = pack8(dg), pu = pack8(du), pa = pack8(a);
         *(u32x4*)(dgu + row * 2 * I + c0 + c) = pg;
         *(u32x4*)(dgu + row * 2 * I + I + c0 + c) = pu;

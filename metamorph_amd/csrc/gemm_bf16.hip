@@ -23,7 +23,7 @@ namespace {
 // Epilogue of the fused gate|up GEMM (mm355_gemm_swiglu_bf16): a wave's 64 tile columns are 32 gate channels followed by the SAME 32
 // up channels (the B tile is staged from two row ranges of the fused weight, see gemm_pp_tile<.., SWI>), so after the staging slab a
 // lane finds gate and up of a channel 32 floats apart in its row: gu goes out as two 64-B runs per wave row (gate block at column ch,
-// up block at column I + ch) and act = bf(silu(bf(g))) * bf(u) -- the arithmetic of swiglu_fwd_kernel on the bf16-rounded values, bit
+// up block at column I + ch) and act = bf(silu(bf(g))) * bf(u) -- swiglu_f (mm355_common.h), which swiglu_fwd_kernel applies too, on the bf16-rounded values, bit
 // for bit -- as one 16-B store per lane.  a.C = gu [M][ldc], a.res = act [M][ldr], a.res_mod = I.
 MM_DEV void gemm_epilogue_swiglu(f32x4 (&acc)[8][4], const GemmArgs& a, unsigned char* smem, int m0, int tn, int wm, int wn, int wave, int lane) {
     constexpr int TN = 64;
@@ -60,7 +60,7 @@ MM_DEV void gemm_epilogue_swiglu(f32x4 (&acc)[8][4], const GemmArgs& a, unsigned
             unpack8(gp, gb);
             unpack8(up, ub);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = round_bf(gb[e] / (1.0f + __expf(-gb[e]))) * ub[e];
+            for (int e = 0; e < 8; ++e) o[e] = swiglu_f(gb[e], ub[e]);
             *(u32x4*)(act + (int64_t)grow * a.ldr + ch) = pack8(o);
         }
     }
@@ -68,7 +68,7 @@ MM_DEV void gemm_epilogue_swiglu(f32x4 (&acc)[8][4], const GemmArgs& a, unsigned
 
 // Epilogue of the fused down_proj input-gradient GEMM + SwiGLU backward (mm355_gemm_swiglu_bwd_bf16).  The accumulators are
 // d act = dY . Wd of a 256 x 256 (rows x channels) tile; rounded to bf16 they are exactly what mm355_gemm_bf16 would have stored and
-// mm355_swiglu_bwd_t re-read, and the same arithmetic follows: with g / u from gu [M][2 I] (a.res)
+// mm355_swiglu_bwd_t re-read, and the same function follows (swiglu_bwd_f, mm355_common.h): with g / u from gu [M][2 I] (a.res)
 //     a = bf(silu(g)) u,   du = da bf(silu(g)),   dg = da u sigma(g) (1 + g (1 - sigma(g)))
 // go out row-major as dgu [M][2 I] (a.C) AND contraction-major as actT [I][ld_aux] (aux0), dguT [2 I][ld_aux] (aux1) -- what the two
 // weight-gradient GEMMs read -- through a wave-private LDS tile: 32 rows x 64 channels x 3 quantities per flush, 16-B transposed
@@ -128,13 +128,7 @@ MM_DEV void gemm_epilogue_swiglu_bwd(f32x4 (&acc)[8][4], const GemmArgs& a, unsi
                 unpack8(gq[i % PF][j8], g);
                 unpack8(uq[i % PF][j8], u);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float sg = 1.0f / (1.0f + __expf(-g[e]));
-                    const float silu = g[e] * sg;
-                    av[e] = round_bf(silu) * u[e];
-                    du[e] = da[e] * round_bf(silu);
-                    dg[e] = da[e] * u[e] * (sg * (1.0f + g[e] * (1.0f - sg)));
-                }
+                for (int e = 0; e < 8; ++e) swiglu_bwd_f(g[e], u[e], da[e], dg[e], du[e], av[e]);
                 const u32x4 pg = pack8(dg), pu = pack8(du), pa = pack8(av);
                 if (live) {
                     const int64_t wo = (int64_t)grow * a.ldc + c_wave + c;
@@ -178,7 +172,7 @@ MM_DEV void gemm_epilogue_swiglu_bwd(f32x4 (&acc)[8][4], const GemmArgs& a, unsi
 // Epilogue of the fused QKV projection + RoPE (mm355_gemm_rope_bf16, head size 128).  The B tile is staged from permuted weight rows
 // (gemm_pp_tile<.., ROPE>): a wave's 64 tile columns are d = sub*32 .. +31 (first half of a head) followed by d = 64 + sub*32 .. +31 (second
 // half), so the rotation partners x1 = x[d], x2 = x[d + 64] of a row sit 32 floats apart in the wave's staging slab.  Both are rounded to
-// bf16 first (what mm355_gemm_bf16 would have stored) and rotated with the arithmetic of rope_qk_kernel, bit for bit:
+// bf16 first (what mm355_gemm_bf16 would have stored) and rotated with rope_lo / rope_hi (mm355_common.h), which rope_qk_kernel applies too, bit for bit:
 //     y1 = bf(bf(x1 c) + bf(-x2 s)),  y2 = bf(bf(x2 c) + bf(x1 s)),  c / s = cos / sin[position][d]
 // for the columns below a.res_mod (the q and k blocks); the v block is stored as it is.  a.aux0 / a.aux1 = cos / sin tables [*][128] bf16,
 // a.ld_aux = L (rows per sample), a.bias = optional int32 position offsets per sample.
@@ -221,8 +215,8 @@ MM_DEV void gemm_epilogue_rope(f32x4 (&acc)[8][4], const GemmArgs& a, unsigned c
                 unpack8(*(const u32x4*)(a.aux1 + (int64_t)l * 128 + d1), sn);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    y1[e] = round_bf(x1[e] * c[e]) + round_bf(-x2[e] * sn[e]);
-                    y2[e] = round_bf(x2[e] * c[e]) + round_bf(x1[e] * sn[e]);
+                    y1[e] = rope_lo(x1[e], x2[e], c[e], sn[e]);
+                    y2[e] = rope_hi(x2[e], x1[e], c[e], sn[e]);
                 }
                 w1 = pack8(y1); w2 = pack8(y2);
             }
@@ -1019,7 +1013,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_norm_kernel(const float* __
         }
     }
 }
-// act[m][c] = SiLU(g) * u of the bf16-rounded sums g = column c, u = column I + c (swiglu_fwd_kernel's arithmetic)
+// act[m][c] = SiLU(g) * u of the bf16-rounded sums g = column c, u = column I + c (swiglu_f, as swiglu_fwd_kernel)
 __global__ __launch_bounds__(256) void splitk_reduce_swiglu_kernel(const float* __restrict__ part, int S, int M, int I, uint16_t* __restrict__ act,
                                                                    int64_t ld_act) {
     const int iv = I >> 3, N = 2 * I;
@@ -1033,7 +1027,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_swiglu_kernel(const float* 
         unpack8(pack8(g), g);
         unpack8(pack8(u), u);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = round_bf(g[e] / (1.0f + __expf(-g[e]))) * u[e];
+        for (int e = 0; e < 8; ++e) o[e] = swiglu_f(g[e], u[e]);
         *(u32x4*)(act + m * ld_act + c) = pack8(o);
     }
 }
@@ -1054,11 +1048,11 @@ __global__ __launch_bounds__(256) void splitk_reduce_swiglu_tail_kernel(const fl
         }
         g = round_bf(g);
         u = round_bf(u);
-        act[m * ld_act + c] = f2bf(round_bf(g / (1.0f + __expf(-g))) * u);
+        act[m * ld_act + c] = f2bf(swiglu_f(g, u));
     }
 }
 // q|k|v sums of one new row per sequence: q rotated at positions[m] -> qkv[m][0 .. Hq d), rotated k and v -> cache row positions[m]
-// (rope_kv_append_kernel's arithmetic on the bf16-rounded sums; the k | v columns of qkv are not written)
+// (rope_lo / rope_hi on the bf16-rounded sums, as rope_kv_append_kernel; the k | v columns of qkv are not written)
 __global__ __launch_bounds__(256) void splitk_reduce_rope_append_kernel(const float* __restrict__ part, int S, int M, int Hq, int Hkv, int d,
                                                                         uint16_t* __restrict__ qkv, int64_t ld, const uint16_t* __restrict__ cos_t,
                                                                         const uint16_t* __restrict__ sin_t, const int32_t* __restrict__ positions,
@@ -1085,8 +1079,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_rope_append_kernel(const fl
             unpack8(*(const u32x4*)(sin_t + (int64_t)pos * d + v * 8), sn);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                y1[e] = round_bf(x1[e] * c[e]) + round_bf(-x2[e] * sn[e]);
-                y2[e] = round_bf(x2[e] * c[e]) + round_bf(x1[e] * sn[e]);
+                y1[e] = rope_lo(x1[e], x2[e], c[e], sn[e]);
+                y2[e] = rope_hi(x2[e], x1[e], c[e], sn[e]);
             }
             const u32x4 o1 = pack8(y1), o2 = pack8(y2);
             if (hd < Hq) {

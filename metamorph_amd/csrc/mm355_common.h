@@ -118,6 +118,33 @@ MM_DEV float gelu_tanh_grad(float x) {
     return 0.5f * (1.0f + t) + 0.5f * x * (1.0f - t * t) * du;
 }
 
+// ---- THE definitions of the arithmetic a fused kernel shares with the launch sequence it replaces (the tests compare bits): every
+// kernel that applies SwiGLU or the forward rotation calls these; the 8-wide loops and the packing stay with the callers.
+// SwiGLU forward: bf16(SiLU(g)) * u, the caller rounds the product
+MM_DEV float swiglu_f(float g, float u) { return round_bf(g / (1.0f + __expf(-g))) * u; }
+// SwiGLU backward: (g, u, dact) -> dg, du and the recomputed act, each rounded by the caller
+MM_DEV void swiglu_bwd_f(float g, float u, float dact, float& dg, float& du, float& act) {
+    const float sg = 1.0f / (1.0f + __expf(-g));
+    const float silu = g * sg;
+    act = round_bf(silu) * u;
+    du = dact * round_bf(silu);
+    dg = dact * u * (sg * (1.0f + g * (1.0f - sg)));
+}
+// The forward rotation in HF rounding order, bf(bf(x c) + bf(-+ partner s)): x in the first half of a head (partner d/2 above it) takes
+// rope_lo, x in the second half (partner d/2 below) rope_hi; the caller rounds the sum
+MM_DEV float rope_lo(float x, float partner, float c, float s) { return round_bf(x * c) + round_bf(-partner * s); }
+MM_DEV float rope_hi(float x, float partner, float c, float s) { return round_bf(x * c) + round_bf(partner * s); }
+// The inverse rotation of a gradient (rope_qk_kernel): dx1 = dy1 c + dy2 s with the second product fused into the sum, dx2 = dy2 c - dy1 s
+// with both products rounded -- written out, so that the bits do not hang on what the compiler chooses to contract
+MM_DEV float rope_inv_lo(float dy, float partner, float c, float s) {
+#pragma clang fp contract(off)
+    return fmaf(partner, s, dy * c);
+}
+MM_DEV float rope_inv_hi(float dy, float partner, float c, float s) {
+#pragma clang fp contract(off)
+    return dy * c - partner * s;
+}
+
 static inline int mm_launch_status() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? MM355_OK : MM355_ELAUNCH;

@@ -964,7 +964,7 @@ def test_batched_gemv_x_window_protocol():
 
 
 def test_fused_decode_gemv_row_ownership_is_a_partition():
-    """csrc/decode.hip, unit_rows<MODE> (gemv_deep_kernel, gemv_mfma_kernel): a wave owns four-row units chosen so that its epilogue finds its partners in its own
+    """csrc/decode_gemv.h, unit_rows<MODE> (every decode GEMV kernel): a wave owns four-row units chosen so that its epilogue finds its partners in its own
     accumulators -- MODE 1 (SwiGLU): gate rows c, c + 1 and up rows I + c, I + c + 1; MODE 2 (RoPE + cache append): the rotation partners
     j, j + 1, j + d/2, j + 1 + d/2 of one q / k head, four neighbours of a v head.  The formulas, restated here, must cover every weight
     row exactly once for the geometries the models use (a row owned twice or never would be a silent wrong answer only for some heads)."""

@@ -1241,6 +1241,31 @@ def test_gemv_rejects_many_rows(ops):
         ops.gemv(rnd(17, 64, seed=1).to(DEV), rnd(16, 64, seed=2).to(DEV))
 
 
+@pytest.mark.parametrize("M", [1, 2, 4, 5, 16])
+@pytest.mark.parametrize("fmt", ["bf16", "w8", "w4"])
+def test_gemv_plain_epilogue_order_and_flags_together(ops, fmt, M):
+    """The plain epilogue of every decode GEMV is one chain: sum (+ bias) (GELU) (+ residual) -> fp32 or bf16.  With s the call's own fp32
+    output, bias + residual in bf16 is ((s + bias) + residual) rounded once -- single IEEE fp32 adds and one RNE rounding, which the host
+    reproduces exactly -- and bias + erf-GELU + residual is close to gelu(s + bias) + residual (test_gemv's bounds for "gemv bias+gelu").
+    Residual entries are about 1, so another order (a residual inside the GELU, a bias behind it) is far outside either check.
+    N = 40: ten 4-row units, the third group of 16 MFMA rows half empty; M = 1, 2, 4: the vector-ALU kernel's row counts, 5, 16: the MFMA
+    form.  K = 520 (bf16) ends in a partial k-step; the quantised formats only take K % 16 == 0 (e4m3) and K % 32 == 0 (MXFP4), so they
+    run the next K they accept, 528 and 544, which end in a partial step of theirs (64 and 128 columns) as well."""
+    N, K = 40, {"bf16": 520, "w8": 528, "w4": 544}[fmt]
+    x, w, b, r = rnd(M, K, seed=1).to(DEV), rnd(N, K, seed=2, scale=0.05).to(DEV), rnd(N, seed=3).to(DEV), rnd(M, N, seed=4).to(DEV)
+    if fmt == "bf16":
+        run = lambda **kw: ops.gemv(x, w, **kw)
+    elif fmt == "w8":
+        q, sc = ops.quantize_w8(w)
+        run = lambda **kw: ops.gemv_w8(x, q, sc, **kw)
+    else:
+        q, sc = ops.quantize_w4(w)
+        run = lambda **kw: ops.gemv_w4(x, q, sc, **kw)
+    s = run(out=torch.empty(M, N, device=DEV, dtype=torch.float32))
+    assert torch.equal(run(bias=b, residual=r), ((s + b.float()) + r.float()).bfloat16()), (fmt, M)
+    close(run(bias=b, residual=r, gelu="erf"), R.gelu_erf(s.cpu() + b.float().cpu()) + r.float().cpu(), 1e-2, 0.02, f"gemv {fmt} bias+gelu+residual")
+
+
 @pytest.mark.parametrize("M", [17, 32, 64, 130])
 def test_gemm_splitk_fused_reduce_launches_equal_the_launch_sequences(ops, M):
     """mm355_gemm_splitk_{norm,swiglu,rope_append}_bf16 (what follows a split projection folded into its reduce launch) against
