@@ -1055,6 +1055,11 @@ def layernorm_bwd(dy, x, w, eps, dw_f32, db_f32, dres=None, dx=None):
 # ------------------------------------------------------------------------------------------------ rope / attention
 
 def rope_table(L, d, theta, device):
+    """cos / sin [L, d] bf16 of the unscaled RoPE from theta alone (mm355_rope_table): tests, tools and benchmarks.  The inverse frequencies
+    come from powf on the device and may differ from HF's host-computed inv_freq by an ulp, which the position multiplies: against
+    rope_table_freq on HF's inv_freq, 0.1 % of the entries differ below row 4096, 1.7 % from row 65536 on (3 % at row 131071, up to two bf16
+    steps; tests/test_kv_long_context_gpu.py prints the figures).  Guaranteed: both halves of a row equal, row 0 exact.  The model builds its
+    tables with rope_table_freq (metamorph_amd.rope), which is pinned to HF's arithmetic up to row 131071."""
     cos = torch.empty((L, d), device=device, dtype=BF16)
     sin = torch.empty((L, d), device=device, dtype=BF16)
     _chk_dev(cos)
