@@ -20,13 +20,6 @@
 // Replaces torch SDPA as driven by HF LlamaModel (reference call site metamorph_llama.py:349-359).
 #include "attn2.h"
 
-// the generated streams; timing-only ablation builds (tools/gen_attn4.py --abl ...) compile with -DATTN4_GEN_DIR=attn4_gen_<name>
-#ifndef ATTN4_GEN_DIR
-#define ATTN4_GEN_DIR attn4_gen
-#endif
-#define ATTN4_STR2(x) #x
-#define ATTN4_STR(x) ATTN4_STR2(x)
-#define ATTN4_INC(f) ATTN4_STR(ATTN4_GEN_DIR/f)
 
 namespace attn4 {
 using namespace attn2;
@@ -60,13 +53,6 @@ template <bool SAFE>
 __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) void fwd_kernel(Args a) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[4 * TILE];
     asm volatile("" ::: "v255", "a255");                   // the stream's literal registers: the descriptor must allocate the whole file
-#ifdef MM355_ATTN4_TIMING                                    // TIMING-ONLY build (tools/): phase stamps of waves 0 and 3 overwrite the block's lse rows
-    const long long tm0 = __builtin_readcyclecounter();
-    long long tm1 = 0, tm2 = 0, tm3 = 0, tm4 = 0, tm5 = 0;
-#define ATTN4_STAMP(x) x = __builtin_readcyclecounter()
-#else
-#define ATTN4_STAMP(x) do {} while (0)
-#endif
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane & 31, hi = lane >> 5;
@@ -118,7 +104,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) void f
     {
         const uint16_t* qp0_ = a.q + (row_base + min(qw0 + c, L - 1)) * a.ld_q + (int64_t)hq * 128 + hi * 8;
         const uint16_t* qp1_ = a.q + (row_base + min(qw0 + 32 + c, L - 1)) * a.ld_q + (int64_t)hq * 128 + hi * 8;
-#include ATTN4_INC(q_load.inc)
+#include "attn4_gen/q_load.inc"
     }
     bool do_bar = true;
     int kdst, vdst;
@@ -131,7 +117,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) void f
     rsK = ATTN4_TILE_RSRC(kbase, 1); kdst = TILE + wave * 4096;
 #pragma unroll
     for (int i = 0; i < 4; ++i) { ATTN4_DMA_K(i); }
-#include ATTN4_INC(zero_o.inc)
+#include "attn4_gen/zero_o.inc"
     float LS[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};   // [qb][r & 3] partial row sums of this lane's keys
     float MX[2][2], rm_[2], rt_[2];
     uint64_t grow_ = 0;
@@ -166,7 +152,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) void f
     }
     // Q fragments into the accumulator file: d-steps 0 and 1 here (the 16 row loads precede the 12 DMA pieces in the memory queue), 2..7 inside the head
     asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-#include ATTN4_INC(q_pre01.inc)
+#include "attn4_gen/q_pre01.inc"
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
 
@@ -175,55 +161,51 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) void f
     rsK = ATTN4_TILE_RSRC(kbase, s__ + 2); rsV = ATTN4_TILE_RSRC(vbase, s__ + 2); \
     kdst = (s__ & 1) * TILE + wave * 4096; vdst = VRING + (s__ & 1) * TILE + wave * 4096; } while (0)
 
-    ATTN4_STAMP(tm1);
     if (tw >= 0) {
         bool mask_next = tw == 0;
         ATTN4_STEP_VARS(-1);
         if constexpr (SAFE) {
-#include ATTN4_INC(safe_head.inc)
+#include "attn4_gen/safe_head.inc"
         } else {
-#include ATTN4_INC(head.inc)
+#include "attn4_gen/head.inc"
         }
-        ATTN4_STAMP(tm2);
         int t = 0;
         for (;;) {
             if (t >= tw) break;
             mask_next = t + 1 == tw;
             ATTN4_STEP_VARS(t);
             if constexpr (SAFE) {
-#include ATTN4_INC(safe_loop0.inc)
+#include "attn4_gen/safe_loop0.inc"
             } else {
-#include ATTN4_INC(loop0.inc)
+#include "attn4_gen/loop0.inc"
             }
             ++t;
             if (t >= tw) break;
             mask_next = t + 1 == tw;
             ATTN4_STEP_VARS(t);
             if constexpr (SAFE) {
-#include ATTN4_INC(safe_loop1.inc)
+#include "attn4_gen/safe_loop1.inc"
             } else {
-#include ATTN4_INC(loop1.inc)
+#include "attn4_gen/loop1.inc"
             }
             ++t;
         }
-        ATTN4_STAMP(tm3);
         do_bar = tw <= T - 2;
         ATTN4_STEP_VARS(tw);
         if (tw & 1) {
             if constexpr (SAFE) {
-#include ATTN4_INC(safe_tail1.inc)
+#include "attn4_gen/safe_tail1.inc"
             } else {
-#include ATTN4_INC(tail1.inc)
+#include "attn4_gen/tail1.inc"
             }
         } else {
             if constexpr (SAFE) {
-#include ATTN4_INC(safe_tail0.inc)
+#include "attn4_gen/safe_tail0.inc"
             } else {
-#include ATTN4_INC(tail0.inc)
+#include "attn4_gen/tail0.inc"
             }
         }
     }
-    ATTN4_STAMP(tm4);
     // a wave that is done keeps moving its quarter of every remaining tile and meets the barriers of steps <= T - 2
     do_bar = true;
     for (int s = tw < 0 ? -1 : tw + 1; s <= T - 2; ++s) {
@@ -238,7 +220,6 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) void f
     }
     asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // last P V MFMAs, stray DMA
     __syncthreads();                                         // every wave is done with the rings: they become the output staging area
-    ATTN4_STAMP(tm5);
 
     // epilogue: O = O^T / l -> bf16 [q][d] in this wave's 16 KiB (16-B chunk ^ (row & 15)) -> row-contiguous 16-B stores
     unsigned char* so = smem + wave * TILE;
@@ -251,7 +232,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) void f
 #pragma unroll
         for (int db_ = 0; db_ < 4; ++db_) {
             float x_[16];
-#include ATTN4_INC(epi_read.inc)
+#include "attn4_gen/epi_read.inc"
 #pragma unroll
             for (int i4 = 0; i4 < 4; ++i4) {
                 u32x2 w;
@@ -272,14 +253,6 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) void f
         if (qg < L) *(u32x4*)(o_base + (int64_t)qg * a.ld_o + j * 8) = *(const u32x4*)(so + r * 256 + ((j ^ (r & 15)) << 4));
     }
     if (a.dbg && lane == 0) a.dbg[(((int64_t)b * a.Hq + hq) * ((L + 255) / 256) + xb) * 4 + wave] = nresc_;   // [B][Hq][blocks][4 waves], zeroed by the caller
-#ifdef MM355_ATTN4_TIMING
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const long long tm6 = __builtin_readcyclecounter();
-    if (lane == 0 && (wave == 0 || wave == 3) && q0 + 64 <= L) {
-        long long* w = (long long*)(lse_base + q0) + (wave == 3 ? 8 : 0);
-        w[0] = tm1 - tm0; w[1] = tm2 - tm1; w[2] = tm3 - tm2; w[3] = tm4 - tm3; w[4] = tm5 - tm4; w[5] = tm6 - tm5; w[6] = tw; w[7] = T;
-    }
-#endif
 }
 
 }  // namespace attn4

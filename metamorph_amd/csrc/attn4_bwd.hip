@@ -16,13 +16,6 @@
 // Replaces the backward of torch SDPA as driven by HF LlamaModel (reference call site metamorph_llama.py:349-359).
 #include "attn2.h"
 
-#ifndef ATTN4B_GEN_DIR
-#define ATTN4B_GEN_DIR attn4_bwd_gen
-#endif
-#define ATTN4B_STR2(x) #x
-#define ATTN4B_STR(x) ATTN4B_STR2(x)
-#define ATTN4B_INC(f) ATTN4B_STR(ATTN4B_GEN_DIR/f)
-
 namespace attn4b {
 using namespace attn2;
 
@@ -65,13 +58,6 @@ template <bool SAFE>
 __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(96))) void dkdv_kernel(Args a, const float* __restrict__ nstat) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     asm volatile("" ::: "v255", "a255");
-#ifdef MM355_ATTN4_TIMING                                    // TIMING-ONLY build (tools/): phase stamps of wave 0 overwrite the block's first dk row
-    const long long tm0 = __builtin_readcyclecounter();
-    long long tm1 = 0, tm2 = 0, tm3 = 0, tm4 = 0;
-#define BWD_STAMP(x) x = __builtin_readcyclecounter()
-#else
-#define BWD_STAMP(x) do {} while (0)
-#endif
     constexpr int NDMA = 9;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -165,95 +151,91 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(96))) void d
         const int key = min(kw0 + c, L - 1);
         const uint16_t* p0_ = a.k + (row_base + key) * a.ld_k + (int64_t)hk * 128 + hi * 8;
         const uint16_t* p1_ = a.v + (row_base + key) * a.ld_k + (int64_t)hk * 128 + hi * 8;
-#include ATTN4B_INC(kv_pers_load.inc)
+#include "attn4_bwd_gen/kv_pers_load.inc"
     }
-#include ATTN4B_INC(kv_zero.inc)
+#include "attn4_bwd_gen/kv_zero.inc"
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     {
         float t1_;
-#include ATTN4B_INC(kv_pers_place.inc)
+#include "attn4_bwd_gen/kv_pers_place.inc"
     }
     __builtin_amdgcn_s_barrier();
 
-    BWD_STAMP(tm1);
     KV_TILE_VARS(2);                                         // the head moves tile 2
     if constexpr (SAFE) {
-#include ATTN4B_INC(kv_safe_head.inc)
+#include "attn4_bwd_gen/kv_safe_head.inc"
     } else {
-#include ATTN4B_INC(kv_head.inc)
+#include "attn4_bwd_gen/kv_head.inc"
     }
-    BWD_STAMP(tm2);
     int u = 0;
     for (;;) {
         if (u >= n_tot - 1) break;
         KV_TILE_VARS(3); KV_MASK_VARS();
         if constexpr (SAFE) {
-#include ATTN4B_INC(kv_safe_loop0.inc)
+#include "attn4_bwd_gen/kv_safe_loop0.inc"
         } else {
-#include ATTN4B_INC(kv_loop0.inc)
+#include "attn4_bwd_gen/kv_loop0.inc"
         }
         ++u;
         if (u >= n_tot - 1) break;
         KV_TILE_VARS(0); KV_MASK_VARS();
         if constexpr (SAFE) {
-#include ATTN4B_INC(kv_safe_loop1.inc)
+#include "attn4_bwd_gen/kv_safe_loop1.inc"
         } else {
-#include ATTN4B_INC(kv_loop1.inc)
+#include "attn4_bwd_gen/kv_loop1.inc"
         }
         ++u;
         if (u >= n_tot - 1) break;
         KV_TILE_VARS(1); KV_MASK_VARS();
         if constexpr (SAFE) {
-#include ATTN4B_INC(kv_safe_loop2.inc)
+#include "attn4_bwd_gen/kv_safe_loop2.inc"
         } else {
-#include ATTN4B_INC(kv_loop2.inc)
+#include "attn4_bwd_gen/kv_loop2.inc"
         }
         ++u;
         if (u >= n_tot - 1) break;
         KV_TILE_VARS(2); KV_MASK_VARS();
         if constexpr (SAFE) {
-#include ATTN4B_INC(kv_safe_loop3.inc)
+#include "attn4_bwd_gen/kv_safe_loop3.inc"
         } else {
-#include ATTN4B_INC(kv_loop3.inc)
+#include "attn4_bwd_gen/kv_loop3.inc"
         }
         ++u;
     }
-    BWD_STAMP(tm3);
     KV_MASK_VARS();
     switch (u & 3) {
     case 0:
         if constexpr (SAFE) {
-#include ATTN4B_INC(kv_safe_tail0.inc)
+#include "attn4_bwd_gen/kv_safe_tail0.inc"
         } else {
-#include ATTN4B_INC(kv_tail0.inc)
+#include "attn4_bwd_gen/kv_tail0.inc"
         }
         break;
     case 1:
         if constexpr (SAFE) {
-#include ATTN4B_INC(kv_safe_tail1.inc)
+#include "attn4_bwd_gen/kv_safe_tail1.inc"
         } else {
-#include ATTN4B_INC(kv_tail1.inc)
+#include "attn4_bwd_gen/kv_tail1.inc"
         }
         break;
     case 2:
         if constexpr (SAFE) {
-#include ATTN4B_INC(kv_safe_tail2.inc)
+#include "attn4_bwd_gen/kv_safe_tail2.inc"
         } else {
-#include ATTN4B_INC(kv_tail2.inc)
+#include "attn4_bwd_gen/kv_tail2.inc"
         }
         break;
     default:
         if constexpr (SAFE) {
-#include ATTN4B_INC(kv_safe_tail3.inc)
+#include "attn4_bwd_gen/kv_safe_tail3.inc"
         } else {
-#include ATTN4B_INC(kv_tail3.inc)
+#include "attn4_bwd_gen/kv_tail3.inc"
         }
         break;
     }
 #undef BWD_DMA
     asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();                                         // the ring becomes the output staging area
-    BWD_STAMP(tm4);
 
     // epilogue: lane (key c, hi) holds X^T[d = db*32 + 8*(r >> 2) + 4*hi + (r & 3)][key]; dK *= scale, optional inverse RoPE on the
     // bf16-rounded dK (partner column d + 64 = block db + 2 of the same lane), bf16 [key][d] through this wave's 8 KiB -> row stores
@@ -269,13 +251,13 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(96))) void d
                 float x_[4], lo_[4], hi_[4];
                 {
                     const int db_ = dbp;
-#include ATTN4B_INC(kv_acc_read.inc)
+#include "attn4_bwd_gen/kv_acc_read.inc"
 #pragma unroll
                     for (int r = 0; r < 4; ++r) lo_[r] = x_[r] * sc;
                 }
                 {
                     const int db_ = dbp + 2;
-#include ATTN4B_INC(kv_acc_read.inc)
+#include "attn4_bwd_gen/kv_acc_read.inc"
 #pragma unroll
                     for (int r = 0; r < 4; ++r) hi_[r] = x_[r] * sc;
                 }
@@ -316,15 +298,6 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(96))) void d
                 *(u32x4*)((which_ ? a.dv : a.dk) + (row_base + key) * a.ld_dkv + (int64_t)hk * 128 + j * 8) = val;
             }
         }
-#ifdef MM355_ATTN4_TIMING
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const long long tm5 = __builtin_readcyclecounter();
-    __syncthreads();
-    if (tid == 0) {
-        long long* w = (long long*)(a.dk + (row_base + kv0) * a.ld_dkv + (int64_t)hk * 128);
-        w[0] = tm1 - tm0; w[1] = tm2 - tm1; w[2] = tm3 - tm2; w[3] = tm4 - tm3; w[4] = tm5 - tm4; w[5] = n_tot;
-    }
-#endif
 }
 
 // ================================================================================================ dQ
@@ -407,57 +380,57 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(80))) void d
         const int qc = min(qg, L - 1);
         const uint16_t* p0_ = a.q + (row_base + qc) * a.ld_q + (int64_t)hq * 128 + hi * 8;
         const uint16_t* p1_ = a.d_o + (row_base + qc) * a.ld_o + (int64_t)hq * 128 + hi * 8;
-#include ATTN4B_INC(q_pers_load.inc)
+#include "attn4_bwd_gen/q_pers_load.inc"
         const float nl_ = -a.lse_in[((int64_t)b * a.Hq + hq) * L + qc] * (1.0f / a.scale);
         const float nd_ = -a.delta[((int64_t)b * a.Hq + hq) * L + qc];
-#include ATTN4B_INC(q_tuple_write.inc)
+#include "attn4_bwd_gen/q_tuple_write.inc"
     }
-#include ATTN4B_INC(q_zero.inc)
+#include "attn4_bwd_gen/q_zero.inc"
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     {
         float t0_, t1_;
-#include ATTN4B_INC(q_pers_place.inc)
+#include "attn4_bwd_gen/q_pers_place.inc"
     }
     __builtin_amdgcn_s_barrier();
 
     Q_TILE_VARS(2);
     if constexpr (SAFE) {
-#include ATTN4B_INC(q_safe_head.inc)
+#include "attn4_bwd_gen/q_safe_head.inc"
     } else {
-#include ATTN4B_INC(q_head.inc)
+#include "attn4_bwd_gen/q_head.inc"
     }
     int u = 0;
     for (;;) {
         if (u >= n_tot - 1) break;
         Q_TILE_VARS(3); Q_MASK_VARS();
         if constexpr (SAFE) {
-#include ATTN4B_INC(q_safe_loop0.inc)
+#include "attn4_bwd_gen/q_safe_loop0.inc"
         } else {
-#include ATTN4B_INC(q_loop0.inc)
+#include "attn4_bwd_gen/q_loop0.inc"
         }
         ++u;
         if (u >= n_tot - 1) break;
         Q_TILE_VARS(0); Q_MASK_VARS();
         if constexpr (SAFE) {
-#include ATTN4B_INC(q_safe_loop1.inc)
+#include "attn4_bwd_gen/q_safe_loop1.inc"
         } else {
-#include ATTN4B_INC(q_loop1.inc)
+#include "attn4_bwd_gen/q_loop1.inc"
         }
         ++u;
         if (u >= n_tot - 1) break;
         Q_TILE_VARS(1); Q_MASK_VARS();
         if constexpr (SAFE) {
-#include ATTN4B_INC(q_safe_loop2.inc)
+#include "attn4_bwd_gen/q_safe_loop2.inc"
         } else {
-#include ATTN4B_INC(q_loop2.inc)
+#include "attn4_bwd_gen/q_loop2.inc"
         }
         ++u;
         if (u >= n_tot - 1) break;
         Q_TILE_VARS(2); Q_MASK_VARS();
         if constexpr (SAFE) {
-#include ATTN4B_INC(q_safe_loop3.inc)
+#include "attn4_bwd_gen/q_safe_loop3.inc"
         } else {
-#include ATTN4B_INC(q_loop3.inc)
+#include "attn4_bwd_gen/q_loop3.inc"
         }
         ++u;
     }
@@ -465,30 +438,30 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(80))) void d
     switch (u & 3) {
     case 0:
         if constexpr (SAFE) {
-#include ATTN4B_INC(q_safe_tail0.inc)
+#include "attn4_bwd_gen/q_safe_tail0.inc"
         } else {
-#include ATTN4B_INC(q_tail0.inc)
+#include "attn4_bwd_gen/q_tail0.inc"
         }
         break;
     case 1:
         if constexpr (SAFE) {
-#include ATTN4B_INC(q_safe_tail1.inc)
+#include "attn4_bwd_gen/q_safe_tail1.inc"
         } else {
-#include ATTN4B_INC(q_tail1.inc)
+#include "attn4_bwd_gen/q_tail1.inc"
         }
         break;
     case 2:
         if constexpr (SAFE) {
-#include ATTN4B_INC(q_safe_tail2.inc)
+#include "attn4_bwd_gen/q_safe_tail2.inc"
         } else {
-#include ATTN4B_INC(q_tail2.inc)
+#include "attn4_bwd_gen/q_tail2.inc"
         }
         break;
     default:
         if constexpr (SAFE) {
-#include ATTN4B_INC(q_safe_tail3.inc)
+#include "attn4_bwd_gen/q_safe_tail3.inc"
         } else {
-#include ATTN4B_INC(q_tail3.inc)
+#include "attn4_bwd_gen/q_tail3.inc"
         }
         break;
     }
@@ -508,13 +481,13 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(80))) void d
             float x_[4], lo_[4], hi_[4];
             {
                 const int db_ = dbp;
-#include ATTN4B_INC(q_acc_read.inc)
+#include "attn4_bwd_gen/q_acc_read.inc"
 #pragma unroll
                 for (int r = 0; r < 4; ++r) lo_[r] = x_[r] * keep;
             }
             {
                 const int db_ = dbp + 2;
-#include ATTN4B_INC(q_acc_read.inc)
+#include "attn4_bwd_gen/q_acc_read.inc"
 #pragma unroll
                 for (int r = 0; r < 4; ++r) hi_[r] = x_[r] * keep;
             }

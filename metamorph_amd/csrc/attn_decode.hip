@@ -231,9 +231,6 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(Args a, int ngroup, i
     const int tid = threadIdx.x, sb = tid >> 8, t = tid & 255, lane = tid & 63, wave = t >> 6;
     const int Hq = a.Hq, d = a.d;
     const int kv_len = a.kv_lens[b];
-#if defined(MM355_AD_STOP) && MM355_AD_STOP == 0                                 // TIMING-ONLY builds (tools/build_ad_stop.sh): the kernel cut short after a phase
-    if (kv_len >= 0) return;
-#endif
     const int ngr_live = (kv_len + SB * CH - 1) / (SB * CH);                    // groups that hold keys
     const int rec = d + 2;
     float* wrec = a.ws + (((int64_t)b * Hq + hk * G) * ngroup + grp) * rec;
@@ -328,9 +325,6 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(Args a, int ngroup, i
             }
         }
         __syncthreads();
-#if defined(MM355_AD_STOP) && MM355_AD_STOP == 1
-        if (kv_len >= 0) return;
-#endif
         const int key = k0 + t;
         float sc[G];
         if (active) {
@@ -353,9 +347,6 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(Args a, int ngroup, i
             }
         }
         __syncthreads();
-#if defined(MM355_AD_STOP) && MM355_AD_STOP == 2
-        if (kv_len >= 0) return;
-#endif
         // ---- o = sum_key p[key] V[key]: thread = (16-B chunk of d, key group of 16), batches of NB V rows
         if (active) {
             const int dc = t & 15, kg = t >> 4;
@@ -400,9 +391,6 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(Args a, int ngroup, i
                 }
         }
         __syncthreads();
-#if defined(MM355_AD_STOP) && MM355_AD_STOP == 3
-        if (kv_len >= 0) return;
-#endif
         // ---- the four chunks of this group -> one (m, l, o[d]) per query head, in a fixed order
         for (int i = tid; i < G * d; i += 1024) {
             const int g = i / d, c = i % d;

@@ -157,9 +157,9 @@ __global__ __launch_bounds__(NT) void gemv_kernel(GemvArgs a) {
 //     fq = lane >> 4 holds row fr at k + 8 fq).  WLDS (the product form): a block of 256 columns is loaded COALESCED -- instruction u =
 //     rows 2u and 2u + 1, 512 contiguous bytes each, eight instructions per block, the next block issued before the MFMAs of the current
 //     one -- and re-laid out into fragments through 8.5 KiB of wave-private LDS (eight ds_write_b128 + eight ds_read_b128 per block, rows
-//     544 B apart: conflict-free; a wave's LDS operations execute in order, so no barrier).  The first form loaded straight into the
-//     fragment layout, i.e. 64 contiguous bytes per row and instruction: gate|up at 16 rows 69 us against 53 now, lm_head 275 -> 204
-//     (it remains for the folded-norm variant, whose x rows take the LDS);
+//     544 B apart: conflict-free; a wave's LDS operations execute in order, so no barrier).  Loading straight into the
+//     fragment layout, i.e. 64 contiguous bytes per row and instruction, was slower: gate|up at 16 rows 69 us against 53 now, lm_head
+//     275 -> 204 (only the folded-norm variant, PRENORM, whose x rows take the LDS, still loads its weights that way);
 //   * the x rows are the B operand (row m = fr, zero beyond M): XK (the product form wherever it wins, see the launcher): through
 //     double-buffered LDS windows of one block, staged once per workgroup; else from L2 as they are, or -- PRENORM -- from LDS, where every workgroup
 //     forms bf16(w * bf16(x * rstd)) once (rmsnorm_fwd_kernel's arithmetic and reduction order);
@@ -171,11 +171,14 @@ __global__ __launch_bounds__(NT) void gemv_kernel(GemvArgs a) {
 // on the same weight fragments -- every fragment read back from the re-layout buffer feeds two MFMAs, the x windows hold 32 rows (35 KB),
 // the weights are streamed once.  (Sharing weights between WORKGROUPS through L2 was measured and lost: profiles/r6_gemv_row_groups.log.)
 // Each x row's column of D is computed exactly as in a 16-row call: the bits of the 16-row calls on the row slices.
-template <int MODE, bool PRENORM, int GR, bool WLDS = false, int XK = 0, int RG = 1>
+template <int MODE, bool PRENORM, bool WLDS = false, int XK = 0, int RG = 1>
 __global__ __launch_bounds__(NT) void gemv_mfma_kernel(GemvArgs a) {
-    static_assert(!WLDS || GR == 1, "the LDS re-layout is written for one group of 16 rows per wave");
-    static_assert(XK == 0 || (WLDS && !PRENORM), "x windows come with the coalesced weight stream");
-    static_assert(RG == 1 || (RG == 2 && XK == 1 && GR == 1), "two x row groups: one K range per workgroup, x windows in LDS");
+    static_assert(PRENORM != WLDS, "LDS holds either the folded norm's x rows (PRENORM) or the weights' re-layout (WLDS)");
+    static_assert(PRENORM ? XK == 0 : (XK == 0 || XK == 1 || XK == 2 || XK == 4), "x windows come with the coalesced weight stream, one per K slice");
+    static_assert(RG == 1 || (RG == 2 && XK == 1), "two x row groups: one K range per workgroup, x windows in LDS");
+    // groups of 16 weight rows per wave: always one (see gemv_mfma_shape).  The arrays and loops below keep their [GR] shape because hipcc
+    // schedules every instantiation differently once they are written as scalars (profiles/experiment_prune.md).
+    constexpr int GR = 1;
     constexpr int WROW = 512 + 32;                           // WLDS: bytes per weight row of a 256-column block in LDS (+ 32: every 16-lane group the hardware services together
                                                              // reads 16 different 16-byte slots of the 256-byte bank row; + 16 leaves two-way conflicts: tests/test_host_logic.py)
     __shared__ __attribute__((aligned(16))) unsigned char wl[WLDS ? NT / 64 : 1][WLDS ? 16 * WROW : 16];
@@ -461,20 +464,18 @@ __global__ __launch_bounds__(NT) void gemv_mfma_kernel(GemvArgs a) {
     }
 }
 
-// groups of 16 rows per wave (GR: the x fragments are re-used GR times) and waves per group block (KS: the K split) by the number of weight
-// rows: as many rows per wave as still leaves >= ~1000 waves in flight.  A function of (weight rows, K) only, so a fused kernel and the
-// launch sequence it replaces see the same sums.
-void gemv_mfma_shape(int64_t units, int& gr, int& ks) {
+// waves per group of 16 weight rows (KS: the K split) by the number of weight rows: >= ~1000 waves in flight.  A function of (weight rows, K)
+// only, so a fused kernel and the launch sequence it replaces see the same sums.
+// Measured: two / four groups of 16 rows per wave bought nothing (profiles/r5_gemv_rows.log), so a wave owns one.
+void gemv_mfma_shape(int64_t units, int& ks) {
     const int64_t groups = (units + 3) / 4;
-    gr = 1;                                                  // measured (profiles/r5_gemv_rows.log): 2 / 4 groups per wave buy nothing on the wide shapes (gate|up 67 us
-                                                             // either way: the x traffic was never the limit) and lose on the narrow ones (fewer waves)
-    const int64_t blocks = (groups + gr - 1) / gr;
-    ks = blocks <= 640 ? 4 : (blocks <= 1280 ? 2 : 1);
+    ks = groups <= 640 ? 4 : (groups <= 1280 ? 2 : 1);
 }
 
-template <int MODE, int GR>
-int launch_gemv_mfma_gr(GemvArgs& g, int64_t units, bool prenorm, hipStream_t s) {
-    const int64_t blocks = ((units + 3) / 4 + GR - 1) / GR;
+template <int MODE>
+int launch_gemv_mfma(GemvArgs& g, int64_t units, bool prenorm, hipStream_t s) {
+    gemv_mfma_shape(units, g.ks);
+    const int64_t blocks = (units + 3) / 4;
     const int bpw = (NT / 64) / g.ks;
     const unsigned grid = (unsigned)((blocks + bpw - 1) / bpw);
     if (prenorm) {
@@ -483,48 +484,38 @@ int launch_gemv_mfma_gr(GemvArgs& g, int64_t units, bool prenorm, hipStream_t s)
         const int lds = g.M * g.xs_stride;
         if (lds > 140 * 1024) return MM355_EUNSUPPORTED;
         static std::atomic<uint64_t> ok{0};                  // (one opt-in per device, to the largest size any call may ask for)
-        if (mm_ensure_dynamic_lds((const void*)gemv_mfma_kernel<MODE, true, GR>, 140 * 1024, ok) != MM355_OK) return MM355_ELAUNCH;
-        hipLaunchKernelGGL((gemv_mfma_kernel<MODE, true, GR>), dim3(grid), dim3(NT), lds, s, g);
-    } else {
-        if constexpr (GR == 1) {                             // weights coalesced + re-laid out through LDS, x rows through LDS windows
-            // measured (profiles/r5_gemv_rows.log): the windows win wherever the waves of a workgroup share one K range (wide weights:
-            // gate|up 47 -> 42 us at 8 rows, 53 -> 42 at 16, lm_head 208 -> 174) and, with K split over the waves, from nine rows on
-            // (down 26.8 -> 23.6 at 16); below that the per-block barriers of four slices cost more than the L2 reads they replace
-            if (g.M > 16) {                                // 17 .. 32 rows: two x row groups per workgroup, shapes with one K range per workgroup only
-                if constexpr (MODE == 2) return MM355_EUNSUPPORTED;
-                else {
-                    if (g.ks != 1 || g.M > 32) return MM355_EUNSUPPORTED;
-                    static std::atomic<uint64_t> ok2{0};
-                    constexpr int XL2 = 2 * 1 * 16 * 2 * 544;
-                    if (mm_ensure_dynamic_lds((const void*)gemv_mfma_kernel<MODE, false, 1, true, 1, 2>, XL2, ok2) != MM355_OK) return MM355_ELAUNCH;
-                    hipLaunchKernelGGL((gemv_mfma_kernel<MODE, false, 1, true, 1, 2>), dim3(grid), dim3(NT), XL2, s, g);
-                    return mm_launch_status();
-                }
-            }
-            if (g.ks > 1 && g.M <= 8) { hipLaunchKernelGGL((gemv_mfma_kernel<MODE, false, 1, true>), dim3(grid), dim3(NT), 0, s, g); return mm_launch_status(); }
-            const int xlds = 2 * g.ks * 16 * 544;
-#define GX(KSC) do { static std::atomic<uint64_t> okx{0};                                                                                      \
-                if (mm_ensure_dynamic_lds((const void*)gemv_mfma_kernel<MODE, false, 1, true, KSC>, 2 * 4 * 16 * 544, okx) != MM355_OK) return MM355_ELAUNCH; \
-                hipLaunchKernelGGL((gemv_mfma_kernel<MODE, false, 1, true, KSC>), dim3(grid), dim3(NT), xlds, s, g); } while (0)
-            if (g.ks == 4) GX(4); else if (g.ks == 2) GX(2); else GX(1);
-#undef GX
-        } else {
-            hipLaunchKernelGGL((gemv_mfma_kernel<MODE, false, GR>), dim3(grid), dim3(NT), 0, s, g);
+        if (mm_ensure_dynamic_lds((const void*)gemv_mfma_kernel<MODE, true>, 140 * 1024, ok) != MM355_OK) return MM355_ELAUNCH;
+        hipLaunchKernelGGL((gemv_mfma_kernel<MODE, true>), dim3(grid), dim3(NT), lds, s, g);
+        return mm_launch_status();
+    }
+    // weights coalesced + re-laid out through LDS, x rows through LDS windows
+    // measured (profiles/r5_gemv_rows.log): the windows win wherever the waves of a workgroup share one K range (wide weights:
+    // gate|up 47 -> 42 us at 8 rows, 53 -> 42 at 16, lm_head 208 -> 174) and, with K split over the waves, from nine rows on
+    // (down 26.8 -> 23.6 at 16); below that the per-block barriers of four slices cost more than the L2 reads they replace
+    if (g.M > 16) {                                        // 17 .. 32 rows: two x row groups per workgroup, shapes with one K range per workgroup only
+        if constexpr (MODE == 2) return MM355_EUNSUPPORTED;
+        else {
+            if (g.ks != 1 || g.M > 32) return MM355_EUNSUPPORTED;
+            static std::atomic<uint64_t> ok2{0};
+            constexpr int XL2 = 2 * 1 * 16 * 2 * 544;
+            if (mm_ensure_dynamic_lds((const void*)gemv_mfma_kernel<MODE, false, true, 1, 2>, XL2, ok2) != MM355_OK) return MM355_ELAUNCH;
+            hipLaunchKernelGGL((gemv_mfma_kernel<MODE, false, true, 1, 2>), dim3(grid), dim3(NT), XL2, s, g);
+            return mm_launch_status();
         }
     }
+    if (g.ks > 1 && g.M <= 8) { hipLaunchKernelGGL((gemv_mfma_kernel<MODE, false, true>), dim3(grid), dim3(NT), 0, s, g); return mm_launch_status(); }
+    const int xlds = 2 * g.ks * 16 * 544;
+#define GX(KSC) do { static std::atomic<uint64_t> okx{0};                                                                                      \
+        if (mm_ensure_dynamic_lds((const void*)gemv_mfma_kernel<MODE, false, true, KSC>, 2 * 4 * 16 * 544, okx) != MM355_OK) return MM355_ELAUNCH; \
+        hipLaunchKernelGGL((gemv_mfma_kernel<MODE, false, true, KSC>), dim3(grid), dim3(NT), xlds, s, g); } while (0)
+    if (g.ks == 4) GX(4); else if (g.ks == 2) GX(2); else GX(1);
+#undef GX
     return mm_launch_status();
 }
 
 // the MFMA kernel addresses weights and x rows with 32-bit buffer offsets, and marks a skipped prefetch by setting the top four bits
 bool gemv_mfma_addressable(int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldw) {
     return (N - 1) * ldw * 2 + K * 2 < 0xf0000000ll && (M - 1) * ldx * 2 + K * 2 < 0xf0000000ll;
-}
-
-template <int MODE>
-int launch_gemv_mfma(GemvArgs& g, int64_t units, bool prenorm, hipStream_t s) {
-    int gr;
-    gemv_mfma_shape(units, gr, g.ks);                        // (gr is 1: two / four groups of 16 rows per wave were measured and bought nothing; the kernel keeps the parameter)
-    return launch_gemv_mfma_gr<MODE, 1>(g, units, prenorm, s);
 }
 
 // ------------------------------------------------------------------------------------------------ up to four rows: x in LDS, weights alone in the queue
@@ -875,7 +866,7 @@ extern "C" int mm355_gemv_bf16(const mm355_bf16* x, int64_t ldx, const mm355_bf1
                                int64_t K, const mm355_bf16* bias, const mm355_bf16* residual, int64_t ldr, uint32_t flags, void* stream) {
     (void)hipGetLastError();   // drop any stale, unrelated runtime status before we launch
     if (!x || !W || !y || M <= 0 || N <= 0 || K <= 0) return MM355_EINVAL;
-    if (M > 32) return MM355_EUNSUPPORTED;                   // more rows: mm355_gemm_bf16 (17 .. 32: wide weights only, see launch_gemv_mfma_gr)
+    if (M > 32) return MM355_EUNSUPPORTED;                   // more rows: mm355_gemm_bf16 (17 .. 32: wide weights only, see launch_gemv_mfma)
     if ((K & 7) || (ldx & 7) || (ldw & 7) || !mm_aligned16(x) || !mm_aligned16(W)) return MM355_EINVAL;
     if ((flags & MM355_GEMM_BIAS) && !bias) return MM355_EINVAL;
     if ((flags & MM355_GEMM_RESIDUAL) && !residual) return MM355_EINVAL;

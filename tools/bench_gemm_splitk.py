@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """mm355_gemm_splitk_bf16 on the decode-wide / prompt-pass shapes (ROWS rows against the LLaMA-3-8B projections), weights rotated so that
-nothing stays in L2 / MALL between launches.  With MM355_LIB_PATH=build/splitk_<name>/libmm355.so: the timing builds of tools/build_splitk_tune.sh."""
+nothing stays in L2 / MALL between launches.  MM355_LIB_PATH=<path>/libmm355.so times another build of the library (A/B of two builds)."""
 import os, sys, statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -32,15 +32,13 @@ SDPA sees -- and the softmax scale enters on the fp32 side: P = exp2((scale * lo
 of its `v_exp_f32` (the constant sits in an SGPR).  Rounds 1-4 multiplied q by scale * log2 e and re-rounded it to bf16 before
 the MFMA: one rounding more than the reference has, a score error that grows with |s| (measured: 3x the error of a textbook bf16 flash
 attention at |s| = 50).  Costs 64 multiplies per tile.  They are PLAIN `v_mul_f32`, not `v_pk_mul_f32`: between MFMAs a
-packed-fp32 instruction costs ~22 cycles here against ~3.5 for a plain one (measured with the timing ablations `--abl noscl / noadd /
-sclscalar`: 32 v_pk_mul_f32 = +700 cycles per tile, 64 v_mul_f32 = +220); the same holds for `v_pk_add_f32`, so the row sums stay scalar.
+packed-fp32 instruction costs ~22 cycles here against ~3.5 for a plain one (measured, profiles/r5_attn4_packed_fp32.log:
+32 v_pk_mul_f32 = +700 cycles per tile, 64 v_mul_f32 = +220); the same holds for `v_pk_add_f32`, so the row sums stay scalar.
 `safe_*` are the same streams with every LDS read waited for at once and every MFMA followed by 32 wait states: the debugging build that
 separates a placement / hazard defect from a logic defect (tools/bench_attn4.py runs both).
 """
 import os
-import sys
 
-ABL = set()                                                  # timing-only ablations (--abl a,b,...): the build is WRONG by construction
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "metamorph_amd", "csrc", "attn4_gen")
 TILE = 16384
 O_A, Q_A, KRING_A, VRING_A = 0, 128, 192, 224
@@ -112,7 +110,7 @@ class Stream:
         return self.issued
 
     def wait(self, ident):
-        if ident <= self.done or "nolds" in ABL:
+        if ident <= self.done:
             return
         n = min(self.issued - ident, 15)
         self.asm("s_waitcnt lgkmcnt(%d)" % n)
@@ -239,8 +237,6 @@ def gen(mode, par, safe):
 
     def do_filler(f):
         kind = f[0]
-        if ("no" + kind) in ABL or (kind in ("kread", "vread", "kpre") and "nolds" in ABL):
-            return
         if kind == "exp":
             _, kb, qb, r = f
             v = s_blk(par, kb, qb) + r
@@ -327,8 +323,7 @@ def gen(mode, par, safe):
                 st.wait(kread_id.get((ks, 1), 0))
             d = vreg(s_blk(nxt, kb, qb), 16)
             src_c = d if ks else ("0" if head else vreg(nm_blk(qb), 16))
-            if "nomfma" not in ABL:
-                st.asm("v_mfma_f32_32x32x16_bf16 %s, %s, %s, %s" % (d, areg(k_frag(ks, kb), 4), areg(q_frag(qb, ks), 4), src_c))
+            st.asm("v_mfma_f32_32x32x16_bf16 %s, %s, %s, %s" % (d, areg(k_frag(ks, kb), 4), areg(q_frag(qb, ks), 4), src_c))
             st.mfma_pad()
         for f in a_fill[a]:
             do_filler(f)
@@ -373,15 +368,14 @@ def gen(mode, par, safe):
     counts = []
     for b in range(32):
         n0 = len(st.lines)
-        if b == 24 and "nobar" not in ABL:
+        if b == 24:
             st.raw("ATTN4_BARRIER();")
         if pv:
             kstep, db, qb = b >> 3, (b >> 1) & 3, b & 1
             if qb == 0 and db % 2 == 0:                      # one wait per pair of d-blocks
                 st.wait(vread_id.get((kstep, db + 1), 0))
             d = areg(o_blk(db, qb), 16)
-            if "nomfma" not in ABL:
-                st.asm("v_mfma_f32_32x32x16_bf16 %s, %s, %s, %s" % (d, areg(v_frag(kstep, db), 4), vreg(p_frag(kstep, qb), 4), d))
+            st.asm("v_mfma_f32_32x32x16_bf16 %s, %s, %s, %s" % (d, areg(v_frag(kstep, db), 4), vreg(p_frag(kstep, qb), 4), d))
             st.mfma_pad()
         if b == 1 and mx:
             emit_mask(st, nxt)
@@ -389,7 +383,7 @@ def gen(mode, par, safe):
             do_filler(f)
         counts.append(len(st.lines) - n0)
     st.stats.append(("B", counts))
-    if mx and not ("nodecide" in ABL and not head):
+    if mx:
         emit_decide(st, nxt, head)
     return st
 
@@ -441,12 +435,6 @@ def gen_q_pre01():
 
 
 def main():
-    global OUT
-    if "--abl" in sys.argv:
-        names = sys.argv[sys.argv.index("--abl") + 1]
-        ABL.update(names.split(","))
-        # ablation streams are scratch: build/<dir>/ (git-ignored), never next to the product streams
-        OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "build", "attn4_abl", "attn4_gen_" + names.replace(",", "_"))
     os.makedirs(OUT, exist_ok=True)
     report = []
     for safe in (False, True):

@@ -31,10 +31,8 @@ by scale * log2 e (K~ in the dK / dV kernel, Q~ in the dQ kernel -- so the two k
 P from the same q, k): one rounding more than the reference has, with a score error growing with |s|.
 """
 import os
-import sys
 
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "metamorph_amd", "csrc", "attn4_bwd_gen")
-ABL = set()
 
 
 def areg(lo, n):
@@ -109,7 +107,7 @@ class Stream:
         return self.issued
 
     def wait(self, ident):
-        if ident <= self.done or "nolds" in ABL:
+        if ident <= self.done:
             return
         n = min(self.issued - ident, 15)
         self.asm("s_waitcnt lgkmcnt(%d)" % n)
@@ -260,8 +258,6 @@ def gen(K, mode, u4, safe):
 
     def do_filler(f):
         kind = f[0]
-        if ("no" + kind.rstrip("01")) in ABL or (kind in ("aread", "tread", "apre", "preload") and "nolds" in ABL):
-            return
         if kind == "exp":
             kstep, i, r = elem(f[1])
             v = K.x(par, i) + r
@@ -308,8 +304,7 @@ def gen(K, mode, u4, safe):
             else:
                 c = d
             pers = (K.PERS0 if j < 2 else K.PERS1) + 4 * ks
-            if "nomfma" not in ABL:
-                st.asm("v_mfma_f32_32x32x16_bf16 %s, %s, %s, %s" % (d, areg(K.RINGA + 4 * (a % 8), 4), areg(pers, 4), c))
+            st.asm("v_mfma_f32_32x32x16_bf16 %s, %s, %s, %s" % (d, areg(K.RINGA + 4 * (a % 8), 4), areg(pers, 4), c))
             st.mfma_pad()
         for f in a_fill[a]:
             do_filler(f)
@@ -333,7 +328,7 @@ def gen(K, mode, u4, safe):
     counts = []
     for b in range(NB):
         n0 = len(st.lines)
-        if b == K.BAR and not tail and "nobar" not in ABL:
+        if b == K.BAR and not tail:
             st.raw("BWD_BARRIER();")
         if va:
             st.wait(tread_id.get(b, 0))
@@ -345,8 +340,7 @@ def gen(K, mode, u4, safe):
                 kstep, db = b >> 2, b & 3
                 acc = K.ACC0 + 16 * db
                 pk = K.PK1 + 4 * kstep
-            if "nomfma" not in ABL:
-                st.asm("v_mfma_f32_32x32x16_bf16 %s, %s, %s, %s" % (areg(acc, 16), areg(K.RINGT + 4 * (b % 8), 4), vreg(pk, 4), areg(acc, 16)))
+            st.asm("v_mfma_f32_32x32x16_bf16 %s, %s, %s, %s" % (areg(acc, 16), areg(K.RINGT + 4 * (b % 8), 4), vreg(pk, 4), areg(acc, 16)))
             st.mfma_pad()
         for f in b_fill[b]:
             do_filler(f)
@@ -409,12 +403,6 @@ def gen_tuple_write(K):
 
 
 def main():
-    global OUT
-    if "--abl" in sys.argv:
-        names = sys.argv[sys.argv.index("--abl") + 1]
-        ABL.update(names.split(","))
-        # ablation streams are scratch: build/<dir>/ (git-ignored), never next to the product streams
-        OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "build", "attn4_abl", "attn4_bwd_gen_" + names.replace(",", "_"))
     os.makedirs(OUT, exist_ok=True)
     report = []
     for kname in ("kv", "q"):
