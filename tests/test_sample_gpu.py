@@ -6,53 +6,9 @@ import pytest
 import torch
 
 import test_greedy_batch_gpu as G  # noqa: E402  (the tiny fixture models)
+from sample_refs import DEV, FAMILIES, SETTINGS, U_MAX, check_row, device_draw, family  # noqa: E402  (shared with the edge tests)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-EPS = 1e-4               # the host model's band: an fp32 tree sum of a row is within ~3e-5 * Z of exact
-U_MAX = 1.0 - 2.0 ** -24
-#           T   top_k top_p
-SETTINGS = [(1.0, 0, 1.0), (0.7, 0, 0.9), (0.7, 50, 1.0), (1.3, 40, 0.95), (0.7, 1, 1.0)]
-FAMILIES = ("peaked", "flat", "ties", "-inf entries", "all equal", "spike")
-
-
-def f32(v):
-    return float(np.float32(v))
-
-
-def family(name, R, C, g):
-    x = torch.randn(R, C, generator=g)
-    if name == "peaked":
-        return x * 4.0
-    if name == "ties":
-        return torch.round(x * 4.0) / 2.0
-    if name == "-inf entries":
-        x[torch.rand(R, C, generator=g) < 0.3] = float("-inf")
-        x[:, C // 2] = 0.25                                      # (no row of -inf alone)
-    if name == "all equal":
-        return torch.full((R, C), 1.25)
-    if name == "spike":
-        x[torch.arange(R), (torch.arange(R) * 7919 + C // 3) % C] = 80.0
-    return x
-
-
-def device_draw(x, T, top_k, top_p, u):
-    from metamorph_amd import ops
-    stats = torch.full((x.shape[0], 2), -1.0, device=DEV)
-    out = ops.sample_rows(x.to(DEV).contiguous(), f32(1.0 / T), top_k, f32(top_p), u.to(DEV), stats=stats)
-    assert out.dtype == torch.int32
-    return out.cpu().tolist(), stats.cpu().double().numpy()
-
-
-def check_row(row, T, top_k, top_p, u, out, tau, Z, who):
-    """one row of the device's answer against the host model; returns the number of candidates"""
-    from metamorph_amd import functional as F
-    cand, lo, hi, Zh = F.sample_row_host(row, f32(1.0 / T), top_k, f32(top_p), u, eps=EPS, tau=tau)
-    assert bool((row == tau).any()), (who, "tau is no value of the row", tau)
-    assert lo <= tau <= hi, (who, "tau out of the band", tau, lo, hi)
-    assert abs(Z - Zh) <= 1e-4 * Zh, (who, "Z", Z, Zh)
-    assert out in cand, (who, "pick", out, cand, u)
-    return len(cand)
 
 
 @pytest.mark.parametrize("R,C", [(R, C) for C in (37, 1000) for R in (1, 3, 17)] + [(3, 128258)])
